@@ -13,6 +13,15 @@ backward (CSR transpose aggregations, gathered weight-gradient GEMM) ->
 value = sampled edges of all ranks in the K timed steps / max-over-ranks wall
 time.  Inputs are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps and prints the line (the
+roofline in it comes from HIP events inside those same steps).  `--full` adds
+every measurement that takes a run of its own: full epochs, the
+training-stream-alone probe, the GPU sampler alone, the secondary orders /
+arithmetic / generator stream (child runs) and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step left with its caller
+(loss, updated weights, the sampled batch) as DIR/<name>.npy; the inputs are
+generated from fixed seeds, so two builds can be compared output for output.
+
 Multi-GPU: `python bench.py --gpus N` starts `python -m torch.distributed.run
 --nproc-per-node N bench.py --gpus N ...` as a child process (before anything
 touches the GPU), relays rank 0's JSON line and exits with the child's status;
@@ -206,7 +215,7 @@ _CHILD_DROP = {"--secondary": False, "--no-secondary-exact": False, "--no-second
                "--no-secondary-af": False, "--gpus": True, "--no-cpu-baseline": False,
                "--cpu-threads": True, "--cpu-max-steps": True, "--cpu-o0-steps": True,
                "--epochs": True, "--sampler-batches": True, "--no-interference-probe": False,
-               "--launch-selftest": False}
+               "--launch-selftest": False, "--full": False, "--dump-outputs": True}
 
 
 def child_argv(argv: list, overrides: dict) -> list:
@@ -235,6 +244,16 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: --epochs full epochs, "
+                        "the training-stream-alone probe, the GPU sampler alone "
+                        "(--sampler-batches), the secondary measurements (child runs) and the "
+                        "CPU baseline; their own flags apply only with --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last of them computed (loss, "
+                        "updated weights, the sampled batch's arrays) as DIR/<name>.npy, float32 "
+                        "or float64; a fixed seeded sample of any array too large for the "
+                        "48 MiB total")
     p.add_argument("--shape", default="reddit")
     p.add_argument("--batch", type=int, default=10000)
     p.add_argument("--fanout", default="25-10")
@@ -346,6 +365,49 @@ def lib_sha256() -> str:
     return hashlib.sha256(_abi.LIB_PATH.read_bytes()).hexdigest()
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together
+_LAYER_ARRAYS = ("destination", "column_offset", "row_indices", "sample_ans", "source",
+                 "edge_weight_forward", "row_offset", "column_indices", "edge_weight_backward")
+
+
+def _dump_array(t) -> np.ndarray:
+    """A device tensor as float32 (floating point) or float64 (the integer
+    arrays hold unsigned ids / offsets in signed storage: exact in float64)."""
+    a = t.detach().cpu().contiguous().numpy()
+    if a.dtype.kind == "i":
+        a = a.view(a.dtype.str.replace("i", "u"))
+    return a.astype(np.float32 if a.dtype.kind == "f" else np.float64).reshape(-1)
+
+
+def dump_outputs(out: pathlib.Path, drv, rank: int) -> None:
+    """--dump-outputs: what the caller of the last timed train_batch() holds
+    afterwards — the loss, the updated weights and the batch it trained on
+    (every sampled layer's sizes and arrays, top down) — one .npy per array.
+    An array over its share of DUMP_BUDGET_BYTES is written as a fixed sample:
+    the elements at sorted indices drawn without replacement by
+    numpy.random.default_rng(0) (the same indices for the same length)."""
+    drv.synchronize()
+    arrays = {"loss": drv.loss.reshape(-1)}
+    for i, w in enumerate(drv.weights()):
+        arrays[f"weight_{i}"] = w
+    for l, lay in enumerate(drv.last_layers):
+        arrays[f"layer{l}_sizes"] = torch.tensor(
+            [int(lay["v_size"]), int(lay["src_size"]), int(lay["e_size"])], dtype=torch.int64)
+        for k in _LAYER_ARRAYS:
+            if lay.get(k) is not None:
+                arrays[f"layer{l}_{k}"] = lay[k]
+    out.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, t in arrays.items():
+        a = _dump_array(t)
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(out / f"{name}{suffix}.npy", a)
+    log(f"[bench] outputs of the last timed step written to {out} ({len(arrays)} arrays)")
+
+
 def main():
     args = parse()
     bad = diag_env()
@@ -401,7 +463,9 @@ def main():
     if args.train_limit > 0:
         train = train[:args.train_limit]
     log(f"[bench] graph {args.shape}: V={V} E={En} F={F_dim} C={C}  ready in {time.time()-t0:.1f}s")
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.secondary
+    # the measurements beside the headline's own (--full; never in a secondary child)
+    extras = args.full and not args.secondary
+    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and extras
     src_host = g.src.cpu().numpy().view(np.uint32) if want_cpu else None
     dst_host = g.dst.cpu().numpy().view(np.uint32) if want_cpu else None
     del g
@@ -505,9 +569,11 @@ def main():
     # sizes of the last timed batch (before the epoch runs replace them)
     layer_sizes = [{"v": int(l["v_size"]), "src": int(l["src_size"]), "e": int(l["e_size"])}
                    for l in drv.last_layers]
+    if args.dump_outputs:
+        dump_outputs(pathlib.Path(args.dump_outputs), drv, rank)
     # ---- epoch time (mean of epochs 2..N) ----------------------------
     epoch_times = []
-    for _ in range(0 if args.secondary else max(args.epochs, 0)):
+    for _ in range(max(args.epochs, 0) if extras else 0):
         drv.restart()
         barrier()
         te = time.perf_counter()
@@ -529,7 +595,7 @@ def main():
     # ---- diagnostic: the training stream without the sampler beside it -----------
     alone = None
     if (args.model == "gcn" and not args.no_interference_probe and args.steps > 0
-            and not args.secondary
+            and extras
             and not args.no_pipeline):
         drv.set_diag_reuse_sample(True)
         for _ in range(args.warmup):
@@ -556,7 +622,7 @@ def main():
 
     # ---- GPU sampler alone (SURVEY §8d sampler-only rate) -------------------------
     sampler_only = None
-    if args.sampler_batches > 0 and args.model == "gcn" and not args.secondary:
+    if args.sampler_batches > 0 and args.model == "gcn" and extras:
         L = len(fan)
         csr = [not args.atomic_backward] * (L - 1) + [tf]
         wt = {"sum": E.WeightType.Sum, "mean": E.WeightType.Mean,
@@ -602,7 +668,7 @@ def main():
     secondary = None  # the reference's bottom-layer order
     pair_tf = None    # the headline order on the f16 pair tables (22-bit inputs)
     mt_ref = None     # the reference's generator stream
-    if (tf and args.model == "gcn" and args.steps > 0 and world == 1 and not args.secondary):
+    if (tf and args.model == "gcn" and args.steps > 0 and world == 1 and extras):
         if not args.no_secondary_af:
             secondary = {
                 "bottom_layer": "aggregate-first (A X) W, the reference's order: fp32 aggregation "
@@ -619,7 +685,7 @@ def main():
     # the same workload on the reference's own generator stream (std::mt19937
     # + Lemire, every sampled array bit-exact vs the reference's serial order)
     if (args.model == "gcn" and args.rng == "philox" and world == 1 and args.steps > 0
-            and not args.no_secondary_mt and not args.secondary):
+            and not args.no_secondary_mt and extras):
         mt_ref = {
             "rng": "std::mt19937(2000) + Lemire, the reference's stream (FastSampler::sample_fast)",
             **child_secondary({"--rng": "mt"},

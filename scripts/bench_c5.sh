@@ -7,7 +7,7 @@ O=gpurun_out/c5_${1:-a}
 mkdir -p $O
 run() {
   local tag=$1; shift
-  timeout -k 10 700 python -u bench.py --no-cpu-baseline --shape papers100m --layers 128-256-256-172 --fanout 15-10-5 --batch 1024 --weight mean --steps 20 --warmup 5 --epochs 0 --sampler-batches 8 "$@" > $O/$tag.json 2> $O/$tag.err || { echo "bench $tag failed"; tail -5 $O/$tag.err; exit 1; }
+  timeout -k 10 700 python -u bench.py --full --no-cpu-baseline --shape papers100m --layers 128-256-256-172 --fanout 15-10-5 --batch 1024 --weight mean --steps 20 --warmup 5 --epochs 0 --sampler-batches 8 "$@" > $O/$tag.json 2> $O/$tag.err || { echo "bench $tag failed"; tail -5 $O/$tag.err; exit 1; }
   python3 -c "
 import json
 d=json.loads(open('$O/$tag.json').read().strip().splitlines()[-1]); c=d['config']

@@ -5,7 +5,7 @@ O=gpurun_out/configs_${1:-a}
 mkdir -p $O
 run() {
   local tag=$1; shift
-  timeout -k 10 400 python -u bench.py --no-cpu-baseline --sampler-batches 16 "$@" > $O/$tag.json 2> $O/$tag.err || { echo "bench $tag failed"; tail -5 $O/$tag.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --sampler-batches 16 "$@" > $O/$tag.json 2> $O/$tag.err || { echo "bench $tag failed"; tail -5 $O/$tag.err; exit 1; }
   python3 -c "
 import json
 d=json.loads(open('$O/$tag.json').read().strip().splitlines()[-1]); c=d['config']

@@ -19,8 +19,8 @@ fi
 grep -E "passed|failed|s call" $O/tests.log | head -16
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
-timeout -k 10 300 python -u bench.py --transform-first 0 --no-cpu-baseline --epochs 1 --sampler-batches 0 > $O/bench_af.json 2> $O/bench_af.err || { echo "bench af failed"; tail -20 $O/bench_af.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --transform-first 0 --no-cpu-baseline --epochs 1 --sampler-batches 0 > $O/bench_af.json 2> $O/bench_af.err || { echo "bench af failed"; tail -20 $O/bench_af.err; exit 1; }
 python - <<PY
 import json
 for f in ("$O/bench.json", "$O/bench_af.json"):

@@ -160,12 +160,14 @@ def test_child_argv_keeps_the_workload(bench):
     replace the parent's value of the same flag."""
     argv = ["--rng", "mt", "--no-pad-features", "--cache-rate", "0.3", "--steps", "7",
             "--transform-first=1", "--no-secondary-mt", "--gpus", "1", "--cpu-threads", "4",
-            "--epochs", "2", "--sampler-gate", "1"]
+            "--epochs", "2", "--sampler-gate", "1", "--full", "--dump-outputs", "somewhere"]
     out = bench.child_argv(argv, {"--transform-first": 0, "--pair-table": 0})
     assert out[:7] == ["--rng", "mt", "--no-pad-features", "--cache-rate", "0.3", "--steps", "7"]
     assert "--transform-first=1" not in out and out.count("--transform-first") == 1
     assert out[out.index("--transform-first") + 1] == "0" and out[out.index("--pair-table") + 1] == "0"
-    for gone in ("--no-secondary-mt", "--gpus", "--cpu-threads", "--epochs"):
+    # (a child neither repeats the parent's --full extras nor overwrites its dump)
+    for gone in ("--no-secondary-mt", "--gpus", "--cpu-threads", "--epochs", "--full",
+                 "--dump-outputs", "somewhere"):
         assert gone not in out
     assert out[-1] == "--secondary" and out[out.index("--sampler-gate") + 1] == "1"
     mt = bench.child_argv(["--rng", "philox", "--no-pad-features"], {"--rng": "mt"})
@@ -195,3 +197,108 @@ def test_host_extension_env_knobs():
         pytest.skip("nts_host_ext.so not built")
     names = set(m.group(1).decode() for m in re.finditer(rb"\x00(NTS_[A-Z0-9_]+)\x00", ext.read_bytes()))
     assert names <= {"NTS_HOST_PROFILE", "NTS_TIMELINE"}, names
+
+
+class _FakeDriver:
+    """What dump_outputs reads of the driver, on CPU tensors."""
+
+    def __init__(self, e):
+        import torch
+        g = torch.Generator().manual_seed(1)
+        self.loss = torch.tensor(1.25)
+        self._w = [torch.randn(6, 4, generator=g), torch.randn(4, 3, generator=g)]
+        ids = torch.arange(e, dtype=torch.int64)
+        self.last_layers = [{"v_size": 3, "src_size": 5, "e_size": e,
+                             "destination": torch.tensor([-1, 7, 9], dtype=torch.int32),
+                             "row_indices": ids.to(torch.int32),
+                             "edge_weight_forward": ids.to(torch.float32) / 8, "row_offset": None}]
+
+    def synchronize(self):
+        pass
+
+    def weights(self):
+        return [w.clone() for w in self._w]
+
+
+def test_dump_outputs_writes_the_last_step_within_the_budget(bench, monkeypatch, tmp_path):
+    """--dump-outputs: one .npy per array in float32 / float64 (unsigned ids
+    exact), an array over its share of the budget as the same seeded sample
+    every time, everything together within the budget."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 6 * 4096)
+    e = 5000
+    drv = _FakeDriver(e)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, drv, 0)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["layer0_destination.npy", "layer0_edge_weight_forward.npy",
+                     "layer0_row_indices.npy", "layer0_sizes.npy", "loss.npy", "weight_0.npy",
+                     "weight_1.npy"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")) for k, v in got.items())
+    assert {v.dtype for v in got.values()} == {np.dtype(np.float32), np.dtype(np.float64)}
+    assert sum(v.nbytes for v in got.values()) <= 6 * 4096
+    assert got["loss"].tolist() == [1.25] and got["layer0_sizes"].tolist() == [3, 5, e]
+    assert np.array_equal(got["weight_0"], drv._w[0].numpy().reshape(-1))
+    assert got["layer0_destination"].tolist() == [2.0 ** 32 - 1, 7, 9]  # uint32 ids
+    # the sampled arrays: the same sorted indices for the same length
+    idx = got["layer0_row_indices"]
+    share = 6 * 4096 // 7
+    assert idx.dtype == np.float64 and idx.size == share // 8
+    assert np.all(np.diff(idx) > 0) and idx[-1] < e
+    w = got["layer0_edge_weight_forward"]
+    assert w.dtype == np.float32 and w.size == share // 4
+    assert np.all(np.diff(w) > 0) and w[-1] * 8 < e and np.array_equal(w * 8, np.round(w * 8))
+    # a second rank's files do not collide with rank 0's
+    bench.dump_outputs(tmp_path / "a", drv, 1)
+    assert (tmp_path / "a" / "loss_rank1.npy").exists()
+
+
+def _bench_line(args):
+    r = _run_bench(args)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0]), r.stderr
+
+
+_TINY = ["--gpus", "1", "--shape", "tiny", "--batch", "128", "--steps", "3", "--warmup", "1"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain run times its steps and prints the line, nothing more; --full
+    adds the epochs, the training-stream-alone probe and the GPU sampler alone
+    (the secondaries' child runs are left out here for time: their argv is
+    checked above), and leaves what the timed path computes unchanged:
+    both runs' --dump-outputs files are equal array for array."""
+    import numpy as np
+    plain, err = _bench_line(_TINY + ["--dump-outputs", str(tmp_path / "plain")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    c = plain["config"]
+    assert "cpu_baseline" not in plain and c["epoch_times_s"] == []
+    assert c["training_stream_alone"] is None and c["gpu_sampler_only"] is None
+    assert c["reference_stream_secondary"] is None and "secondary" not in err
+    assert c["epoch_time_kind"] == "ms_per_step x batches/epoch"
+
+    full, err = _bench_line(_TINY + ["--full", "--epochs", "1", "--sampler-batches", "2",
+                                     "--no-cpu-baseline", "--no-secondary-mt",
+                                     "--dump-outputs", str(tmp_path / "full")])
+    c = full["config"]
+    assert len(c["epoch_times_s"]) == 1 and c["training_stream_alone"]["steps"] == 3
+    assert c["gpu_sampler_only"]["value"] > 0
+    assert full["metric"] == plain["metric"] and full["dtype"] == plain["dtype"]
+
+    names = sorted(p.name for p in (tmp_path / "plain").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "full").iterdir())
+    assert {"loss.npy", "weight_0.npy", "weight_1.npy", "layer0_sizes.npy",
+            "layer1_row_indices.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert 0 < total <= 64 << 20
+    assert np.isfinite(np.load(tmp_path / "plain" / "loss.npy")).all()
