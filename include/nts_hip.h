@@ -292,6 +292,22 @@ int nts_hip_spmm_csc_fwd(nts_hip_ctx *ctx, const uint32_t *column_offset,
                          const uint32_t *v, uint32_t v_cap, const float *x, uint64_t ldx,
                          const uint32_t *x_row_map, uint32_t feature_size, float *y,
                          uint64_t ldy);
+/* Full-neighbour aggregation over the GLOBAL CSC of `graph` (u64 offsets,
+ * global ids on both sides) — layer-wise inference over the whole graph:
+ *   Y[d,:] = (relu?)( sum_{e in [co[d],co[d+1])} w(e) * X[row_indices[e],:] )
+ * for v_begin <= d < v_end, in nts_hip_spmm_csc_fwd's arithmetic (serial in
+ * CSC edge order, (x*w)+acc, no contraction, from 0).  w(e) is the weight
+ * nts_hip_sample_layer writes for that (src, dst) from the graph's degrees:
+ * NTS_WEIGHT_SUM, NTS_WEIGHT_MEAN, or 1 for NTS_WEIGHT_NONE; MEAN_SAMPLED and
+ * the UP_DEGREE bit are NTS_ERR_INVALID (they are properties of a sample).
+ * No per-edge weight array is built.  An empty column writes a zero row; rows
+ * outside [v_begin, v_end) are not touched; bit-identical from run to run.
+ * Uses the context's scratch arena (2 V floats + 2 (v_end - v_begin) words).
+ * The reference has no counterpart (its drivers score with sampled batches). */
+int nts_hip_spmm_graph_fwd(nts_hip_ctx *ctx, const nts_graph_dev *graph,
+                           uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
+                           const float *x, uint64_t ldx, uint32_t feature_size,
+                           float *y, uint64_t ldy);
 /* Stage the NON-cached rows of a layer's sources once into HBM:
  *   stage[i,:] = host_table[index[i],:]  for every i with cache_map[index[i]] ==
  *   NTS_NOT_CACHED (other rows of stage are left untouched).

@@ -93,6 +93,20 @@ inline uint32_t dropout_threshold(double p) {
   return p >= 1.0 ? 65536u : (uint32_t)std::min(p * 65536.0, 65536.0);
 }
 
+// Edge weights from the full-graph degrees (the sampler's relabel kernel and
+// the full-graph aggregation, infer.hip):
+// 1 / ((float)std::sqrt(out) * (float)std::sqrt(in)), nts_norm_degree
+// (core/ntsBaseOp.hpp:652-657): std::sqrt of an integer is the double sqrt.
+// degree_sqrt is one factor (tabulated per vertex by infer.hip),
+// norm_from_sqrt the weight from the two factors.
+__device__ __forceinline__ float degree_sqrt(uint32_t degree) { return (float)sqrt((double)degree); }
+__device__ __forceinline__ float norm_from_sqrt(float a, float b) { return 1.0f / (a * b); }
+__device__ __forceinline__ float norm_degree(uint32_t out_src, uint32_t in_dst) {
+  return norm_from_sqrt(degree_sqrt(out_src), degree_sqrt(in_dst));
+}
+// NTS_WEIGHT_MEAN: that weight over the dst's full-graph in-degree
+__device__ __forceinline__ float mean_weight(float w, uint32_t in_dst) { return w / (float)in_dst; }
+
 inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 inline uint32_t ceil_log2(uint64_t x) {
   uint32_t b = 0;

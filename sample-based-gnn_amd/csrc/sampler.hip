@@ -1499,13 +1499,7 @@ __global__ __launch_bounds__(kMarkThreads) void k_mark_write(
 }
 
 // ---- relabel + weights ------------------------------------------------------
-__device__ __forceinline__ float norm_degree(uint32_t out_src, uint32_t in_dst) {
-  // 1 / ((float)std::sqrt(out) * (float)std::sqrt(in)), nts_norm_degree
-  // (core/ntsBaseOp.hpp:652-657): std::sqrt of an integer is the double sqrt.
-  const float a = (float)sqrt((double)out_src);
-  const float b = (float)sqrt((double)in_dst);
-  return 1.0f / (a * b);
-}
+// (norm_degree / mean_weight: common.hpp, shared with the full-graph aggregation)
 
 // up_cnt != nullptr (UP_DEGREE): count the sampled edges per local src
 // instead of computing the weights (k_up_weight does, once counted).
@@ -1546,7 +1540,7 @@ __device__ __forceinline__ uint32_t relabel_one(const RelabelArgs& a, uint32_t k
     const uint32_t dg = a.dst[a.edst[k]];
     const uint32_t ind = a.in_deg[dg];
     float w = norm_degree(a.out_deg[g], ind);
-    if (a.weight_type == NTS_WEIGHT_MEAN) w = w / (float)ind;
+    if (a.weight_type == NTS_WEIGHT_MEAN) w = mean_weight(w, ind);
     if (a.weight_type == NTS_WEIGHT_MEAN_SAMPLED) w = w / (float)(a.co[a.edst[k] + 1] - a.co[a.edst[k]]);
     a.wf[k] = w;
   }

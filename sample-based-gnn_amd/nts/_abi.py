@@ -55,6 +55,7 @@ EXPORTED = (
     "nts_hip_csr_bwd_colmax_rows_per_part", "nts_hip_gemm_h2d_act",
     "nts_hip_act_bits_words", "nts_hip_spmm_csc_fwd_act_bits", "nts_hip_spmm_csr_bwd_postmask_bits",
     "nts_hip_mt_budget_scale", "nts_hip_mt_checkpoint", "nts_hip_mt_rewind",
+    "nts_hip_spmm_graph_fwd",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -119,6 +120,7 @@ def lib() -> C.CDLL:
         "nts_hip_gather_rows": ([P, P, U64, P, P, U32, U32, P, U64], I),
         "nts_hip_gather_labels": ([P, P, P, P, U32, P], I),
         "nts_hip_spmm_csc_fwd": ([P, P, P, P, P, U32, P, U64, P, U32, P, U64], I),
+        "nts_hip_spmm_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, I, I, P, U64, U32, P, U64], I),
         "nts_hip_spmm_csc_fwd_act": ([P, P, P, P, P, U32, P, U64, U32, P, U64, F, U64, U64], I),
         "nts_hip_spmm_csr_bwd_masked": ([P, P, P, P, P, U32, P, U64, P, U64, F, U32, P, U64], I),
         "nts_hip_spmm_csr_bwd_postmask": ([P, P, P, P, P, U32, P, U64, P, U64, F, U32, P, U64], I),

@@ -246,6 +246,9 @@ class InputInfo:
     up_degree: bool = False
     gpu_num: int = 1
     pre_sample_file: str = ""
+    # FULL_INFERENCE (this build's key, no reference counterpart): after the last
+    # epoch, score the final weights over the whole graph with full neighbourhoods
+    full_inference: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -270,6 +273,7 @@ class InputInfo:
             "PIPELINE_NUM": ("pipeline_num", int), "CACHE_RATE": ("cache_rate", float),
             "UP_DEGREE": ("up_degree", lambda s: bool(int(s))), "GPU_NUM": ("gpu_num", int),
             "PRE_SAMPLE_FILE": ("pre_sample_file", str),
+            "FULL_INFERENCE": ("full_inference", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -139,6 +139,17 @@ class HipContext:
                                             ptr(x), x.stride(0), ptr(row_map), F, ptr(y),
                                             y.stride(0)))
 
+    def spmm_graph_fwd(self, graph, x, y, weight_type, relu=False, v_begin=0, v_end=None):
+        """y[d] = (relu?)(sum over ALL in-edges of d of w(e) x[src(e)]) for
+        v_begin <= d < v_end over the global CSC of `graph` (a DeviceGraph);
+        the weights come from its degrees (NTS_WEIGHT_SUM / MEAN / NONE)."""
+        g = graph.as_struct()
+        if v_end is None:
+            v_end = graph.n_vertices
+        check(self.lib.nts_hip_spmm_graph_fwd(self.h, C.byref(g), int(v_begin), int(v_end),
+                                              int(weight_type), int(bool(relu)), ptr(x),
+                                              x.stride(0), x.shape[1], ptr(y), y.stride(0)))
+
     def spmm_csc_fwd_act(self, co, ri, w, v_dev, v_cap, x, y, p=0.0, seed=0, offset=0):
         """y = dropout(relu(A x), p) (transform-first bottom layer)."""
         F = x.shape[1]

@@ -805,6 +805,96 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
   return (double)(uint32_t)correct.cpu().item<int32_t>() / (double)nids.size();
 }
 
+// Full-neighbour layer-wise inference: each layer is one O(E) aggregation over
+// the global CSC plus one GEMM over all V rows, on the narrower side of the
+// layer.  Peak activation footprint V (F_l + F_{l+1}) 4 bytes.
+NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
+  TORCH_CHECK(!cfg.gat, "infer_full: GAT layers are not supported (GCN / GraphSAGE only)");
+  TORCH_CHECK(!cfg.up_degree,
+              "infer_full: UP_DEGREE weights are a property of a sample, not of the whole graph");
+  TORCH_CHECK(cfg.weight_type != WeightType::MeanSampled,
+              "infer_full: MeanSampled weights are a property of a sample, not of the whole graph");
+  TORCH_CHECK(!fcache, "infer_full: needs the whole feature table in HBM (cache_rate < 0)");
+  flush_update();
+  auto guard = cs->guard();
+  const int L = (int)P.size();
+  const int64_t V = (int64_t)graph->global_vertices;
+  const int wt = cfg.weight_type == WeightType::Sum    ? NTS_WEIGHT_SUM
+                 : cfg.weight_type == WeightType::Mean ? NTS_WEIGHT_MEAN
+                                                       : NTS_WEIGHT_NONE;
+  const nts_graph_dev g = graph->dev();
+  hipStream_t st = (hipStream_t)cs->stream();
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+  auto aggregate = [&](const NtsVar& x, bool relu) {
+    NtsVar xr = row_major(x);
+    NtsVar y = row_padded_empty(V, xr.size(1), graph->device);
+    if (cfg.profile) {
+      hipEvent_t a, b;
+      TORCH_CHECK(hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess,
+                  "hipEventCreate");
+      evs.push_back({a, b});
+      (void)hipEventRecord(a, st);
+    }
+    hip_check(nts_hip_spmm_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+                                     xr.data_ptr<float>(), (uint64_t)xr.stride(0),
+                                     (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                     (uint64_t)y.stride(0)),
+              "nts_hip_spmm_graph_fwd");
+    if (cfg.profile) (void)hipEventRecord(evs.back().second, st);
+    return y;
+  };
+  ctx.eval();
+  NtsVar X = F;
+  {
+    torch::NoGradGuard ng;
+    for (int l = 0; l < L; ++l) {
+      const bool last = l == L - 1;
+      const NtsVar& W = P[l]->W;
+      if (W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
+        NtsVar H = P[l]->forward(X);
+        NtsVar Y = aggregate(H, !last);
+        X = last ? Y.log_softmax(1) : Y;
+      } else {  // aggregate first: act((A X) W)
+        NtsVar Y = aggregate(X, false);
+        if (last)
+          X = P[l]->forward(Y).log_softmax(1);
+        else if (cfg.hip_gemm && cfg.fuse_activation)  // p = 0: no mask, no offset drawn
+          X = hip_linear_act(Y, W, 0.0, 0, 0, cs.get(), false);
+        else
+          X = torch::relu(P[l]->forward(Y));
+      }
+    }
+  }
+  ctx.train();
+  cs->synchronize();
+  full_agg_ms.clear();
+  for (auto& e : evs) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e.first, e.second);
+    full_agg_ms.push_back((double)ms);
+    (void)hipEventDestroy(e.first);
+    (void)hipEventDestroy(e.second);
+  }
+  return X;
+}
+
+double GCN_SAMPLE_ALLGPU_impl::evaluate_full(const std::vector<VertexId>& nids) {
+  NtsVar out = infer_full();
+  if (nids.empty()) return 0.0;
+  for (VertexId v : nids)
+    TORCH_CHECK((uint64_t)v < graph->global_vertices, "evaluate_full: vertex id ", v,
+                " >= vertex count ", graph->global_vertices);
+  auto guard = cs->guard();
+  torch::NoGradGuard ng;
+  NtsVar idx = torch::from_blob((void*)nids.data(), {(int64_t)nids.size()}, torch::kInt32)
+                   .to(torch::Device(torch::kCUDA, graph->device))
+                   .to(torch::kInt64);
+  // labels gathered and rows counted on the device; one scalar comes back
+  NtsVar n_ok = out.index_select(0, idx).argmax(1).eq(L_GT.index_select(0, idx)).sum();
+  const int64_t correct = n_ok.cpu().item<int64_t>();
+  return (double)correct / (double)nids.size();
+}
+
 // ---------------------------------------------------------------------------
 // PD cache
 std::pair<std::vector<uint32_t>, std::vector<uint32_t>> GCN_SAMPLE_ALLGPU_impl::presample() {

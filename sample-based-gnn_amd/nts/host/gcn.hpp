@@ -129,6 +129,18 @@ class GCN_SAMPLE_ALLGPU_impl {
   // training batch size, sampled like training (the reference's eval/test
   // samplers); returns correct / |nids|.
   double evaluate(const std::vector<VertexId>& nids);
+  // Full-neighbour layer-wise inference over the whole graph (no sampling; the
+  // reference has no counterpart): [V, C] log-softmax rows of every vertex in
+  // eval mode, layer by layer — hidden layers relu((A X) W), the last
+  // log_softmax((A X) W), A = nts_hip_spmm_graph_fwd under cfg.weight_type,
+  // each layer aggregated on its narrower side.  Deterministic: no RNG stream,
+  // sampler slot, eval_seq or dropout offset is touched.  Not for GAT,
+  // UP_DEGREE or a spilled feature table (cache_rate >= 0).
+  NtsVar infer_full();
+  // correct / |nids| of infer_full()'s argmax rows (counted on the device)
+  double evaluate_full(const std::vector<VertexId>& nids);
+  // cfg.profile: device ms of each layer's aggregation in the last infer_full()
+  std::vector<double> full_agg_ms;
   // PD cache: the hot vertices of every super-batch (preSample on the device,
   // per super-batch counts + their concatenated ids, the PRE_SAMPLE_FILE
   // layout), or replace them (e.g. read from a PRE_SAMPLE_FILE)

@@ -188,10 +188,21 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
             out(f"Eval Acc: {acc_val:f} {int(round(acc_val * ids['val'].size))} {ids['val'].size}")
             out(f"Test Acc: {acc_test:f} {int(round(acc_test * ids['test'].size))} {ids['test'].size}")
             out(f"GNNmini::Running.Epoch[{ep}]:Times[{rec['epoch_time_s']:f}(s)]:loss\t{loss:f}")
+    res = {"cfg": str(cfg_path), "algorithm": info.algorithm, "epochs": hist}
+    if info.full_inference:
+        # FULL_INFERENCE:1 — the exact score of the final weights: every vertex
+        # with its whole neighbourhood, layer by layer over the whole graph
+        # (no sampling: the same numbers for every RNG mode and every run)
+        for key, name in (("val", "Eval"), ("test", "Test")):
+            n = int(ids[key].size)
+            acc = drv.evaluate_full(torch.from_numpy(ids[key])) if n else 0.0
+            res[f"full_{name.lower()}_acc"] = acc
+            if rank == 0:
+                out(f"Full {name} Acc: {acc:f} {int(round(acc * n))} {n}")
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
-    return {"cfg": str(cfg_path), "algorithm": info.algorithm, "epochs": hist}
+    return res
 
 
 def main(argv=None):
