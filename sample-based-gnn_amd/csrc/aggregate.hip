@@ -326,8 +326,7 @@ template <int U>
 constexpr uint32_t kLongRow() { return 4 * U; }
 constexpr uint32_t kCoopRows = 16;
 
-// Row software pipeline of k_spmm_gather (compile-time A/B builds, `make
-// variant`): 0 none, 1 the next row's offsets, 2 the offsets two rows ahead
+// Row software pipeline of k_spmm_gather: 0 none, 1 the next row's offsets, 2 the offsets two rows ahead
 // and the first id/weight chunk one row ahead; and the waves-per-SIMD floor of
 // its single-chunk instances (0: the compiler's choice).  Measured at C2 size
 // (scripts/micro_agg.py, r04): bottom fwd / CSR bwd 103.7 / 121.7 us with 0,
@@ -335,14 +334,8 @@ constexpr uint32_t kCoopRows = 16;
 // floor of 6 waves (spills) — the prefetch registers cost a wave per SIMD
 // (occupancy 6 -> 5) and the gather needs the waves more than the shorter
 // chain, so 0 stays
-#ifndef NTS_AGG_PF
-#define NTS_AGG_PF 0
-#endif
-#ifndef NTS_AGG_WPE
-#define NTS_AGG_WPE 0
-#endif
-constexpr int kAggPf = NTS_AGG_PF;
-constexpr int kAggWpe = NTS_AGG_WPE == 0 ? 1 : NTS_AGG_WPE;
+constexpr int kAggPf = 0;
+constexpr int kAggWpe = 1;  // (amdgpu_waves_per_eu minimum: 1 = no floor)
 
 template <int VEC, int LPD, int NCH, bool MAP, int U, bool TIER, int MODE = kAggPlain,
           bool COOP = false>
@@ -398,19 +391,7 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(NCH
       wt = w ? __builtin_nontemporal_load(w + b + sl) : 1.0f;
     }
   };
-#ifdef NTS_AGG_XCD
-  // (A/B build: XCD-aware block order — the blocks one XCD runs, b % 8 under
-  // round-robin placement, take one contiguous eighth of the dsts, so each
-  // XCD's L2 sees one dst range's sources; bijective for any grid)
-  uint32_t bid = blockIdx.x;
-  if constexpr (!CM) {
-    const uint32_t q8 = gridDim.x / 8, r8 = gridDim.x % 8, x8 = blockIdx.x % 8;
-    bid = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + blockIdx.x / 8;
-  }
-  uint32_t d = bid * GPB + grp;
-#else
   uint32_t d = blockIdx.x * GPB + grp;
-#endif
   uint32_t beg = 0, end = 0, beg1 = 0, end1 = 0, pr = 0;
   float pw = 0.f;
   if (kAggPf >= 1 && d < n) {
@@ -681,355 +662,6 @@ __global__ void k_adam(float* __restrict__ W, const float* __restrict__ G, float
   }
 }
 
-#ifdef NTS_WITH_AGG_LDS  // negative result (2.5 TB/s of rows vs 6.7 in registers): variant builds only
-// ---------------------------------------------------------------------------
-// LDS-staged aggregation of 128- and 256-float rows (k_agg_lds): the same sums as
-// k_spmm_gather (per output row, its edges in edge order, acc + x * w with
-// contraction off — bit-identical for every row k_spmm_gather sums serially;
-// the long CSR rows it splits into pieces are summed serially here, i.e. in
-// MiniBatchFuseOp's order), but the neighbour rows are gathered into LDS by
-// LDS DMA (global_load_lds_dwordx4, per-lane row bases) instead of registers:
-// the gather form MI355X_MICROARCH.md measures at 7.4-8.6 TB/s against
-// 5.5-5.8 for register gathers (§ Indexed rows: gather into LDS).
-//
-// Block = an id loader wave, a row loader wave and 4 consumer waves (8 groups
-// of 32 lanes, one float4 of the row per lane, two for 256-float rows).
-// Output rows are cut into parts of R <= kLdsR rows; block b takes parts b,
-// b + G, ... and streams each part's edges in 16 KB stages (kLdsSE rows of 128
-// floats, or 16 of 256) through a ring of kLdsNS LDS slots:
-//   id loader   per stage: the stage's row ids, weights and its part's
-//               offsets by LDS DMA into an id ring, 8 stages ahead (the id
-//               loads' latency never sits in front of a row DMA)
-//   row loader  per stage: once its ids are in and its slot is free (stage
-//               k - NS consumed), 16 row DMAs; stage k-2 is marked full when
-//               it lands — three stages in flight.  Each loader issues only
-//               its own LDS DMAs, so its vmcnt counts are static.
-//   groups      group g owns rows pR + g + 8 j of part p, sums each row's
-//               edges that fall in the stage, stores a row when its last edge
-//               is in, and carries a row that continues into the next stage.
-// Output modes as k_spmm_gather's: plain, relu/dropout epilogue (kAggAct),
-// post-mask (kAggPostMask), column maxima per part (kAggColmax; part p's
-// maxima row = max over its rows of |rs(row) y|, the TN GEMM's operand
-// scales), all written by store_row.
-constexpr int kLdsR = 128;                       // output rows per part
-constexpr int kLdsSE = 32;                       // edges (rows of x) per stage
-constexpr int kLdsNS = 4;                        // ring slots
-constexpr int kLdsCons = 4;                      // consumer waves
-constexpr int kLdsThreads = kWave * (kLdsCons + 2);  // + row loader + id loader
-constexpr int kLdsID = 12;                       // id-ring entries (stages ahead of the rows)
-constexpr int kLdsIdAhead = 8;                   // id loads in flight (3 LDS DMAs each)
-constexpr int kLdsRowB = 512;                    // 128 floats
-constexpr int kLdsMaxParts = 64;                 // parts per block (lane-held bounds)
-constexpr int kLdsCmSlots = 8;                   // colmax part ring
-constexpr int kLdsF = 128;                       // floats per row
-
-struct LdsAggShared {
-  float4 rows[kLdsNS][kLdsSE * 32];              // 64 KB: 16 KB per slot (32 or 16 rows)
-  uint32_t full[kLdsNS], freed[kLdsNS];          // row slots: stages landed / waves done
-  // id ring (kLdsID stages, filled kLdsIdAhead stages ahead by the id loader's
-  // LDS DMAs): per stage [0, 32) row ids, [32, 64) weights, [64, 192) the
-  // part's offsets off[pR + j]; its descriptor and the part's edge end
-  uint32_t ids[kLdsID][64 + kLdsR];
-  uint4 meta[kLdsID];                            // {part, sb, se, flags | total << 8}
-  uint32_t pend[kLdsID];                         // off[min(pR + R, n)]
-  uint32_t ids_ready;                            // stages whose id entries landed
-  uint32_t cm[kLdsCmSlots][kLdsF];               // kAggColmax: part maxima ring
-  uint32_t cm_cnt[kLdsCmSlots];
-};
-
-// 16 (or 4) bytes per lane from `src` to LDS (wave-uniform base `lds`) + 16 (4)
-// * lane.  Inline asm: the compiler neither counts these loads nor waits for
-// them — the loader's s_waitcnt vmcnt(N) are the only waits, with N counted by
-// hand (every load the loader issues is one of these).
-__device__ __forceinline__ void glds16a(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds)
-      : "memory");
-}
-__device__ __forceinline__ void glds4a(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds)
-      : "memory");
-}
-__device__ __forceinline__ uint32_t lds_u32(const void* p) {
-  return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void lds_st(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// bounded spin (a hang would take the GPU with it): gives up after ~2^22 polls
-__device__ __forceinline__ void lds_wait_ge(const uint32_t* p, uint32_t v) {
-  for (uint32_t it = 0; lds_ld(p) < v && it < (1u << 22); ++it) __builtin_amdgcn_s_sleep(1);
-  asm volatile("" ::: "memory");
-}
-
-template <int MODE, int NCH>
-__global__ __launch_bounds__(kLdsThreads) void k_agg_lds(
-    const uint32_t* __restrict__ off, const uint32_t* __restrict__ idx,
-    const float* __restrict__ w, const uint32_t* n_dev, uint32_t n_cap,
-    const float* __restrict__ x, uint64_t ldx, float* __restrict__ y, uint64_t ldy, uint32_t R,
-    AggExtra ax) {
-  constexpr bool CM = MODE == kAggColmax;
-  constexpr int EM = CM ? kAggPlain : MODE;
-  constexpr int RF4 = 32 * NCH;         // float4s per row (128 or 256 floats)
-  constexpr int SE = kLdsSE / NCH;      // rows per stage (16 KB)
-  static_assert(!CM || NCH == 1, "column maxima: 128-float rows");
-  __shared__ LdsAggShared sh;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const uint32_t n = n_dev ? min(*n_dev, n_cap) : n_cap;
-  const uint32_t G = gridDim.x, b = blockIdx.x;
-  const uint32_t parts = (n + R - 1) / R;
-  const uint32_t parts_cap = (n_cap + R - 1) / R;
-  const uint32_t my_parts = parts > b ? (parts - b + G - 1) / G : 0u;  // <= kLdsMaxParts (host)
-  for (int i = tid; i < kLdsNS; i += kLdsThreads) {
-    sh.full[i] = 0u;
-    sh.freed[i] = 0u;
-  }
-  if (tid == 0) sh.ids_ready = 0u;
-  if (CM) {
-    for (int i = tid; i < kLdsCmSlots * kLdsF; i += kLdsThreads) (&sh.cm[0][0])[i] = 0u;
-    for (int i = tid; i < kLdsCmSlots; i += kLdsThreads) sh.cm_cnt[i] = 0u;
-    // parts past the live rows: zero maxima (as k_spmm_gather's per-block rows)
-    for (uint32_t p = parts + (b + G - parts % G) % G; p < parts_cap; p += G)
-      for (int c = tid; c < kLdsF; c += kLdsThreads) ax.cm_out[(uint64_t)p * kLdsF + c] = 0u;
-  }
-  __syncthreads();
-  if (my_parts == 0) return;
-
-  // stage k consumed by every consumer wave
-  auto consumed = [&](uint32_t k) {
-    return lds_ld(&sh.freed[k % kLdsNS]) >= (uint32_t)kLdsCons * (k / kLdsNS + 1);
-  };
-  if (wv == kLdsCons + 1) {
-    // ---------------- id loader ----------------
-    // lane i holds part i's edge bounds and stage count; per stage three LDS
-    // DMAs (ids | weights, the part's offsets) into id-ring entry k % kLdsID,
-    // kLdsIdAhead stages in flight; entry k is refilled once stage k - kLdsID
-    // is consumed.  (The only vector-memory ops of this wave: counted waits.)
-    uint32_t pe0 = 0, pe1 = 0, nst = 0;
-    if ((uint32_t)lane < my_parts) {
-      const uint32_t p = b + (uint32_t)lane * G;
-      pe0 = off[(uint64_t)p * R];
-      pe1 = off[min((uint64_t)(p + 1) * R, (uint64_t)n)];
-      nst = max(1u, (pe1 - pe0 + SE - 1) / SE);
-    }
-    uint32_t total = nst;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
-    const uint32_t lids = lds_u32(&sh.ids[0][0]);
-    uint32_t cur_i = 0, cur_s = 0;  // cursor: part, stage within the part
-    for (uint32_t k = 0; k < total + kLdsIdAhead - 1; ++k) {
-      if (k < total) {
-        const int q = (int)(k % kLdsID);
-        if (k >= (uint32_t)kLdsID)
-          for (uint32_t it = 0; !consumed(k - kLdsID) && it < (1u << 22); ++it) __builtin_amdgcn_s_sleep(1);
-        const uint32_t i = cur_i;
-        const uint32_t e0 = __shfl(pe0, (int)i), e1 = __shfl(pe1, (int)i), ns = __shfl(nst, (int)i);
-        const uint32_t sb = e0 + cur_s * SE, se = min(sb + SE, e1);
-        if (lane == 0) {
-          sh.meta[q] = make_uint4(b + i * G, sb, se,
-                                  (cur_s == 0 ? 1u : 0u) | (cur_s + 1 == ns ? 2u : 0u) | (total << 8));
-          sh.pend[q] = e1;
-        }
-        if (++cur_s == ns) {
-          cur_s = 0;
-          ++cur_i;
-        }
-        const uint32_t e = sb + (uint32_t)(lane & 31);
-        const uint32_t ec = e < se ? e : sb < se ? sb : 0u;
-        const void* src = lane < 32 || !w ? (const void*)(idx + ec) : (const void*)(w + ec);
-        glds4a(src, lids + (uint32_t)(q * (64 + kLdsR) * 4));
-        const uint64_t p = b + i * G;
-        glds4a(off + min(p * R + lane, (uint64_t)n), lids + (uint32_t)((q * (64 + kLdsR) + 64) * 4));
-        glds4a(off + min(p * R + 64 + lane, (uint64_t)n), lids + (uint32_t)((q * (64 + kLdsR) + 128) * 4));
-      }
-      // entry k - (kLdsIdAhead - 1) landed: younger are the 3 (kLdsIdAhead - 1)
-      // loads of the stages after it (fewer at the end: then wait for all)
-      if (k + 1 >= (uint32_t)kLdsIdAhead) {
-        if (k < total) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * (kLdsIdAhead - 1)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) lds_st(&sh.ids_ready, min(k + 2 - kLdsIdAhead, total));
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) lds_st(&sh.ids_ready, total);
-    return;
-  }
-  if (wv == kLdsCons) {
-    // ---------------- row loader ----------------
-    // per stage 16 LDS DMAs of 1 KB into row slot k % kLdsNS once its ids are
-    // in and stage k - kLdsNS is consumed; stage k-2 is marked full when it
-    // lands (younger: the 32 DMAs of k-1 and k), three stages in flight
-    const uint32_t lrows = lds_u32(&sh.rows[0][0]);
-    uint32_t total = 1;
-    for (uint32_t k = 0; k < total; ++k) {
-      const uint32_t slot = k % kLdsNS;
-      const int q = (int)(k % kLdsID);
-      lds_wait_ge(&sh.ids_ready, k + 1);
-      if (k >= (uint32_t)kLdsNS) lds_wait_ge(&sh.freed[slot], (uint32_t)kLdsCons * (k / kLdsNS));
-      const uint4 mt = sh.meta[q];
-      total = mt.w >> 8;
-      const uint32_t nrow = mt.z - mt.y;
-      const uint32_t id = sh.ids[q][lane & 31];
-      const uint32_t id0 = __shfl(id, 0);
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {
-        const int fl4 = 64 * jj + lane, r = fl4 / RF4, c16 = fl4 % RF4;
-        uint32_t rid = __shfl(id, r);
-        rid = (uint32_t)r < nrow ? rid : (nrow ? id0 : 0u);
-        const char* src = reinterpret_cast<const char*>(x + (uint64_t)rid * ldx) + 16 * c16;
-        glds16a(src, lrows + (uint32_t)(slot * kLdsSE * kLdsRowB + 1024 * jj));
-      }
-      if (k >= 2) {
-        asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-        lds_st(&sh.full[(k - 2) % kLdsNS], k - 1);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (uint32_t k = total > 2 ? total - 2 : 0; k < total; ++k) lds_st(&sh.full[k % kLdsNS], k + 1);
-    return;
-  }
-
-  // ---------------- consumer waves: 8 groups of 32 lanes ----------------
-  const int g = 2 * wv + (lane >> 5), l = lane & 31;
-  float4 acc[NCH];
-  float4 cmx = make_float4(0.f, 0.f, 0.f, 0.f);
-  uint32_t j = 0, pcount = 0;                    // local row of the part, rows in the part
-  uint32_t e_beg = 0, e_end = 0, part = 0, part_ord = 0;
-  // per-row operands known before the row's edges (kAggPostMask: the row's
-  // mask, kAggColmax: its scale), loaded one row ahead: a global load used
-  // right away would make the compiler wait for every older store as well
-  float4 pm[NCH], pm_n[NCH];
-  float rsd = 1.f, rsd_n = 1.f;
-  auto zero = [&]() {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  zero();
-  auto row_ctx = [&](uint32_t d) {  // -> the "next" registers
-    if constexpr (MODE == kAggPostMask)
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        pm_n[c] = *reinterpret_cast<const float4*>(ax.mx + (uint64_t)d * ax.ldm + 4 * (l + 32 * c));
-    if constexpr (CM) rsd_n = ax.cm_rs ? ax.cm_rs[ax.cm_map ? ax.cm_map[d] : d] : 1.f;
-  };
-  auto take_ctx = [&]() {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) pm[c] = pm_n[c];
-    rsd = rsd_n;
-  };
-  uint32_t total = 1;
-  for (uint32_t k = 0; k < total; ++k) {
-    const uint32_t slot = k % kLdsNS;
-    const int q = (int)(k % kLdsID);
-    lds_wait_ge(&sh.full[slot], k + 1);
-    const uint4 mt = sh.meta[q];
-    total = mt.w >> 8;
-    const uint32_t sb = mt.y, se = mt.z, fl = mt.w & 255u;
-    if (fl & 1u) {  // first stage of part mt.x: this group's first row
-      part = mt.x;
-      pcount = min(R, n - part * R);
-      j = (uint32_t)g;
-      if (j < pcount) {
-        e_beg = sh.ids[q][64 + j];
-        e_end = j + 1 < pcount ? sh.ids[q][64 + j + 1] : sh.pend[q];
-        row_ctx(part * R + j);
-        take_ctx();
-        if (j + 8 < pcount) row_ctx(part * R + j + 8);
-      }
-      zero();
-      cmx = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float4* srow = &sh.rows[slot][l];
-    const float* sw = reinterpret_cast<const float*>(&sh.ids[q][32]);
-    // rows whose edges start in this stage (a row without edges at the
-    // stage's end included): sum their edges here, store the complete ones
-    while (j < pcount && (e_beg < se || (e_beg == e_end && e_beg <= se))) {
-      uint32_t e = max(e_beg, sb);
-      const uint32_t hi = min(e_end, se);
-      constexpr int UL = 8 / NCH;  // rows of x read ahead of their adds
-      for (; e + UL <= hi; e += UL) {
-        float4 xv[UL][NCH];
-        float wv4[UL];
-#pragma unroll
-        for (int u = 0; u < UL; ++u) {
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) xv[u][c] = srow[(e + u - sb) * RF4 + 32 * c];
-          wv4[u] = w ? sw[e + u - sb] : 1.f;
-        }
-#pragma unroll
-        for (int u = 0; u < UL; ++u)
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) acc[c] = VT<4>::madd(acc[c], xv[u][c], wv4[u]);
-      }
-      for (; e < hi; ++e)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-          acc[c] = VT<4>::madd(acc[c], srow[(e - sb) * RF4 + 32 * c], w ? sw[e - sb] : 1.f);
-      if (e_end > se) break;  // continues in the next stage
-      const uint32_t d = part * R + j;
-      if constexpr (MODE == kAggPostMask)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c)
-          acc[c] = make_float4(pm[c].x > 0.f ? acc[c].x * ax.scale : 0.f, pm[c].y > 0.f ? acc[c].y * ax.scale : 0.f,
-                               pm[c].z > 0.f ? acc[c].z * ax.scale : 0.f, pm[c].w > 0.f ? acc[c].w * ax.scale : 0.f);
-      store_row<4, 32, NCH, MODE == kAggPostMask ? kAggPlain : EM>(acc, d, 0, l, RF4, 4, y, ldy, ax);
-      if constexpr (CM) {
-        cmx.x = fmaxf(cmx.x, fabsf(acc[0].x * rsd));
-        cmx.y = fmaxf(cmx.y, fabsf(acc[0].y * rsd));
-        cmx.z = fmaxf(cmx.z, fabsf(acc[0].z * rsd));
-        cmx.w = fmaxf(cmx.w, fabsf(acc[0].w * rsd));
-      }
-      zero();
-      j += 8;
-      if (j < pcount) {
-        e_beg = sh.ids[q][64 + j];
-        e_end = j + 1 < pcount ? sh.ids[q][64 + j + 1] : sh.pend[q];
-        take_ctx();
-        if (j + 8 < pcount) row_ctx(part * R + j + 8);
-      }
-    }
-    if (CM && (fl & 2u)) {
-      // part done for this group: fold its maxima into the part's ring slot;
-      // the eighth group to arrive writes the part's row and clears the slot
-      // (a group can be at most a few parts ahead: every stage of a part is
-      // consumed by every wave before the ring moves NS stages on)
-      const uint32_t cs = part_ord % kLdsCmSlots;
-      atomicMax(&sh.cm[cs][4 * l + 0], __float_as_uint(cmx.x));
-      atomicMax(&sh.cm[cs][4 * l + 1], __float_as_uint(cmx.y));
-      atomicMax(&sh.cm[cs][4 * l + 2], __float_as_uint(cmx.z));
-      atomicMax(&sh.cm[cs][4 * l + 3], __float_as_uint(cmx.w));
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      uint32_t arrived = 0;
-      if (l == 0) arrived = atomicAdd(&sh.cm_cnt[cs], 1u);
-      arrived = __shfl(arrived, lane & 32);
-      if (arrived == 7u) {
-        const uint4 m4 = *reinterpret_cast<const uint4*>(&sh.cm[cs][4 * l]);
-        *reinterpret_cast<uint4*>(ax.cm_out + (uint64_t)part * kLdsF + 4 * l) = m4;
-        *reinterpret_cast<uint4*>(&sh.cm[cs][4 * l]) = make_uint4(0u, 0u, 0u, 0u);
-        if (l == 0) sh.cm_cnt[cs] = 0u;
-      }
-    }
-    if (fl & 2u) ++part_ord;
-    // this wave is done reading the slot
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0)
-      __hip_atomic_fetch_add(&sh.freed[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-}
-#endif  // NTS_WITH_AGG_LDS
 
 // ---------------------------------------------------------------------------
 // dispatch
@@ -1068,18 +700,6 @@ static int plain_vec(uint32_t F, uint64_t ldx, uint64_t ldy, const void* x, cons
   return vec;
 }
 
-// compile-time A/B (make variant VFLAGS=-DNTS_GATHER_U=4): 4 rows in flight
-// for the mid-width rows instead of 5
-#ifndef NTS_GATHER_U
-#define NTS_GATHER_U 0
-#endif
-constexpr int gather_u_env() { return NTS_GATHER_U; }
-// rows in flight for the post-mask CSR gather (the hop above a transform-first
-// bottom layer: ~2 edges per row at C2); 0: gather_u's (compile-time A/B)
-#ifndef NTS_AGG_PM_U
-#define NTS_AGG_PM_U 0
-#endif
-constexpr int kAggPmU = NTS_AGG_PM_U;
 constexpr int gather_u(int floats_per_lane) {
   return floats_per_lane <= 4 ? 8 : floats_per_lane <= 12 ? 5 : 4;
 }
@@ -1092,18 +712,13 @@ static int launch_gather_vec(hipStream_t st, uint32_t grid, uint32_t last_valid,
                              uint32_t nv, float* y, uint64_t ldy, Tier tier, const AggExtra& ax) {
 // rows in flight per lane group: 8 for narrow rows, 5 for mid-width rows
 // (F ~ 600: 3 float4 per lane; fanout 10/25 -> full batches), 4 for the
-// widest (register budget); -DNTS_GATHER_U=4 forces 4 for the mid-width rows
+// widest (register budget); the post-mask CSR gather takes the same counts
 #define NTS_G(LPD, NCH)                                                                     \
   do {                                                                                      \
-    constexpr int u = (MODE == kAggPostMask && kAggPmU > 0) ? kAggPmU : gather_u(VEC * NCH); \
-    if (u == 5 && gather_u_env() == 4)                                                      \
-      hipLaunchKernelGGL((k_spmm_gather<VEC, LPD, NCH, MAP, 4, TIER, MODE, COOP>), dim3(grid), \
-                         dim3(kAggThreads), 0, st, off, idx, w, n_dev, n_cap, x, ldx, map, \
-                         nv, y, ldy, last_valid, tier, ax);                                 \
-    else                                                                                    \
-      hipLaunchKernelGGL((k_spmm_gather<VEC, LPD, NCH, MAP, u, TIER, MODE, COOP>), dim3(grid), \
-                         dim3(kAggThreads), 0, st, off, idx, w, n_dev, n_cap, x, ldx, map, \
-                         nv, y, ldy, last_valid, tier, ax);                                 \
+    constexpr int u = gather_u(VEC * NCH);                                                  \
+    hipLaunchKernelGGL((k_spmm_gather<VEC, LPD, NCH, MAP, u, TIER, MODE, COOP>), dim3(grid), \
+                       dim3(kAggThreads), 0, st, off, idx, w, n_dev, n_cap, x, ldx, map,   \
+                       nv, y, ldy, last_valid, tier, ax);                                   \
   } while (0)
   if (s.lpd == 8) NTS_G(8, 1);
   else if (s.lpd == 16) NTS_G(16, 1);
@@ -1122,17 +737,6 @@ static int launch_gather_vec(hipStream_t st, uint32_t grid, uint32_t last_valid,
   NTS_LAUNCH_CHECK();
   return NTS_OK;
 }
-
-// the LDS-staged gather (k_agg_lds) takes 128-float rows gathered by local id
-// (no row map, no host tier, no per-edge mask rows) in 16-byte vectors; it
-// exists only in variant builds (make variant V=agglds VFLAGS=-DNTS_WITH_AGG_LDS)
-#ifdef NTS_WITH_AGG_LDS
-template <bool MAP, bool TIER, int MODE>
-static bool agg_lds_applies(int vec, uint32_t F) {
-  return !MAP && !TIER && MODE != kAggMask && vec == 4 &&
-         (F == (uint32_t)kLdsF || (F == 2u * kLdsF && MODE != kAggColmax));
-}
-#endif
 
 template <bool MAP, bool TIER = false, int MODE = kAggPlain, bool COOP = false>
 static int launch_gather(hipStream_t st, const uint32_t* off, const uint32_t* idx,
@@ -1154,51 +758,18 @@ static int launch_gather(hipStream_t st, const uint32_t* off, const uint32_t* id
     vec = 4;
   const uint32_t nv = (F + vec - 1) / vec;
   const uint32_t last_valid = F - (nv - 1) * vec;
-#ifdef NTS_WITH_AGG_LDS
-  if (agg_lds_applies<MAP, TIER, MODE>(vec, F)) {
-    // 128-float rows: the LDS-staged gather (k_agg_lds)
-    // rows per part: kLdsR for the column maxima (the parts the TN GEMM reads,
-    // nts_hip_csr_bwd_colmax_rows_per_part), else smaller parts for small
-    // layers (~1,000 parts: enough blocks for the chip)
-    uint32_t R = (uint32_t)kLdsR;
-    if (MODE != kAggColmax)
-      while (R > 8 && (uint64_t)R * 1024 > n_cap) R /= 2;
-    const uint32_t parts_cap = ceil_div(n_cap, R);
-    const uint32_t grid = std::max(std::min(parts_cap, 1024u), ceil_div(parts_cap, kLdsMaxParts));
-    if (grid == 0) return NTS_OK;
-    if constexpr (MODE == kAggColmax)
-      hipLaunchKernelGGL((k_agg_lds<MODE, 1>), dim3(grid), dim3(kLdsThreads), 0, st, off, idx, w, n_dev,
-                         n_cap, x, ldx, y, ldy, R, ax);
-    else if (F == (uint32_t)kLdsF)
-      hipLaunchKernelGGL((k_agg_lds<MODE, 1>), dim3(grid), dim3(kLdsThreads), 0, st, off, idx, w, n_dev,
-                         n_cap, x, ldx, y, ldy, R, ax);
-    else
-      hipLaunchKernelGGL((k_agg_lds<MODE, 2>), dim3(grid), dim3(kLdsThreads), 0, st, off, idx, w, n_dev,
-                         n_cap, x, ldx, y, ldy, R, ax);
-    NTS_LAUNCH_CHECK();
-    return NTS_OK;
-  }
-#endif
   const Shape s = pick_shape(nv);
   const uint32_t gpb = kAggThreads / s.lpd;
   // one destination per lane group: every row's dependent loads (offsets ->
-  // ids -> rows) are in flight at once; a grid-stride cap (NTS_AGG_GRID)
+  // ids -> rows) are in flight at once; a grid-stride cap
   // serialises rows per group and measured slower (C2: 1.069 vs 1.097 ms per
-  // step at a 4096-block cap; the narrow CSR backward 50 -> ~25 us;
-  // compile-time A/B: -DNTS_AGG_GRID=<blocks>)
-#ifndef NTS_AGG_GRID
-#define NTS_AGG_GRID (1u << 24)
-#endif
-  constexpr uint32_t cap = NTS_AGG_GRID;
+  // step at a 4096-block cap; the narrow CSR backward 50 -> ~25 us)
+  constexpr uint32_t cap = 1u << 24;
   // the post-mask CSR gather (the hop above a transform-first bottom layer,
   // ~2 edges per row at C2) with a few rows per group instead of one
-  // (compile-time A/B, -DNTS_AGG_PM_GRID=<blocks>): 44.7 / 44.6 / 51.7 us at
-  // 4096 / 8192 / 2048 blocks against 44.9 at one row per group
-  // (scripts/ab/r05_au.sh) — bound by its bytes, not by block lifetimes
-#ifndef NTS_AGG_PM_GRID
-#define NTS_AGG_PM_GRID (1u << 24)
-#endif
-  constexpr uint32_t pm_cap = MODE == kAggPostMask ? NTS_AGG_PM_GRID : (1u << 24);
+  // measured 44.7 / 44.6 / 51.7 us at 4096 / 8192 / 2048 blocks against 44.9
+  // at one row per group — bound by its bytes, not by block lifetimes: no cap
+  constexpr uint32_t pm_cap = 1u << 24;
   // COOP: at most kCoopRows rows per lane group (the colmax parts: one)
   const uint32_t grid =
       std::max(1u, COOP ? std::max(ceil_div(n_cap, gpb * kCoopRows), std::min(ceil_div(n_cap, gpb), pm_cap))
@@ -1255,9 +826,6 @@ int nts_hip_spmm_csr_bwd(nts_hip_ctx* ctx, const uint32_t* row_offset,
 uint32_t nts_hip_csr_bwd_colmax_rows_per_part(uint32_t feature_size) {
   if (feature_size == 0) return 0;
   // (the colmax gather always runs on float4 rows: vec 4)
-#ifdef NTS_WITH_AGG_LDS
-  if (agg_lds_applies<false, false, kAggColmax>(4, feature_size)) return (uint32_t)kLdsR;
-#endif
   return (uint32_t)(kAggThreads / pick_shape((feature_size + 3) / 4).lpd);
 }
 

@@ -274,12 +274,10 @@ struct CountArgs {
   const uint32_t* omit_loc;
   uint32_t* omit_row;
 };
-// tmp: count_scan_tmp_elems(v_cap) words for the two-kernel form
-// (NTS_SCAN1=0; the default and tmp == nullptr: the single-pass kernel)
-int count_scan(nts_hip_ctx* ctx, const CountArgs& ca, uint32_t* co, hipStream_t stream,
-               uint32_t* tmp);
+int count_scan(nts_hip_ctx* ctx, const CountArgs& ca, uint32_t* co, hipStream_t stream);
+// words the sampler's workspace layout keeps in front of its block counts
+// (the retired two-kernel form's temporaries: the layout is unchanged)
 size_t count_scan_tmp_elems(uint64_t v_cap);
-bool scan1_enabled();
 
 // Stable LSD radix sort of (key, value) pairs on the low `bits` key bits.
 // n = *n_dev (or n_cap).  vals_in == nullptr means values = 0..n-1.

@@ -928,12 +928,8 @@ int sum_splits(hipStream_t st, const float* part, int splits, uint64_t stride, i
 }
 
 static bool tn_big_ok(int M, int N, const float* B, uint64_t ldb, const GemmExtra& ex, bool bmask) {
-  // RT = 1 for <= 128 output rows (compile-time A/B: -DNTS_TN_NARROW=0)
-#ifndef NTS_TN_NARROW
-#define NTS_TN_NARROW 1
-#endif
-  constexpr bool narrow = NTS_TN_NARROW != 0;
-  if (!(M >= 320 || (narrow && M <= 128)) || N % 128 != 0 || ldb % 4 != 0 || (uintptr_t)B % 16 != 0)
+  // RT = 1 for <= 128 output rows
+  if (!(M >= 320 || M <= 128) || N % 128 != 0 || ldb % 4 != 0 || (uintptr_t)B % 16 != 0)
     return false;
   if (bmask && (ex.ldbx % 4 != 0 || (uintptr_t)ex.bx % 16 != 0)) return false;
   return true;
@@ -948,22 +944,15 @@ static int launch_tn_big(nts_hip_ctx* ctx, int M, int N, int K, const float* A, 
   const int nrg = (M + (rt1 ? tb_rows<1>() : tb_rows<5>()) - 1) / (rt1 ? tb_rows<1>() : tb_rows<5>());
   const int ncb = N / 128;
   // narrow tiles hold ~55 KB of LDS and ~70 VGPRs: two blocks fit a CU, and
-  // the second doubles the gathered rows in flight (A/B: -DNTS_TN_NARROW_BLOCKS=n)
-#ifndef NTS_TN_NARROW_BLOCKS
-#define NTS_TN_NARROW_BLOCKS 512
-#endif
-  constexpr int narrow_blocks = NTS_TN_NARROW_BLOCKS;
+  // the second doubles the gathered rows in flight
+  constexpr int narrow_blocks = 512;
   const int target = rt1 ? narrow_blocks : 256;
   int splits = std::max(1, std::min(target / (nrg * ncb), (K + 4 * kTbKS - 1) / (4 * kTbKS)));
   const int kchunk = ((K + splits - 1) / splits + kTbKS - 1) / kTbKS * kTbKS;
   splits = (K + kchunk - 1) / kchunk;
   const dim3 grid(nrg * ncb * splits);
-#ifndef NTS_TN_STAGGER  // compile-time A/B: -DNTS_TN_STAGGER=0
-#define NTS_TN_STAGGER 1
-#endif
-  constexpr bool stagger = NTS_TN_STAGGER != 0;
-  const size_t lds = rt1 ? (stagger ? sizeof(TbSmem<3, 1>) : sizeof(TbSmem<2, 1>))
-                        : (stagger ? sizeof(TbSmem<3, 5>) : sizeof(TbSmem<2, 5>));
+  // (the staggered form, SG = true, is the only one launched)
+  const size_t lds = rt1 ? sizeof(TbSmem<3, 1>) : sizeof(TbSmem<3, 5>);
   const bool a4 = lda % 4 == 0 && lda >= (uint64_t)(M + 3) / 4 * 4 && (uintptr_t)A % 16 == 0;
   const bool a2 = M % 2 == 0 && lda % 2 == 0 && (uintptr_t)A % 8 == 0;
   const bool direct = splits == 1;
@@ -975,27 +964,21 @@ static int launch_tn_big(nts_hip_ctx* ctx, int M, int N, int K, const float* A, 
     out = (float*)ctx->scratch;
     ldo = N;
   }
-#define NTS_TB_R(AV, SG, R)                                                                     \
+#define NTS_TB_R(AV, R)                                                                         \
   do {                                                                                          \
-    NTS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tn_big<BMASK, AV, SG, R>), \
+    NTS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tn_big<BMASK, AV, true, R>), \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
-    hipLaunchKernelGGL((k_gemm_tn_big<BMASK, AV, SG, R>), grid, dim3(kTbWaves * 64), lds, st, M, N, \
+    hipLaunchKernelGGL((k_gemm_tn_big<BMASK, AV, true, R>), grid, dim3(kTbWaves * 64), lds, st, M, N, \
                        K, A, lda, B, ldb, out, ldo, kchunk, direct ? (uint64_t)0 : stride, nrg, \
                        ncb, ex);                                                                \
   } while (0)
-#define NTS_TB_S(AV, SG)                  \
-  do {                                    \
-    if (rt1) NTS_TB_R(AV, SG, 1);         \
-    else NTS_TB_R(AV, SG, 5);             \
-  } while (0)
-#define NTS_TB(AV)                               \
-  do {                                           \
-    if (stagger) NTS_TB_S(AV, true);             \
-    else NTS_TB_S(AV, false);                    \
+#define NTS_TB(AV)                \
+  do {                            \
+    if (rt1) NTS_TB_R(AV, 1);     \
+    else NTS_TB_R(AV, 5);         \
   } while (0)
   if (a4) NTS_TB(4); else if (a2) NTS_TB(2); else NTS_TB(1);
 #undef NTS_TB
-#undef NTS_TB_S
 #undef NTS_TB_R
   NTS_LAUNCH_CHECK();
   if (direct) return NTS_OK;
@@ -1047,29 +1030,17 @@ static int launch_wres(hipStream_t st, int ncol, int M, int N, int K, const floa
   if (lda % 4 == 0 && (uintptr_t)A % 16 == 0) avec = 4;
   else if (lda % 2 == 0 && (uintptr_t)A % 8 == 0) avec = 2;
   const int vs = (ldc % 4 == 0 && (uintptr_t)C % 16 == 0) ? 1 : 0;
-#ifndef NTS_WRES_DEPTH  // compile-time A/B: -DNTS_WRES_DEPTH=3, -DNTS_WRES_XT=0
-#define NTS_WRES_DEPTH 2
-#endif
-#ifndef NTS_WRES_XT
-#define NTS_WRES_XT 1
-#endif
-  constexpr int depth = NTS_WRES_DEPTH;
-  constexpr bool xtask = NTS_WRES_XT != 0;
-#define NTS_WRES_D(NC, AV, D, X)                                                                \
+  // the launched form: two rotating A register sets, cross-task prefetch
+  constexpr int depth = 2;
+  constexpr bool xtask = true;
+#define NTS_WRES(NC, AV)                                                                        \
   do {                                                                                          \
     NTS_HIP_TRY(hipFuncSetAttribute(                                                            \
-        reinterpret_cast<const void*>(&k_gemm_wres<NC, AV, EPI, D, X>),                         \
+        reinterpret_cast<const void*>(&k_gemm_wres<NC, AV, EPI, depth, xtask>),                 \
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-    hipLaunchKernelGGL((k_gemm_wres<NC, AV, EPI, D, X>), dim3(grid), dim3(wres_threads<NC>()),  \
-                       lds, st, M, N, K, nkb, A, lda, B, ldb, C, ldc, ncb, vs, ex);             \
-  } while (0)
-#define NTS_WRES(NC, AV)                                            \
-  do {                                                              \
-    if (depth == 3) {                                               \
-      if (xtask) NTS_WRES_D(NC, AV, 3, true); else NTS_WRES_D(NC, AV, 3, false); \
-    } else {                                                        \
-      if (xtask) NTS_WRES_D(NC, AV, 2, true); else NTS_WRES_D(NC, AV, 2, false); \
-    }                                                               \
+    hipLaunchKernelGGL((k_gemm_wres<NC, AV, EPI, depth, xtask>), dim3(grid),                    \
+                       dim3(wres_threads<NC>()), lds, st, M, N, K, nkb, A, lda, B, ldb, C, ldc, \
+                       ncb, vs, ex);                                                            \
   } while (0)
   if (ncol == 128) {
     if (avec == 4) NTS_WRES(128, 4); else if (avec == 2) NTS_WRES(128, 2); else NTS_WRES(128, 1);
@@ -1077,19 +1048,8 @@ static int launch_wres(hipStream_t st, int ncol, int M, int N, int K, const floa
     if (avec == 4) NTS_WRES(64, 4); else if (avec == 2) NTS_WRES(64, 2); else NTS_WRES(64, 1);
   }
 #undef NTS_WRES
-#undef NTS_WRES_D
   NTS_LAUNCH_CHECK();
   return NTS_OK;
-}
-
-// Kernel selection (NTS_GEMM_TILED=1 forces the LDS-tiled kernel everywhere,
-// for A/B comparisons).
-static bool force_tiled() {  // compile-time A/B: -DNTS_GEMM_TILED=1
-#ifdef NTS_GEMM_TILED
-  return NTS_GEMM_TILED != 0;
-#else
-  return false;
-#endif
 }
 
 // One GEMM: split the reduction when the output grid alone cannot fill the
@@ -1108,19 +1068,13 @@ static int gemm(nts_hip_ctx* ctx, bool trans_a, int M, int N, int K, const float
   // faster on the fp32-input MFMA kernels (C3: 0.716 vs 0.740 ms/step).
   // Round 6: short dense reductions (K <= 128) on k_x3_nnk, which keeps the
   // whole W image in LDS.
-#ifndef NTS_NO_X3K  // (A/B build: -DNTS_NO_X3K keeps these on the fp32-input kernels)
   const bool nnk = !trans_a && !BMASK && !ex.amap && x3_nnk_ok(M, N, K, A, lda);
-#else
-  const bool nnk = false;
-#endif
-#ifndef NTS_NO_X3K
   // ... and the masked weight gradient of such a layer (dW = Y^T (dZ ⊙ [Z >
   // 0]) s, M <= 128 output rows) on k_x3_tn's one-tile form with the mask rows
   // beside dZ's (the row pitch must cover 32 ceil(M / 32) floats)
   if (trans_a && BMASK && !EPI && ctx->gemm_mode != NTS_GEMM_F32 &&
       x3_tn_bm_ok(M, N, K, A, lda, B, ldb, ex.bx, ex.ldbx))
     return x3_tn(ctx, M, N, K, A, lda, ex.amap, B, ldb, C, ldc, ex.bx, ex.ldbx, ex.bscale);
-#endif
   if (ctx->gemm_mode == NTS_GEMM_SPLIT3_ALL ||
       (ctx->gemm_mode == NTS_GEMM_SPLIT3 && ((trans_a ? M : K) >= 256 || nnk))) {
     if (!trans_a && !BMASK && gemm3_nn_ok(M, N, K, A, lda))
@@ -1130,14 +1084,12 @@ static int gemm(nts_hip_ctx* ctx, bool trans_a, int M, int N, int K, const float
       return gemm3_tn(ctx, M, N, K, A, lda, ex.amap, B, ldb, BMASK ? ex.bx : nullptr, ex.ldbx,
                       ex.bscale, C, ldc);
   }
-  if (!force_tiled()) {
-    if (!trans_a && !BMASK) {
-      const int ncol = wres_ncol(M, N, K);
-      if (ncol) return launch_wres<EPI>(st, ncol, M, N, K, A, lda, B, ldb, C, ldc, ex);
-    }
-    if (trans_a && !EPI && tn_big_ok(M, N, B, ldb, ex, BMASK))
-      return launch_tn_big<BMASK>(ctx, M, N, K, A, lda, B, ldb, C, ldc, ex);
+  if (!trans_a && !BMASK) {
+    const int ncol = wres_ncol(M, N, K);
+    if (ncol) return launch_wres<EPI>(st, ncol, M, N, K, A, lda, B, ldb, C, ldc, ex);
   }
+  if (trans_a && !EPI && tn_big_ok(M, N, B, ldb, ex, BMASK))
+    return launch_tn_big<BMASK>(ctx, M, N, K, A, lda, B, ldb, C, ldc, ex);
   const int tiles = (int)(ceil_div(M, kBM) * ceil_div(N, kBN));
   int splits = 1;
   const int ksteps = (K + kBK - 1) / kBK;

@@ -27,32 +27,17 @@
 //               and split there, B staged as bf16 pieces in LDS and read with
 //               ds_read_b64_tr_b16, the long reduction split over blocks and
 //               summed in a fixed order (sum_splits) — deterministic.
-//   k_gemm3_tn  the first-generation TN (NTS_S3_V1=1): a 320 x 128 output
+//   k_gemm3_tn  the first-generation TN (operands k_s3_tn cannot take): a 320 x 128 output
 //               tile per block, k-slices of A and B staged transposed into
 //               fragment order.
-#include "common.hpp"
+#include "mfma_lds.hpp"
 
 namespace nts_hip {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kS3Threads = 512;  // 8 waves
 constexpr int kS3Frag = 64 * 16;  // bytes of one fragment image (64 lanes x 8 bf16)
 
-// x -> (x0, x1, x2), element-wise over one lane's 8 fragment values
-__device__ __forceinline__ void split3(const float (&x)[8], bf16x8& h0, bf16x8& h1, bf16x8& h2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 a0 = (__bf16)x[j];
-    const float r1 = x[j] - (float)a0;
-    const __bf16 a1 = (__bf16)r1;
-    const float r2 = r1 - (float)a1;
-    h0[j] = a0;
-    h1[j] = a1;
-    h2[j] = (__bf16)r2;
-  }
-}
 
 // acc += a * b over one 32-deep k-slice, a and b given as split triples
 __device__ __forceinline__ f32x4 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4 acc) {
@@ -85,12 +70,6 @@ struct Gemm3Extra {
   uint64_t ldbx = 0;
   float bscale = 1.f;
   const uint32_t* amap = nullptr;  // gathered A rows (NN: M rows, TN: K rows)
-#ifdef NTS_PROBE_BUILD
-  int diag = 0;  // NTS_S3_DIAG timing probes (results invalid): 1 no global loads,
-                 // 2 no split, 4 no barrier, 8 no MFMA, 16 no B fragment reads
-#else
-  static constexpr int diag = 0;  // the product library has no timing probes
-#endif
 };
 
 // ---------------------------------------------------------------------------
@@ -123,25 +102,6 @@ __global__ __launch_bounds__(256) void k_split3_b(const float* __restrict__ B, u
 // pipeline).  Their completion is counted by hand (s_waitcnt vmcnt(N)); the
 // only compiler-visible global loads of the k-loop (the partial last step)
 // come after a vmcnt(0).
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(lds_ptr_t)p;
-}
-// 16 bytes per lane from `src` to LDS (wave-uniform base `lds`) + 16 * lane
-__device__ __forceinline__ void glds16(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds)
-      : "memory");
-}
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // NN.  Block = 8 waves (two per SIMD), one column block of 128 per grid.y.
 // The M rows are cut into 16-row tiles; wave gw of the grid owns the
@@ -202,14 +162,12 @@ __global__ __launch_bounds__(kS3NnThreads, 1) void k_gemm3_nn(int M, int N, int 
     }
   };
   auto issue_b = [&](int s) {
-    if (ex.diag & 1) return;
     const uint32_t dst = lsb + (s & 1) * kS3Img + wv * 1024;
     const char* src = bsrc + (size_t)s * bstride;
 #pragma unroll
     for (int p = 0; p < 3; ++p) glds16(src + 8192 * p, dst + 8192 * p);
   };
   auto issue_a = [&](int s) {
-    if (ex.diag & 1) return;
     const uint32_t dst = lsa + (s % 3) * kS3NnA + wv * kS3NnAWave;
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
@@ -220,25 +178,9 @@ __global__ __launch_bounds__(kS3NnThreads, 1) void k_gemm3_nn(int M, int N, int 
   // split the row tiles' fragments and run the MFMAs of step s against B(s)
   auto mma = [&](int s, const float (&x)[2][8], bool two) {
     bf16x8 a[2][3];
-    if (ex.diag & 2) {
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) a[rt][p] = *reinterpret_cast<const bf16x8*>(&x[rt][0]);
-    } else {
-      split3(x[0], a[0][0], a[0][1], a[0][2]);
-      split3(x[1], a[1][0], a[1][1], a[1][2]);
-    }
-    if (ex.diag & 8) return;
+    split3(x[0], a[0][0], a[0][1], a[0][2]);
+    split3(x[1], a[1][0], a[1][1], a[1][2]);
     const char* img = sb + (s & 1) * kS3Img;
-    if (ex.diag & 16) {  // no B reads: the A pieces stand in for B
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) {
-        acc[0][ct] = mfma6(a[0], a[1], acc[0][ct]);
-        acc[1][ct] = mfma6(a[1], a[0], acc[1][ct]);
-      }
-      return;
-    }
     if (two) {
 #pragma unroll
       for (int ct = 0; ct < 8; ++ct) {
@@ -268,14 +210,10 @@ __global__ __launch_bounds__(kS3NnThreads, 1) void k_gemm3_nn(int M, int N, int 
     if (nfull > 0) issue_a(0);
     if (nfull > 1) issue_a(1);
     for (int s = 0; s < nsteps; ++s) {
-      // B(s) and A(s) landed (A(s+1), issued after B(s), may stay in flight)
-#ifdef NTS_S3NN_COUNTED  // (A/B build: the counted wait)
-      if (s + 1 < nfull) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else  // drained: the LDS-DMA loads need not retire in issue order (k_x3_tn, round 6)
+      // B(s) and A(s) landed; drained, not counted: the LDS-DMA loads need not
+      // retire in issue order (k_x3_tn, round 6)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-      if (!(ex.diag & 4)) raw_barrier();
+      raw_barrier();
       if (s + 1 < nsteps) issue_b(s + 1);
       if (s + 2 < nfull) issue_a(s + 2);
       float x[2][8];
@@ -530,7 +468,6 @@ __global__ __launch_bounds__(kS3Threads, 1) void k_gemm3_tn(int M, int N, int K,
   };
   Stage sg0, sg1;
   auto load = [&](int s, Stage& q) {
-    if (ex.diag & 1) return;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float* arow = A + (uint64_t)rnext[j] * lda;
@@ -542,7 +479,6 @@ __global__ __launch_bounds__(kS3Threads, 1) void k_gemm3_tn(int M, int N, int K,
     }
   };
   auto store = [&](int s, const Stage& q) {
-    if (ex.diag & 2) return;
     const int st = s & 1;
     const int kl = kend - (kbeg + 32 * s + 8 * kg);  // valid k rows of this thread's 8
     float x[8];
@@ -568,7 +504,6 @@ __global__ __launch_bounds__(kS3Threads, 1) void k_gemm3_tn(int M, int N, int K,
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) acc[q][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto compute = [&](int s) {
-    if (ex.diag & 8) return;
     const int st = s & 1;
     bf16x8 b[2][3], a[2][3];
 #pragma unroll
@@ -632,7 +567,7 @@ __global__ __launch_bounds__(kS3Threads, 1) void k_gemm3_tn(int M, int N, int K,
 }
 
 // ---------------------------------------------------------------------------
-// TN v2 (the default for TN; NTS_S3_V1=1 selects k_gemm3_tn above): two
+// TN v2 (the default for TN; k_gemm3_tn above takes what it cannot): two
 // waves per SIMD, every operand software-pipelined in registers ahead of its
 // MFMAs, the split of step s+1 beside the MFMAs of step s (the loads and
 // splits of the last steps are skipped by uniform branches: clamped
@@ -657,14 +592,6 @@ constexpr int kS3TnV2Threads = 512;
 constexpr int kS3TnV2Img = 32 * 256;            // one piece of one step: 32 rows x 128 bf16
 constexpr int kS3TnV2Lds = 2 * 3 * kS3TnV2Img;  // 2 stages x 3 pieces = 48 KB
 
-// byte offset of 16-byte chunk `ch` (0..15) of row `row` in a [32][256 B] image
-__device__ __forceinline__ int s3_tr_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 template <int TPW, bool BMASK, bool AMAP>
 __global__ __launch_bounds__(kS3TnV2Threads, 1) void k_s3_tn(int M, int N, int K,
@@ -759,7 +686,7 @@ __global__ __launch_bounds__(kS3TnV2Threads, 1) void k_s3_tn(int M, int N, int K
     for (int u = 0; u < 8; ++u) v[u] = ok ? v[u] : 0.f;
     bf16x8 q0, q1, q2;
     split3(v, q0, q1, q2);
-    char* dst = s3tn + buf * 3 * kS3TnV2Img + s3_tr_off(br, bc / 8);
+    char* dst = s3tn + buf * 3 * kS3TnV2Img + tr_off(br, bc / 8);
     *reinterpret_cast<bf16x8*>(dst) = q0;
     *reinterpret_cast<bf16x8*>(dst + kS3TnV2Img) = q1;
     *reinterpret_cast<bf16x8*>(dst + 2 * kS3TnV2Img) = q2;
@@ -767,8 +694,8 @@ __global__ __launch_bounds__(kS3TnV2Threads, 1) void k_s3_tn(int M, int N, int K
   // transposed fragment reads: lane 4q+p of each 16-lane group addresses row
   // r0 + q, columns 4p .. 4p+3 of the column tile (chunk 2 ct + (p >> 1), +8 B)
   const int tq = (lane & 15) >> 2, tp = lane & 3;
-  const int off_lo = s3_tr_off(8 * g + tq, tp >> 1) + 8 * (tp & 1);
-  const int off_hi = s3_tr_off(8 * g + 4 + tq, tp >> 1) + 8 * (tp & 1);
+  const int off_lo = tr_off(8 * g + tq, tp >> 1) + 8 * (tp & 1);
+  const int off_hi = tr_off(8 * g + 4 + tq, tp >> 1) + 8 * (tp & 1);
   auto read_b = [&](int buf, int ct, bf16x8 (&b)[3]) {
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc) {
@@ -855,17 +782,9 @@ bool gemm3_nn_ok(int M, int N, int K, const float* A, uint64_t lda) {
 }
 bool gemm3_tn_ok(int M, int N, int K) { return M >= 1 && K >= 256 && N % 16 == 0; }
 
-// NTS_S3_V1=1: the first-generation TN kernel (k_gemm3_tn), for A/B.  (A
-// second-generation NN kernel with the same register pipeline as k_s3_tn
+// (A second-generation NN kernel with the same register pipeline as k_s3_tn
 // measured equal to k_gemm3_nn on the gathered shape and slower on the dense
 // one — DESIGN §3 — so NN keeps k_gemm3_nn.)
-static bool use_v1() {  // compile-time A/B: -DNTS_S3_V1=1
-#ifdef NTS_S3_V1
-  return NTS_S3_V1 != 0;
-#else
-  return false;
-#endif
-}
 
 int gemm3_nn(nts_hip_ctx* ctx, bool epi, int M, int N, int K, const float* A, uint64_t lda,
              const uint32_t* amap, const float* B, uint64_t ldb, float* C, uint64_t ldc,
@@ -876,13 +795,6 @@ int gemm3_nn(nts_hip_ctx* ctx, bool epi, int M, int N, int K, const float* A, ui
   ex.seed = seed;
   ex.offset = offset;
   ex.amap = amap;
-#ifdef NTS_PROBE_BUILD
-  static const int diag = [] {
-    const char* e = getenv("NTS_S3_DIAG");
-    return e ? atoi(e) : 0;
-  }();
-  ex.diag = diag;
-#endif
   const int ncb = (N + 127) / 128;
   const int nsteps = (K + 31) / 32;
   // the weight's fragment image (scratch: the NN call uses no other scratch)
@@ -893,14 +805,12 @@ int gemm3_nn(nts_hip_ctx* ctx, bool epi, int M, int N, int K, const float* A, ui
   hipLaunchKernelGGL(k_split3_b, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, B, ldb, K,
                      N, total, ncb, bimg);
   NTS_LAUNCH_CHECK();
-#ifndef NTS_NO_X3  // (variant builds: -DNTS_NO_X3 keeps k_gemm3_nn for A/B)
   // the row-gathered NN (k_x3_nn / k_x3_nn7); dense rows reach k_x3_nn7 (and
   // its relu/dropout epilogue) only under NTS_GEMM_SPLIT3_ALL: on C3's dense
   // 100-wide bottom layer it measured 124 us vs 60 us on k_h2_nnd (round 6)
   if ((amap && x3_nn_ok(M, N, K, A, lda)) ||
       (ctx->gemm_mode == NTS_GEMM_SPLIT3_ALL && x3_nn7_ok(M, N, K, A, lda)))
     return x3_nn(ctx, epi, M, N, K, A, lda, amap, bimg, C, ldc, keep_threshold, scale, seed, offset);
-#endif
   if (!amap && x3_nnk_ok(M, N, K, A, lda)) {  // short reductions, dense rows
     const int G = std::max(1, std::min(256 / ncb, ((M + 31) / 32 + 7) / 8));
     const int lds = nsteps * kS3Img;
@@ -946,25 +856,16 @@ int gemm3_tn(nts_hip_ctx* ctx, int M, int N, int K, const float* A, uint64_t lda
              const uint32_t* amap, const float* B, uint64_t ldb, const float* X, uint64_t ldx,
              float bscale, float* C, uint64_t ldc) {
   Gemm3Extra ex;
-#ifdef NTS_PROBE_BUILD
-  static const int diag = [] {
-    const char* e = getenv("NTS_S3_DIAG");
-    return e ? atoi(e) : 0;
-  }();
-  ex.diag = diag;
-#endif
   ex.amap = amap;
   ex.bx = X;
   ex.ldbx = ldx;
   ex.bscale = bscale;
-#ifndef NTS_NO_X3  // (variant builds: -DNTS_NO_X3 keeps k_s3_tn for A/B)
   if (amap && !X && x3_tn_ok(M, N, K, A, lda, B, ldb))
     return x3_tn(ctx, M, N, K, A, lda, amap, B, ldb, C, ldc);
-#endif
   const bool v2_ok = ldb % 4 == 0 && (uintptr_t)B % 16 == 0 &&
                      (!X || (ldx % 4 == 0 && (uintptr_t)X % 16 == 0)) &&
                      (!amap || (uintptr_t)amap % 16 == 0);
-  if (!use_v1() && v2_ok) {
+  if (v2_ok) {
     // v2: 8-wave blocks of up to 8 x TPW column tiles of A x 128 columns,
     // the reduction split so that one block lands on every CU
     constexpr int TPW = 3;

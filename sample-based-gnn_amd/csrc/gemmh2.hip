@@ -33,17 +33,11 @@
 //   k_h2_nn          C = diag(rs[amap]) P[amap] W (+ relu/dropout epilogue)
 //   k_h2_tn          C = P[amap]^T diag(rs[amap]) op(B) (weight gradient),
 //                    op = B or the relu/dropout backward B * bscale where X > 0
-#include "common.hpp"
+#include "mfma_lds.hpp"
 #include <type_traits>
 
 namespace nts_hip {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4h __attribute__((ext_vector_type(4)));
-typedef short s16x4h __attribute__((ext_vector_type(4)));
-typedef short s16x8h __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4h lds_s16x4h;
-typedef __attribute__((address_space(3))) void* lds_ptr_h;
 
 constexpr int kH2Frag = 64 * 16;  // one fragment image: 64 lanes x 8 f16
 
@@ -78,7 +72,7 @@ __device__ __forceinline__ void h2_unpack(const uint32_t (&w)[8], f16x8& p0, f16
 }
 
 // acc += a * b over one 32-deep k-slice (small products first)
-__device__ __forceinline__ f32x4h mfma3(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x4h acc) {
+__device__ __forceinline__ f32x4 mfma3(const f16x8 (&a)[2], const f16x8 (&b)[2], f32x4 acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], acc, 0, 0, 0);
@@ -275,37 +269,10 @@ __global__ __launch_bounds__(512) void k_h2_prep_w(const float* __restrict__ B, 
 }
 
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lds_addr_h(const void* p) {
-  return (uint32_t)(uintptr_t)(lds_ptr_h)p;
-}
-// 16 bytes per lane from `src` to LDS (wave-uniform base `lds`) + 16 * lane
-// (inline asm: see gemm3.hip — a compiler-visible LDS DMA drains the pipeline)
-__device__ __forceinline__ void glds16h(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds)
-      : "memory");
-}
-__device__ __forceinline__ void raw_barrier_h() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // CUs the one-block-per-CU pair-table GEMMs spread over (k_h2_nn3/4 row
-// tiles, k_h2_tn4 k-chunks, k_h2_nnd tiles): 256, or NTS_GEMM_CUS (A/B: a grid
-// below the CU count leaves CUs to the pipelined sampler's blocks instead of
-// waiting for them)
-static int gemm_cus() {  // compile-time A/B: -DNTS_GEMM_CUS=n
-#ifdef NTS_GEMM_CUS
-  return NTS_GEMM_CUS > 0 && NTS_GEMM_CUS <= 256 ? NTS_GEMM_CUS : 256;
-#else
-  return 256;
-#endif
-}
+// tiles, k_h2_tn4 k-chunks, k_h2_nnd tiles)
+constexpr int kGemmCus = 256;
 
 struct H2Extra {
   uint32_t keep_threshold = 0;  // EPI: relu + inverted dropout (common.hpp dropout_*)
@@ -355,7 +322,7 @@ __global__ __launch_bounds__(kH2NnThreads, 1) void k_h2_nn(int M, int N, int K,
   const int t_lo = (int)(gw * T / W), t_hi = (int)((gw + 1) * T / W);
   const int nsteps = K / 32;
   const size_t bstride = (size_t)gridDim.y * kH2Img;
-  const uint32_t lsb = lds_addr_h(sb), lsa = lds_addr_h(sa);
+  const uint32_t lsb = lds_addr(sb), lsa = lds_addr(sa);
   const char* bsrc = bimg + (size_t)blockIdx.y * kH2Img + wv * 1024 + 16 * lane;
   const int gr = (lane >> 1) & 15, gpo = 8 * (lane >> 5) + 4 * (lane & 1);
   const uint32_t* arow[2];
@@ -372,23 +339,23 @@ __global__ __launch_bounds__(kH2NnThreads, 1) void k_h2_nn(int M, int N, int K,
     const uint32_t dst = lsb + (s & 1) * kH2Img + wv * 1024;
     const char* src = bsrc + (size_t)s * bstride;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) glds16h(src + 8192 * p, dst + 8192 * p);
+    for (int p = 0; p < 2; ++p) glds16(src + 8192 * p, dst + 8192 * p);
   };
   auto issue_a = [&](int s) {
     const uint32_t dst = lsa + (s % 3) * kH2NnA + wv * kH2NnAWave;
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) glds16h(arow[rt] + 32 * s + 16 * q, dst + rt * 2048 + q * 1024);
+      for (int q = 0; q < 2; ++q) glds16(arow[rt] + 32 * s + 16 * q, dst + rt * 2048 + q * 1024);
   };
-  f32x4h acc[2][8];
+  f32x4 acc[2][8];
   for (int rd = 0; rd < rounds; ++rd) {
     const int nt = min(2, max(0, t_hi - (t_lo + 2 * rd)));
     set_rows(rd);
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-      for (int ct = 0; ct < 8; ++ct) acc[rt][ct] = f32x4h{0.f, 0.f, 0.f, 0.f};
+      for (int ct = 0; ct < 8; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
     issue_b(0);
     if (nsteps > 0) issue_a(0);
     if (nsteps > 1) issue_a(1);
@@ -397,7 +364,7 @@ __global__ __launch_bounds__(kH2NnThreads, 1) void k_h2_nn(int M, int N, int K,
       // per step a wave issues 2 (B) + 4 (A) pieces
       if (s + 1 < nsteps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      raw_barrier_h();
+      raw_barrier();
       if (s + 1 < nsteps) issue_b(s + 1);
       if (s + 2 < nsteps) issue_a(s + 2);
       if (nt == 0) continue;
@@ -420,7 +387,7 @@ __global__ __launch_bounds__(kH2NnThreads, 1) void k_h2_nn(int M, int N, int K,
         if (nt == 2) acc[1][ct] = mfma3(a[1], b, acc[1][ct]);
       }
     }
-    raw_barrier_h();
+    raw_barrier();
     // acc[rt][ct][v] = C[16 t + 4 g + v][n0 + 16 ct + i]
     float cs[8];
 #pragma unroll
@@ -474,9 +441,6 @@ constexpr int kH2TnThreads = 512;
 constexpr int kH2TnImg = 32 * 256;            // one piece of one step: 32 rows x 128 f16
 constexpr int kH2TnLds = 2 * 2 * kH2TnImg;    // 2 stages x 2 pieces = 32 KB
 
-__device__ __forceinline__ int h2_tr_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 
 template <int TPW, bool BMASK, bool AMAP>
 __global__ __launch_bounds__(kH2TnThreads, 1) void k_h2_tn(int M, int N, int K,
@@ -518,11 +482,11 @@ __global__ __launch_bounds__(kH2TnThreads, 1) void k_h2_tn(int M, int N, int K,
 #pragma unroll
   for (int u = 0; u < 8; ++u) bexp[u] = bok ? col_exp(n0 + bc + u) : 0;
 
-  f32x4h acc[TPW][8];
+  f32x4 acc[TPW][8];
 #pragma unroll
   for (int t = 0; t < TPW; ++t)
 #pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[t][ct] = f32x4h{0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < 8; ++ct) acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   uint32_t rid[2][8];
   uint32_t xa[TPW][8];
   f16x8 pa[TPW][2];
@@ -583,20 +547,20 @@ __global__ __launch_bounds__(kH2TnThreads, 1) void k_h2_tn(int M, int N, int K,
     for (int u = 0; u < 8; ++u) w[u] = ok ? h2_pair(ldexpf(v[u] * brs, bexp[u])) : 0u;
     f16x8 q0, q1;
     h2_unpack(w, q0, q1);
-    char* dst = h2tn + buf * 2 * kH2TnImg + h2_tr_off(br, bc / 8);
+    char* dst = h2tn + buf * 2 * kH2TnImg + tr_off(br, bc / 8);
     *reinterpret_cast<f16x8*>(dst) = q0;
     *reinterpret_cast<f16x8*>(dst + kH2TnImg) = q1;
   };
   const int tq = (lane & 15) >> 2, tp = lane & 3;
-  const int off_lo = h2_tr_off(8 * g + tq, tp >> 1) + 8 * (tp & 1);
-  const int off_hi = h2_tr_off(8 * g + 4 + tq, tp >> 1) + 8 * (tp & 1);
+  const int off_lo = tr_off(8 * g + tq, tp >> 1) + 8 * (tp & 1);
+  const int off_hi = tr_off(8 * g + 4 + tq, tp >> 1) + 8 * (tp & 1);
   auto read_b = [&](int buf, int ct, f16x8 (&b)[2]) {
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) {
       const char* img = h2tn + (buf * 2 + pc) * kH2TnImg;
-      const s16x4h lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4h*)(img + (off_lo ^ (32 * ct))));
-      const s16x4h hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4h*)(img + (off_hi ^ (32 * ct))));
-      const s16x8h c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (off_lo ^ (32 * ct))));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (off_hi ^ (32 * ct))));
+      const s16x8 c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       b[pc] = __builtin_bit_cast(f16x8, c);
     }
   };
@@ -711,11 +675,11 @@ __global__ __launch_bounds__(kH2TnThreads, 1) void k_h2_tn2(int M, int N, int K,
 #pragma unroll
   for (int u = 0; u < 8; ++u) bexp[u] = bok ? col_exp(n0 + bc + u) : 0;
 
-  f32x4h acc[TPW][8];
+  f32x4 acc[TPW][8];
 #pragma unroll
   for (int t = 0; t < TPW; ++t)
 #pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[t][ct] = f32x4h{0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < 8; ++ct) acc[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
   uint32_t xa[3][TPW][8];
   float4 braw[3][2], xraw[3][BMASK ? 2 : 1];
   float bsc[3];
@@ -768,20 +732,20 @@ __global__ __launch_bounds__(kH2TnThreads, 1) void k_h2_tn2(int M, int N, int K,
     for (int u = 0; u < 8; ++u) w[u] = ok ? h2_pair(ldexpf(v[u] * sc, bexp[u])) : 0u;
     f16x8 q0, q1;
     h2_unpack(w, q0, q1);
-    char* dst = h2tn2 + buf * 2 * kH2TnImg + h2_tr_off(br, bc / 8);
+    char* dst = h2tn2 + buf * 2 * kH2TnImg + tr_off(br, bc / 8);
     *reinterpret_cast<f16x8*>(dst) = q0;
     *reinterpret_cast<f16x8*>(dst + kH2TnImg) = q1;
   };
   const int tq = (lane & 15) >> 2, tp = lane & 3;
-  const int off_lo = h2_tr_off(8 * g + tq, tp >> 1) + 8 * (tp & 1);
-  const int off_hi = h2_tr_off(8 * g + 4 + tq, tp >> 1) + 8 * (tp & 1);
+  const int off_lo = tr_off(8 * g + tq, tp >> 1) + 8 * (tp & 1);
+  const int off_hi = tr_off(8 * g + 4 + tq, tp >> 1) + 8 * (tp & 1);
   auto read_b = [&](int buf, int ct, f16x8 (&b)[2]) {
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) {
       const char* img = h2tn2 + (buf * 2 + pc) * kH2TnImg;
-      const s16x4h lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4h*)(img + (off_lo ^ (32 * ct))));
-      const s16x4h hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4h*)(img + (off_hi ^ (32 * ct))));
-      const s16x8h c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (off_lo ^ (32 * ct))));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + (off_hi ^ (32 * ct))));
+      const s16x8 c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       b[pc] = __builtin_bit_cast(f16x8, c);
     }
   };
@@ -885,11 +849,8 @@ __device__ __forceinline__ uint32_t h2_swz(int row) { return (uint32_t)(4 * (row
 // TN v4: the structure above on v_mfma_f32_32x32x16_f16 (full-rate f16 MFMA
 // at K = 16; the 16x16x16 form issues at the 16x16x32 form's cycles for half
 // the work: 232 vs 183 us at C2, measured and dropped).
-// DIAG (timing probes only, NTS_TN4_DIAG; results are garbage): bit 0 skips
-// the MFMAs, bit 1 stops streaming after the first two steps, bit 2 skips the
-// partial-slab stores
 // RP (pitch 2560 only): row-aligned LDS-DMA pieces, as k_h2_nn3
-template <int TPW, int DIAG = 0, bool RP = false>
+template <int TPW, bool RP = false>
 __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const char* __restrict__ Q,
                                                             uint64_t ldq, int pitch, int plane_bytes,
                                                             const float* __restrict__ B, uint64_t ldb,
@@ -974,7 +935,7 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
 #pragma unroll
     for (int u = 0; u < 4; ++u) bexp[u] = sce[sc + u];
   }
-  const uint32_t lsx = (uint32_t)(uintptr_t)(lds_ptr_h)sx, lsbr = (uint32_t)(uintptr_t)(lds_ptr_h)sbr;
+  const uint32_t lsx = lds_addr(sx), lsbr = lds_addr(sbr);
   const int row_chunks = 2 * plane_bytes / 16;
   // X(s): 5 x 1 KB pieces per wave per 16-row step (16 * pitch = 40 KB for Kp 608)
   const int xpieces = xstage / 1024 / 8;
@@ -990,7 +951,7 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
         const uint32_t id = sid[min(16 * s + row, klast)];
         const char* src = Q + (uint64_t)id * ldq + 16 * (gc < row_chunks ? gc : 0);
         const uint32_t dst = __builtin_amdgcn_readfirstlane(lsx + st * xstage + row * 2560 + 1024 * part);
-        if (c < 160) glds16h(src, dst);
+        if (c < 160) glds16(src, dst);
       }
     } else {
       for (int q = 0; q < xpieces; ++q) {
@@ -1000,13 +961,13 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
         const int gc = c ^ (int)h2_swz(row);  // the global chunk this LDS slot holds
         const uint32_t id = sid[min(16 * s + row, klast)];
         const char* src = Q + (uint64_t)id * ldq + 16 * (gc < row_chunks ? gc : 0);
-        glds16h(src, lsx + st * xstage + 1024 * p);
+        glds16(src, lsx + st * xstage + 1024 * p);
       }
     }
     {  // B raw: 1 KB per wave (rows 2 wv, 2 wv + 1)
       const int row = 2 * wv + (lane >> 5);
       const int k = kbeg + min(16 * s + row, klast);
-      glds16h(reinterpret_cast<const char*>(B + (uint64_t)k * ldb + n0) + 16 * (lane & 31),
+      glds16(reinterpret_cast<const char*>(B + (uint64_t)k * ldb + n0) + 16 * (lane & 31),
               lsbr + st * kH2Tn3BRaw + 1024 * wv);
     }
   };
@@ -1034,8 +995,8 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     const int ch = (2 * (64 * wn + 32 * nt + 16 * half + 4 * tp)) / 16;  // 16-byte chunk of the 256-byte row
-    boff[nt][0] = h2_tr_off(r0, ch) + 8 * (tp & 1);
-    boff[nt][1] = h2_tr_off(r1, ch) + 8 * (tp & 1);
+    boff[nt][0] = tr_off(r0, ch) + 8 * (tp & 1);
+    boff[nt][1] = tr_off(r1, ch) + 8 * (tp & 1);
   }
   issue(0);
   issue(1);
@@ -1044,8 +1005,8 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
     if (RP) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
     else if (xpieces == 5) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    raw_barrier_h();
-    if (!(DIAG & 2)) issue(s + 2);
+    raw_barrier();
+    issue(s + 2);
     const int st = s % 3;
     {  // split B(s): row sr, 4 columns
       const float4 v = *reinterpret_cast<const float4*>(sbr + st * kH2Tn3BRaw + 512 * sr + 4 * sc);
@@ -1059,23 +1020,23 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
       const uint32_t lo1 = __builtin_amdgcn_perm(w[3], w[2], 0x05040100u);
       const uint32_t hi0 = __builtin_amdgcn_perm(w[1], w[0], 0x07060302u);
       const uint32_t hi1 = __builtin_amdgcn_perm(w[3], w[2], 0x07060302u);
-      const int off = h2_tr_off(sr, sc / 8) + 8 * ((sc / 4) & 1);
+      const int off = tr_off(sr, sc / 8) + 8 * ((sc / 4) & 1);
       *reinterpret_cast<uint2*>(sbp + off) = make_uint2(lo0, lo1);
       *reinterpret_cast<uint2*>(sbp + kH2Tn3BPl + off) = make_uint2(hi0, hi1);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the planes are written before the barrier
-    raw_barrier_h();
+    raw_barrier();
     auto tr = [&](const char* p) {
-      return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4h*)p);
+      return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
     };
     f16x8 bf[2][2];  // [n tile][plane]
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int pc = 0; pc < 2; ++pc) {
-        const s16x4h lo = tr(sbp + pc * kH2Tn3BPl + boff[nt][0]);
-        const s16x4h hi = tr(sbp + pc * kH2Tn3BPl + boff[nt][1]);
-        const s16x8h c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const s16x4 lo = tr(sbp + pc * kH2Tn3BPl + boff[nt][0]);
+        const s16x4 hi = tr(sbp + pc * kH2Tn3BPl + boff[nt][1]);
+        const s16x8 c = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         bf[nt][pc] = __builtin_bit_cast(f16x8, c);
       }
     const char* xs0 = sx + st * xstage + r0 * pitch;
@@ -1087,9 +1048,9 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
 #pragma unroll
       for (int pc = 0; pc < 2; ++pc) {
         const int c = (pc * plane_bytes + 2 * (32 * (m_lo + t) + 16 * half + 4 * tp)) / 16;
-        const s16x4h lo = tr(xs0 + 16 * (c ^ (int)sw0) + 8 * (tp & 1));
-        const s16x4h hi = tr(xs1 + 16 * (c ^ (int)sw1) + 8 * (tp & 1));
-        const s16x8h cc = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const s16x4 lo = tr(xs0 + 16 * (c ^ (int)sw0) + 8 * (tp & 1));
+        const s16x4 hi = tr(xs1 + 16 * (c ^ (int)sw1) + 8 * (tp & 1));
+        const s16x8 cc = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         af[pc] = __builtin_bit_cast(f16x8, cc);
       }
     };
@@ -1106,19 +1067,15 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
       const f16x8(&af)[2] = afr[t % 2];
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
-        if constexpr (DIAG & 1) {
-          acc[t][nt][0] += (float)af[1][0] + (float)af[0][0] + (float)bf[nt][0][0] + (float)bf[nt][1][0];
-        } else {
-          acc[t][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[nt][0], acc[t][nt], 0, 0, 0);
-          acc[t][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[nt][1], acc[t][nt], 0, 0, 0);
-          acc[t][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[nt][0], acc[t][nt], 0, 0, 0);
-        }
+        acc[t][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1], bf[nt][0], acc[t][nt], 0, 0, 0);
+        acc[t][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[nt][1], acc[t][nt], 0, 0, 0);
+        acc[t][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0], bf[nt][0], acc[t][nt], 0, 0, 0);
       }
     }
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS DMA outlives the block
-  raw_barrier_h();
+  raw_barrier();
   // acc[t][nt][v] = C[32 (m_lo + t) + 8 (v / 4) + 4 h + v % 4][n0 + 64 wn + 32 nt + (lane & 31)]
   float* Cb = C + (uint64_t)split * split_stride;
 #pragma unroll
@@ -1131,7 +1088,7 @@ __global__ __launch_bounds__(kH2Tn3Threads, 1) void k_h2_tn4(int M, int K, const
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
         const int row = 32 * (m_lo + t) + 8 * (v / 4) + 4 * h + (v % 4);
-        if (row < M && (!(DIAG & 4) || acc[t][nt][v] == 1234.5f)) Cb[(uint64_t)row * ldc + n0 + cl] = acc[t][nt][v] * cs;
+        if (row < M) Cb[(uint64_t)row * ldc + n0 + cl] = acc[t][nt][v] * cs;
       }
     }
   }
@@ -1151,15 +1108,13 @@ constexpr int kH2Nn3KS = 20;  // k-steps held in registers (Kp <= 640)
 // fully unrolled with the A fragments read from LDS two steps ahead of their
 // MFMAs (with a runtime count each step's reads were waited on right before
 // its MFMAs: one exposed LDS latency per step).
-// DIAG (timing probes only, NTS_NN3_DIAG; results are garbage): bit 0 skips
-// the MFMAs, bit 1 stops streaming tiles after the first two
 // RP (pitch 2560 only): LDS-DMA pieces cut at row boundaries — three per row
 // (1 KiB, 1 KiB, 512 B with 32 lanes), six per wave and tile — instead of
 // 1 KiB pieces that straddle rows (MI355X_MICROARCH.md, indexed rows into LDS)
 // TR (no epilogue activation, NKS > 0): the MFMA operands swapped so that
 // each lane holds four consecutive columns of one row — one 16-byte store per
 // lane and tile instead of four 4-byte stores
-template <bool EPI, bool AMAP, int NKS = 0, int DIAG = 0, bool RP = false, bool TR = false>
+template <bool EPI, bool AMAP, int NKS = 0, bool RP = false, bool TR = false>
 __global__ __launch_bounds__(512, 1) void k_h2_nn3(int M, int N, int Kp, const char* __restrict__ Q,
                                                   uint64_t ldq, int pitch, int plane_bytes,
                                                   const char* __restrict__ bimg, float* __restrict__ C,
@@ -1201,7 +1156,7 @@ __global__ __launch_bounds__(512, 1) void k_h2_nn3(int M, int N, int Kp, const c
   for (int v = 0; v < 4; ++v)
     cs4[v] = TR ? ldexpf(1.f, -h2_exp(__uint_as_float(ex.cmax[n0 + 16 * wv + 4 * g + v]))) : 0.f;
   __syncthreads();  // (waits for every load above: the LDS DMA counts below start from zero)
-  const uint32_t lsx = (uint32_t)(uintptr_t)(lds_ptr_h)sx;
+  const uint32_t lsx = lds_addr(sx);
   const int xpieces = xstage / 1024 / 8;
   const int row_chunks = 2 * plane_bytes / 16;
 #define NTS_NN3_ISSUE(R_)                                                                        \
@@ -1214,7 +1169,7 @@ __global__ __launch_bounds__(512, 1) void k_h2_nn3(int M, int N, int Kp, const c
         const int gc = c ^ (row & 15);                                                           \
         const char* src = Q + (uint64_t)sid[16 * r_ + row] * ldq + 16 * (gc < row_chunks ? gc : 0); \
         const uint32_t dst_ = __builtin_amdgcn_readfirstlane(lsx + (r_ % 3) * xstage + row * 2560 + 1024 * part); \
-        if (c < 160) glds16h(src, dst_);                                                         \
+        if (c < 160) glds16(src, dst_);                                                         \
       }                                                                                          \
     } else {                                                                                     \
       for (int q = 0; q < xpieces; ++q) {                                                        \
@@ -1223,7 +1178,7 @@ __global__ __launch_bounds__(512, 1) void k_h2_nn3(int M, int N, int Kp, const c
         const int row = o / pitch, c = (o - row * pitch) / 16;                                   \
         const int gc = c ^ (row & 15); /* the global chunk this LDS slot holds */                \
         const char* src = Q + (uint64_t)sid[16 * r_ + row] * ldq + 16 * (gc < row_chunks ? gc : 0); \
-        glds16h(src, lsx + (r_ % 3) * xstage + 1024 * p);                                        \
+        glds16(src, lsx + (r_ % 3) * xstage + 1024 * p);                                        \
       }                                                                                          \
     }                                                                                            \
   } while (0)
@@ -1251,14 +1206,12 @@ __global__ __launch_bounds__(512, 1) void k_h2_nn3(int M, int N, int Kp, const c
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    raw_barrier_h();
-    if (!(DIAG & 2)) NTS_NN3_ISSUE(r + 2);
+    raw_barrier();
+    NTS_NN3_ISSUE(r + 2);
     const char* xs = sx + (r % 3) * xstage + i * pitch;
-    f32x4h acc = f32x4h{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     auto step = [&](int s, const f16x8& a1, const f16x8& a0) {
-      if constexpr (DIAG & 1) {
-        acc[0] += (float)a1[0] + (float)a0[0] + (float)wf[s][0][0] + (float)wf[s][1][0];
-      } else if constexpr (TR) {  // D^T: rows of W^T (columns) x columns of X^T (rows)
+      if constexpr (TR) {  // D^T: rows of W^T (columns) x columns of X^T (rows)
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][0], a1, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][1], a0, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[s][0], a0, acc, 0, 0, 0);
@@ -1319,133 +1272,11 @@ __global__ __launch_bounds__(512, 1) void k_h2_nn3(int M, int N, int Kp, const c
       if (r4 + v < M) C[(uint64_t)(r4 + v) * ldc + col] = o[v];
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS DMA outlives the block
-  raw_barrier_h();
+  raw_barrier();
 #undef NTS_NN3_ISSUE
 }
 
 
-#ifdef NTS_WITH_H2_NN4
-// NN v4 (k_h2_nn4): k_h2_nn3 with FOUR LDS stages, three 16-row tiles in
-// flight per block instead of two (the 160 KB of LDS hold exactly four
-// 16 x 2560-byte stages; Kp = 608, 19 k-steps): the row ids move to registers (lane t of each wave
-// holds its two rows of tile t, read with readlane) and the row scales ride in
-// the planar table's row tails (ldq = 1280 halves: the scale at half 2 Kp,
-// nts_hip_h2_split_rows_planar), so the stages take the whole LDS.  RP pieces
-// (three per row, six per wave and tile), planar rows swizzled by row as in
-// k_h2_nn3; the tail chunk (global chunk 2 Kp / 8) lands in LDS slot
-// 2Kp/8 ^ (row & 15).  No epilogue activation (the transform-first forward).
-template <int NKS>
-__global__ __launch_bounds__(512, 1) void k_h2_nn4(int M, int N, const char* __restrict__ Q,
-                                                  uint64_t ldq, int plane_bytes,
-                                                  const char* __restrict__ bimg, float* __restrict__ C,
-                                                  uint64_t ldc, H2Extra ex) {
-  extern __shared__ __attribute__((aligned(16))) char h2nn4[];
-  constexpr int kPitch = 2560, kStage = 16 * kPitch;
-  char* const sx = h2nn4;  // [4][16][2560]
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int i = lane & 15, g = lane >> 4;
-  const int nb = blockIdx.y, n0 = nb * 128;
-  const int T = (M + 15) / 16;
-  const int t0 = (int)((int64_t)blockIdx.x * T / gridDim.x);
-  const int t1 = (int)((int64_t)(blockIdx.x + 1) * T / gridDim.x);
-  const int nt = t1 - t0;  // <= 64 (host)
-  if (nt <= 0) return;
-  // lane t: the ids of rows 2 wv and 2 wv + 1 of tile t (this wave's DMA rows)
-  uint32_t id0 = 0, id1 = 0;
-  if (lane < nt) {
-    const int64_t r0 = min((int64_t)(t0 + lane) * 16 + 2 * wv, (int64_t)M - 1);
-    const int64_t r1 = min((int64_t)(t0 + lane) * 16 + 2 * wv + 1, (int64_t)M - 1);
-    id0 = ex.amap[r0];
-    id1 = ex.amap[r1];
-  }
-  f16x8 wf[kH2Nn3KS][2];
-#pragma unroll
-  for (int s = 0; s < kH2Nn3KS; ++s)
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-      wf[s][p] = s < NKS ? *reinterpret_cast<const f16x8*>(
-                               bimg + ((size_t)s * gridDim.y + nb) * kH2Img + wv * 2 * kH2Frag +
-                               p * kH2Frag + 16 * lane)
-                         : f16x8{};
-  const float cs = ldexpf(1.f, -h2_exp(__uint_as_float(ex.cmax[n0 + 16 * wv + i])));
-  __syncthreads();  // (waits for every load above: the LDS DMA counts below start from zero)
-  const uint32_t lsx = (uint32_t)(uintptr_t)(lds_ptr_h)sx;
-  auto issue = [&](int r) {
-    const int rr = min(r, nt - 1);
-    const uint32_t ida = __builtin_amdgcn_readlane(id0, rr), idb = __builtin_amdgcn_readlane(id1, rr);
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-      const int row = q / 3, part = q - 3 * row;  // this wave's rows 2 wv + row
-      const int grow = 2 * wv + row;
-      const int c = 64 * part + lane;              // LDS slot (16-byte chunk) of the row
-      const int gc = c ^ (grow & 15);               // the global chunk it holds (tail included)
-      const char* src = Q + (uint64_t)(row ? idb : ida) * ldq + 16 * gc;
-      const uint32_t dst = __builtin_amdgcn_readfirstlane(lsx + (rr & 3) * kStage + grow * kPitch + 1024 * part);
-      if (c < 160) glds16h(src, dst);
-    }
-  };
-  const int pch = plane_bytes / 16;  // chunks per plane
-  const int tail = 2 * pch;          // the row-scale chunk
-  issue(0);
-  issue(1);
-  issue(2);
-  for (int r = 0; r < nt; ++r) {
-    // tile r landed.  Younger VMEM ops (6 DMA pieces per tile, 4 stores per
-    // round): r = 0: tiles 1, 2; r = 1: tile 2, tile 3 + round 0's stores;
-    // r = 2: + tile 4 + round 1's stores; r >= 3: round r-3's stores, then
-    // (tile, stores) of rounds r-2 and r-1
-    if (r == 0) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if (r == 1) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if (r == 2) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-    raw_barrier_h();  // also: every wave is past tile r-1 (its stage takes tile r+3)
-    issue(r + 3);
-    const char* st = sx + (r & 3) * kStage;
-    const char* xs = st + i * kPitch;
-    // the row scales of this lane's output rows 4 g + v (row tails)
-    float rsr[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int row = 4 * g + v;
-      rsr[v] = *reinterpret_cast<const float*>(st + row * kPitch + 16 * (tail ^ row));
-    }
-    f32x4h acc = f32x4h{0.f, 0.f, 0.f, 0.f};
-    auto ld1 = [&](int s) { return *reinterpret_cast<const f16x8*>(xs + 16 * ((pch + 4 * s + g) ^ i)); };
-    auto ld0 = [&](int s) { return *reinterpret_cast<const f16x8*>(xs + 16 * ((4 * s + g) ^ i)); };
-    f16x8 b1[3], b0[3];  // fragments of steps s, s+1, s+2 (ring of three)
-    b1[0] = ld1(0);
-    b0[0] = ld0(0);
-    b1[1] = ld1(1);
-    b0[1] = ld0(1);
-#pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      if (s + 2 < NKS) {
-        b1[(s + 2) % 3] = ld1(s + 2);
-        b0[(s + 2) % 3] = ld0(s + 2);
-      }
-      __builtin_amdgcn_sched_barrier(0);  // keep the reads two steps ahead
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1[s % 3], wf[s][0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0[s % 3], wf[s][1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0[s % 3], wf[s][0], acc, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // acc[v] = H[16 (t0 + r) + 4 g + v][n0 + 16 wv + i]
-    const int64_t r4 = (int64_t)(t0 + r) * 16 + 4 * g;
-    const uint32_t col = (uint32_t)(n0 + 16 * wv + i);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const float o = acc[v] * cs * rsr[v];
-      // (four stores per round, as the counted waits assume: only the last
-      // tile of the last block can lose lanes, and no counted wait follows it)
-      if (r4 + v < M) C[(uint64_t)(r4 + v) * ldc + col] = o;
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS DMA outlives the block
-  raw_barrier_h();
-}
-
-#endif  // NTS_WITH_H2_NN4
 
 // ---------------------------------------------------------------------------
 // NN with a DYNAMIC fp32 A of at most 128 columns (the aggregate-first layer
@@ -1505,7 +1336,7 @@ __global__ __launch_bounds__(512) void k_h2_nnd(int M, int K, const float* __res
     cs[j] = ldexpf(1.f, -h2_exp(__uint_as_float(cmax[16 * gct + i])));
   }
   __syncthreads();  // every load above done: the counted waits below start from zero
-  const uint32_t lraw = (uint32_t)(uintptr_t)(lds_ptr_h)raw;
+  const uint32_t lraw = lds_addr(raw);
   // tile r's rows -> raw stage r % 3 (row-major [TM][KP] fp32); chunks past
   // the row's K load the row's first chunk (zeroed by the split), rows past M
   // the last row
@@ -1518,7 +1349,7 @@ __global__ __launch_bounds__(512) void k_h2_nnd(int M, int K, const float* __res
       const int64_t grow = min((int64_t)(t0 + r) * TM + row, (int64_t)M - 1);
       // (pieces past the tile land in the stage's padding: any valid address)
       const float* src = pc < TM * CPR ? A + (uint64_t)grow * lda + (4 * c < K ? 4 * c : 0) : A;
-      glds16h(src, lraw + (r % 3) * RAW + 16 * (q * 512 + wv * 64));
+      glds16(src, lraw + (r % 3) * RAW + 16 * (q * 512 + wv * 64));
     }
   };
   issue(0);
@@ -1531,7 +1362,7 @@ __global__ __launch_bounds__(512) void k_h2_nnd(int M, int K, const float* __res
     if (r == 0) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPC) : "memory");
     else if (r == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPC + NQ + NS) : "memory");
     else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPC + 2 * (NQ + NS)) : "memory");
-    raw_barrier_h();  // also: every wave is past tile r-1's plane reads
+    raw_barrier();  // also: every wave is past tile r-1's plane reads
     issue(r + 2);
     const int64_t row0 = (int64_t)(t0 + r) * TM;
     {  // split: row sr, columns 8 sc .. 8 sc + 7 (16 lanes per row; sc >= PCH: zeros)
@@ -1575,15 +1406,15 @@ __global__ __launch_bounds__(512) void k_h2_nnd(int M, int K, const float* __res
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    raw_barrier_h();
-    f32x4h acc[2][NTW];
+    raw_barrier();
+    f32x4 acc[2][NTW];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int ar = 16 * h + i;
       const char* a0p = pl + ar * PRB;
       const int swz = ar & 15;
 #pragma unroll
-      for (int j = 0; j < NTW; ++j) acc[h][j] = f32x4h{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < NTW; ++j) acc[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < NKS; ++s) {
         const int c = (4 * s + g) ^ swz;
@@ -1654,7 +1485,7 @@ __global__ __launch_bounds__(512) void k_h2_nnd(int M, int K, const float* __res
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no LDS DMA outlives the block
-  raw_barrier_h();
+  raw_barrier();
 }
 
 static int colmax(nts_hip_ctx* ctx, const float* B, uint64_t ldb, uint64_t K, int N, const float* rs,
@@ -1861,7 +1692,7 @@ static int h2p_tn_gather(nts_hip_ctx* ctx, int M, int N, int K, const uint16_t* 
   const int nnb = N / 128;
   const int pitch = (4 * Kp + 511) / 512 * 512;
   const int ksteps = (K + 15) / 16;
-  int splits = std::max(1, std::min(gemm_cus() / nnb, ksteps / 8));
+  int splits = std::max(1, std::min(kGemmCus / nnb, ksteps / 8));
   int kchunk = ((ksteps + splits - 1) / splits) * 16;
   if (kchunk > 960) kchunk = 960;  // the chunk's ids + row scales in LDS (8 B per row)
   splits = (K + kchunk - 1) / kchunk;
@@ -1882,33 +1713,18 @@ static int h2p_tn_gather(nts_hip_ctx* ctx, int M, int N, int K, const uint16_t* 
   ex.cparts = part_max;
   ex.rpp = rows_per_part;
   ex.nparts_ld = (uint64_t)N;
-#ifdef NTS_PROBE_BUILD  // timing probes (scripts/probe): results are garbage
-  static const int diag = [] {
-    const char* e = getenv("NTS_TN4_DIAG");
-    return e ? atoi(e) : 0;
-  }();
-#endif
-#ifndef NTS_TN4_RP  // row-aligned DMA pieces (compile-time A/B: -DNTS_TN4_RP=0)
-#define NTS_TN4_RP 1
-#endif
-  constexpr bool rp = NTS_TN4_RP != 0;
-#define NTS_TN4(D, ...)                                                                            \
+#define NTS_TN4(RP)                                                                                \
   do {                                                                                             \
-    NTS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_h2_tn4<TPW, D, ##__VA_ARGS__>), \
+    NTS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_h2_tn4<TPW, RP>),             \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds));             \
-    hipLaunchKernelGGL((k_h2_tn4<TPW, D, ##__VA_ARGS__>), dim3(nnb * splits), dim3(kH2Tn3Threads), lds, \
+    hipLaunchKernelGGL((k_h2_tn4<TPW, RP>), dim3(nnb * splits), dim3(kH2Tn3Threads), lds,          \
                        ctx->stream, M, K, reinterpret_cast<const char*>(Q), ldq * sizeof(uint16_t), \
                        pitch, 2 * Kp, B, ldb, out, ldo, kchunk,                                    \
                        splits > 1 ? stride : (uint64_t)0, nnb, ex);                                \
   } while (0)
-#ifdef NTS_PROBE_BUILD
-  if (diag == 1) NTS_TN4(1);
-  else if (diag == 2) NTS_TN4(2);
-  else if (diag == 4) NTS_TN4(4);
-  else
-#endif
-  if (rp && pitch == 2560) NTS_TN4(0, true);
-  else NTS_TN4(0);
+  // row-aligned DMA pieces where the pitch allows them
+  if (pitch == 2560) NTS_TN4(true);
+  else NTS_TN4(false);
 #undef NTS_TN4
   NTS_LAUNCH_CHECK();
   if (splits == 1) return NTS_OK;
@@ -1970,7 +1786,7 @@ extern "C" int nts_hip_gemm_h2p_gather(nts_hip_ctx* ctx, int relu_dropout, int M
   // blocks, each with fewer tiles (large bottom frontiers, e.g. C5)
   const int tile_cap = (160 * 1024 - 3 * 16 * pitch) / (2 * 4 * 16);
   NTS_CHECK_ARG(tile_cap >= 1, "row pitch too large for the NN stage");
-  int gx = std::max({1, std::min(gemm_cus() / ncb, T), (T + tile_cap - 1) / tile_cap});
+  int gx = std::max({1, std::min(kGemmCus / ncb, T), (T + tile_cap - 1) / tile_cap});
   const int max_tiles = (T + gx - 1) / gx;
   const int lds = 3 * 16 * pitch + 2 * 4 * 16 * max_tiles;
   NTS_CHECK_ARG(lds <= 160 * 1024, "row-id stage");
@@ -1983,64 +1799,25 @@ extern "C" int nts_hip_gemm_h2p_gather(nts_hip_ctx* ctx, int relu_dropout, int M
                        reinterpret_cast<const char*>(Q), ldq * sizeof(uint16_t), pitch, 2 * Kp, bimg, C, \
                        ldc, ex);                                                                  \
   } while (0)
-#ifdef NTS_PROBE_BUILD  // timing probes (scripts/probe): results are garbage
-  static const int diag = [] {
-    const char* e = getenv("NTS_NN3_DIAG");
-    return e ? atoi(e) : 0;
-  }();
-#else
-  constexpr int diag = 0;
-#endif
-  // row-aligned LDS-DMA pieces (compile-time A/B: -DNTS_NN3_RP=0 keeps the
-  // row-straddling ones)
-#ifndef NTS_NN3_RP
-#define NTS_NN3_RP 1
-#endif
-  constexpr bool rp = NTS_NN3_RP != 0;
-  // 16-byte row stores from swapped MFMA operands (-DNTS_NN3_TR=1; measured:
-  // alone 174-178 -> 168-170 us, in the C2 bench no gain — off by default)
-#ifndef NTS_NN3_TR
-#define NTS_NN3_TR 0
-#endif
-  constexpr bool tr = NTS_NN3_TR != 0;
+  // row-aligned LDS-DMA pieces (rather than row-straddling ones)
+  constexpr bool rp = true;
+  // 16-byte row stores from swapped MFMA operands (measured: alone 174-178 ->
+  // 168-170 us, in the C2 bench no gain — off)
+  constexpr bool tr = false;
   const bool tr_ok = tr && ldc % 4 == 0 && (uintptr_t)C % 16 == 0;
-#ifdef NTS_WITH_H2_NN4
-  // four stages (k_h2_nn4) where the table rows carry their scales in a tail
-  // (ldq >= 2 Kp + 8 halves: 2560-byte rows) and the step count is compiled
-  // in.  Variant builds only (make variant V=nn4 VFLAGS=-DNTS_WITH_H2_NN4):
-  // measured no faster than k_h2_nn3 in the C2 bench (r04d: 152.6 vs ~158 us
-  // alone, 164.9 vs 170.9 us pipelined)
-  if (!relu_dropout && a_rows && pitch == 2560 && ldq >= 2 * (uint64_t)Kp + 8 && nsteps == 19) {
-    gx = std::max(gx, (T + 63) / 64);  // <= 64 tiles per block (lane-held row ids)
-    constexpr int lds4 = 4 * 16 * 2560;
-    NTS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_h2_nn4<19>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
-    hipLaunchKernelGGL((k_h2_nn4<19>), dim3(gx, ncb), dim3(512), lds4, ctx->stream, M, N,
-                       reinterpret_cast<const char*>(Q), ldq * sizeof(uint16_t), 2 * Kp, bimg, C,
-                       ldc, ex);
-    NTS_LAUNCH_CHECK();
-    return NTS_OK;
-  }
-#endif
   // compile-time step counts for the feature widths the driver meets
-  // (C2: 602 -> Kp 608); NTS_NN3_DIAG=4 forces the runtime-count loop
+  // (C2: 602 -> Kp 608)
   if (relu_dropout) {
     if (a_rows) NTS_H2NN3(true, true); else NTS_H2NN3(true, false);
-#ifdef NTS_PROBE_BUILD
-  } else if (a_rows && diag == 1) {
-    NTS_H2NN3(false, true, 19, 1);
-  } else if (a_rows && diag == 2) {
-    NTS_H2NN3(false, true, 19, 2);
-#endif
-  } else if (a_rows && nsteps == 19 && diag != 4 && pitch == 2560 && rp && tr_ok) {
-    NTS_H2NN3(false, true, 19, 0, true, true);
-  } else if (a_rows && nsteps == 19 && diag != 4 && pitch == 2560 && rp) {
-    NTS_H2NN3(false, true, 19, 0, true);
-  } else if (a_rows && nsteps == 19 && diag != 4) {
+  } else if (a_rows && nsteps == 19 && pitch == 2560 && rp && tr_ok) {
+    NTS_H2NN3(false, true, 19, true, true);
+  } else if (a_rows && nsteps == 19 && pitch == 2560 && rp) {
+    NTS_H2NN3(false, true, 19, true);
+  } else if (a_rows && nsteps == 19) {
     NTS_H2NN3(false, true, 19);
-  } else if (a_rows && nsteps == 20 && diag != 4 && pitch == 2560 && rp && tr_ok) {
-    NTS_H2NN3(false, true, 20, 0, true, true);
-  } else if (a_rows && nsteps == 20 && diag != 4) {
+  } else if (a_rows && nsteps == 20 && pitch == 2560 && rp && tr_ok) {
+    NTS_H2NN3(false, true, 20, true, true);
+  } else if (a_rows && nsteps == 20) {
     NTS_H2NN3(false, true, 20);
   } else {
     if (a_rows) NTS_H2NN3(false, true); else NTS_H2NN3(false, false);
@@ -2080,7 +1857,7 @@ extern "C" int nts_hip_gemm_h2d_act(nts_hip_ctx* ctx, int relu_dropout, int M, i
   ex.seed = seed;
   ex.offset = offset;
   const int T = (M + kH2dTM - 1) / kH2dTM;
-  const dim3 grid(std::max(1, std::min(gemm_cus(), T)));  // one block per CU (~156 VGPRs)
+  const dim3 grid(std::max(1, std::min(kGemmCus, T)));  // one block per CU (~156 VGPRs)
 #define NTS_H2D(NK, NT, E, QO)                                                                   \
   hipLaunchKernelGGL((k_h2_nnd<NK, NT, E, QO>), grid, dim3(512), 0, ctx->stream, M, K, A, lda,   \
                      bimg, ncb, cmax, C, ldc, Q, ldq, rs, ex)

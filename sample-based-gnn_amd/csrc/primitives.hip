@@ -389,76 +389,13 @@ int scan1_exclusive(nts_hip_ctx* ctx, const uint32_t* in, uint32_t* out, const u
   return NTS_OK;
 }
 
-// Two-kernel count + scan (NTS_SCAN1=0): per-tile totals of the counts (the
-// counts themselves written to co), then k_scan_down over co in place (it
-// also writes e_size).  No tile waits on another tile's published state.
-// Measured against the single-pass form next to the training stream (one
-// MI355X, bench): C2 0.857 vs 0.851 ms/step, C3 0.708 vs 0.699, GPU sampler
-// alone 4.84 vs 5.07 G edges/s at C2 — the single-pass form stays the default.
-__global__ __launch_bounds__(kScanThreads) void k_count_reduce(CountArgs ca,
-                                                               uint32_t* __restrict__ co,
-                                                               uint32_t* __restrict__ partials) {
-  const int t = threadIdx.x;
-  const uint32_t v_req = *ca.v_in;
-  const uint64_t n = min(v_req, ca.v_cap);
-  if (blockIdx.x == 0 && t == 0) {
-    ca.sizes[0] = (uint32_t)n;
-    ca.sizes[3] = v_req > ca.v_cap ? 1u : 0u;
-  }
-  const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
-  uint32_t s = 0;
-  if (base < n) {
-    uint32_t x[kScanItems];
-    count_items(ca, base, n, x);
-#pragma unroll
-    for (int k = 0; k < kScanItems; ++k) {
-      const uint64_t i = base + (uint64_t)k * kScanThreads + t;
-      if (i < n) co[i] = x[k];
-      s += x[k];
-    }
-  }
-  __shared__ uint32_t wsum[kScanThreads / kWave];
-  uint32_t tot;
-  (void)block_excl_scan(s, wsum, &tot);
-  if (t == 0) partials[blockIdx.x] = tot;
-}
-
 size_t count_scan_tmp_elems(uint64_t v_cap) { return scan_tmp_elems<uint32_t>(v_cap) + 64; }
 
-// -DNTS_SCAN1=0: the two-kernel scans for count_scan and the frontier
-// compaction (A/B); default the single-pass look-back scans
-bool scan1_enabled() {  // compile-time A/B: -DNTS_SCAN1=0
-#ifdef NTS_SCAN1
-  return NTS_SCAN1 != 0;
-#else
-  return true;
-#endif
-}
-
-int count_scan(nts_hip_ctx* ctx, const CountArgs& ca, uint32_t* co, hipStream_t stream,
-               uint32_t* tmp) {
-  if (!scan1_enabled() && tmp) {
-    const uint64_t nb = (uint64_t)ca.v_cap / kScanTile + 1;
-    uint32_t* partials = tmp;
-    uint32_t* rest = tmp + (nb + 1 + 63) / 64 * 64;
-    hipLaunchKernelGGL(k_count_reduce, dim3((uint32_t)nb), dim3(kScanThreads), 0, stream, ca, co,
-                       partials);
-    NTS_LAUNCH_CHECK();
-    if (nb <= kScanDirectTiles) {
-      hipLaunchKernelGGL((k_scan_down<uint32_t, true, true>), dim3((uint32_t)nb),
-                         dim3(kScanThreads), 0, stream, (const uint32_t*)co, co,
-                         (const uint32_t*)ca.sizes, (uint64_t)ca.v_cap, (const uint32_t*)partials,
-                         ca.sizes, ca.e_cap);
-    } else {
-      NTS_RET(scan_exclusive<uint32_t>(partials, partials, nullptr, nb, rest, stream));
-      hipLaunchKernelGGL((k_scan_down<uint32_t, false, true>), dim3((uint32_t)nb),
-                         dim3(kScanThreads), 0, stream, (const uint32_t*)co, co,
-                         (const uint32_t*)ca.sizes, (uint64_t)ca.v_cap, (const uint32_t*)partials,
-                         ca.sizes, ca.e_cap);
-    }
-    NTS_LAUNCH_CHECK();
-    return NTS_OK;
-  }
+// The single-pass look-back scan.  (A two-kernel count + scan, where no tile
+// waits on another tile's published state, measured next to the training
+// stream on one MI355X: C2 0.857 vs 0.851 ms/step, C3 0.708 vs 0.699, GPU
+// sampler alone 4.84 vs 5.07 G edges/s at C2 — retired.)
+int count_scan(nts_hip_ctx* ctx, const CountArgs& ca, uint32_t* co, hipStream_t stream) {
   constexpr int kCountItems = 4;
   const uint64_t nb = (uint64_t)ca.v_cap / (kScanThreads * kCountItems) + 1;
   NTS_RET(ensure_scan_state(ctx, (nb + 63) / 64 * 64));

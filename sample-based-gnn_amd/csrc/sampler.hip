@@ -21,7 +21,7 @@
 //     cuda/ntsCUDATransferKernel.cuh:1107-1125) and without host round trips,
 //   * CSR transpose = stable radix sort of (local src, edge id) -> identical to
 //     the reference's serial fill order (ascending dst), atomic-free.
-#include "common.hpp"
+#include "mfma_lds.hpp"
 
 #include <type_traits>
 
@@ -305,7 +305,7 @@ constexpr int kGrpPerWave = kWave / kGrp;
 // dup |= an earlier accepted lane J of the 16-lane group drew val (J < gl):
 // lane J of each 16-lane row by a DPP row broadcast (row_newbcast) instead of
 // __shfl's ds_bpermute — sampler alone 5.98-6.02 -> 6.04-6.07 G edges/s,
-// bit-identical (scripts/ab/r05_ba.sh)
+// bit-identical
 template <int J>
 struct GrpDupScan {
   static __device__ __forceinline__ void run(bool& dup, uint32_t val, int gl, uint32_t okm) {
@@ -669,20 +669,14 @@ constexpr uint32_t kMtPos = 8192;   // kept positions staged in LDS before the f
 // layer of up to kMtSmallV dsts is cut into kMtChunkSmall-dst chunks, one of
 // up to kMtMaxChunks x kMtChunkMid into kMtChunkMid-dst chunks: a window
 // table's lanes walk fewer dsts each and more chunks fill the CUs (C2 with
-// --rng mt, scripts/ab/r04_n.sh: 4.60 ms/step at 64 / 256, 4.50 at 32 / 128,
+// --rng mt: 4.60 ms/step at 64 / 256, 4.50 at 32 / 128,
 // 4.80 at 64 / 64 — the resolver's chain over the chunks grows; 5.29 with
 // 256 everywhere; round 5, with the tables at 8 / 6 waves per SIMD,
-// scripts/ab/r05_aj.sh: mid 96 / 128 / 192 -> 3.63 / 3.59-3.61 / 3.57,
+// mid 96 / 128 / 192 -> 3.63 / 3.59-3.61 / 3.57,
 // small 24 / 32 / 48 -> 3.56-3.58 / 3.59-3.61 / 3.60); words staged per chunk
-#ifndef NTS_MT_CHUNK_MID  // (A/B builds)
-#define NTS_MT_CHUNK_MID 192
-#endif
-#ifndef NTS_MT_CHUNK_SMALL
-#define NTS_MT_CHUNK_SMALL 32
-#endif
 constexpr uint32_t kMtChunk = 256;
-constexpr uint32_t kMtChunkMid = NTS_MT_CHUNK_MID;
-constexpr uint32_t kMtChunkSmall = NTS_MT_CHUNK_SMALL;
+constexpr uint32_t kMtChunkMid = 192;
+constexpr uint32_t kMtChunkSmall = 32;
 constexpr uint32_t kMtSmallV = 32768;
 constexpr uint32_t kMtStage = 12288;
 
@@ -1063,9 +1057,6 @@ __global__ __launch_bounds__(256) void k_mtp_tables(const uint4* __restrict__ in
                                                    uint32_t* __restrict__ tabs) {
   __shared__ uint4 inf[kMtChunk];
   __shared__ uint32_t bs[kMtChunk];
-#ifdef NTS_MT_LDS_LST  // (A/B build: the fallback walk's list in LDS, NMAX words a lane)
-  __shared__ uint32_t lst[NMAX * 256];
-#endif
   __shared__ float red[2][4];
   __shared__ uint32_t uu[4][2][192];  // per wave: the union windows of two dsts
   const int t = threadIdx.x;
@@ -1094,24 +1085,18 @@ __global__ __launch_bounds__(256) void k_mtp_tables(const uint4* __restrict__ in
   __syncthreads();
   const float mm = red[0][0] + red[0][1] + red[0][2] + red[0][3];
   const float vv = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-// the window's half-width in sigmas (compile-time A/B; a Delta outside its
-// window, ~0.3 % of the chunks at 3, is walked out by the resolver): C2 --rng
-// mt 3.57-3.59 / 3.57-3.58 / 3.52-3.55 ms/step at 4 / 3.5 / 3 (r05_ax.sh)
-#ifndef NTS_MT_SIGMA
-#define NTS_MT_SIGMA 3.f
-#endif
-  const float h = ceilf(NTS_MT_SIGMA * sqrtf(vv)) + 8.f;
+  // the window's half-width in sigmas (a Delta outside its window, ~0.3 % of
+  // the chunks at 3, is walked out by the resolver): C2 --rng mt 3.57-3.59 /
+  // 3.57-3.58 / 3.52-3.55 ms/step at 4 / 3.5 / 3
+  constexpr float kSigma = 3.f;
+  const float h = ceilf(kSigma * sqrtf(vv)) + 8.f;
   const uint32_t lo = (uint32_t)fmaxf(0.f, floorf(mm - h));
   const uint32_t wn = min(kMtWmax, (uint32_t)(mm + h - (float)lo) + 1u);
   if (blockIdx.x == 0 && t == 0) win[k] = make_uint2(lo, wn);
   // waves whose entries all lie past the window leave (no block barrier
   // below): the last block of a window is ~half idle otherwise (3.60-3.62 ->
-  // 3.57-3.59 ms/step, r05_ax.sh)
-#ifdef NTS_MT_BLOCK_EXIT  // (A/B build: whole blocks only)
-  if (blockIdx.x * 256u >= wn) return;
-#else
+  // 3.57-3.59 ms/step)
   if (blockIdx.x * 256u + (uint32_t)(t & ~63) >= wn) return;
-#endif
   const uint32_t slot = blockIdx.x * 256u + t;
   const uint64_t a0 = *a0p;
   const MtWords W{ring, a0, (uint32_t)(gen_hi - a0)};
@@ -1124,10 +1109,8 @@ __global__ __launch_bounds__(256) void k_mtp_tables(const uint4* __restrict__ in
   // from there.  The next drawing dst's union is fetched while this one is
   // checked, based at this step's smallest Delta (Deltas only grow).  A wave
   // whose starts spread wider than the union reads its own words.
-#ifndef NTS_MT_NWX
-#define NTS_MT_NWX 8  // words past the n-th in a lane's window (A/B, r04_o: 4 / 6 / 8 / 12 -> 4.20 / 3.95 / 3.91 / 3.89 ms)
-#endif
-  constexpr int NW = NMAX + NTS_MT_NWX;
+  // words past the n-th in a lane's window (4 / 6 / 8 / 12 -> 4.20 / 3.95 / 3.91 / 3.89 ms)
+  constexpr int NW = NMAX + 8;
   constexpr int kU = 192;
   const int wvi = t >> 6, ln = t & 63;
   // wave minimum / maximum (every lane active here): DPP moves within each
@@ -1187,16 +1170,12 @@ __global__ __launch_bounds__(256) void k_mtp_tables(const uint4* __restrict__ in
       used = regs_consume<NW>(cur, f.y, f.z, f.w, lemire);
     }
     if (used == 0) {
-#ifdef NTS_MT_LDS_LST
-      used = lane_consume<NMAX>(W, p, f.y, f.z, f.w, lemire, lst + t, 256);
-#else
       // the rare sequential walk keeps its list in private memory (scratch):
       // in LDS it cost NMAX KiB a block and capped the kernel at 7 (NMAX 10)
       // or 4 (NMAX 25) waves per SIMD
       uint32_t plst[NMAX];
       asm volatile("" ::"v"(plst) : "memory");  // (its address escapes: scratch, not registers)
       used = lane_consume<NMAX>(W, p, f.y, f.z, f.w, lemire, plst, 1);
-#endif
     }
     dl += used - f.y;
     if (jn < cnt) store_union(buf ^ 1, inf[jn]);
@@ -1216,15 +1195,6 @@ constexpr int kRing = 5;
 constexpr uint32_t kMtMaxChunks = 4096;  // the host keeps v_cap <= kMtMaxChunks * csz
 constexpr int kRingOps = kMtWmax * 4 / (16 * kWave);  // LDS-DMA instructions per window
 
-__device__ __forceinline__ void glds16(const void* src, uint32_t lds) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds)
-      : "memory");
-}
 
 template <int NMAX>
 __global__ __launch_bounds__(kWave) void k_mtp_resolve(const uint4* __restrict__ info,
@@ -2045,7 +2015,7 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
     ca.omit_key = o->omit_key;
     ca.omit_loc = o->omit_loc;
     ca.omit_row = o->omit_row;
-    NTS_RET(count_scan(ctx, ca, o->column_offset, st, t_scan_co));
+    NTS_RET(count_scan(ctx, ca, o->column_offset, st));
   }
 
   // 2) selection (marks the frontier; the byte map is all zeros here: it is
@@ -2083,11 +2053,7 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
     }
   } else {
     const int lem = rng_mode == NTS_RNG_MT19937_LEMIRE ? 1 : 0;
-#ifdef NTS_MT_DEBUG  // (debug builds: -DNTS_MT_DEBUG=1)
-    constexpr int mt_dbg = NTS_MT_DEBUG;
-#else
-    constexpr int mt_dbg = 0;
-#endif
+    constexpr int mt_dbg = 0;  // (the kernels' debug-dump argument: off)
     uint4* info = reinterpret_cast<uint4*>(t_mt);
     // the stream words this layer may read are generated (ahead, on the
     // ring's side stream) before its kernels run
@@ -2172,11 +2138,10 @@ frontier:
   }
 
   // 3) frontier: ascending compaction of the byte map — single pass up to
-  // kMarkFusedMaxTiles tiles (C2's 57), else (and with the two-kernel scans,
-  // NTS_SCAN1=0) count + write: at products' 598 tiles the look-back chain
-  // took 23 us a layer against 5 + 9 for the pair (scripts/r05_c3tr.sh)
+  // kMarkFusedMaxTiles tiles (C2's 57), else count + write: at products' 598
+  // tiles the look-back chain took 23 us a layer against 5 + 9 for the pair
   constexpr uint32_t kMarkFusedMaxTiles = 256;
-  if (scan1_enabled() && nblk_marks <= kMarkFusedMaxTiles) {
+  if (nblk_marks <= kMarkFusedMaxTiles) {
     NTS_RET(ensure_scan_state(ctx, scan1_state_elems((uint64_t)nblk_marks * 4096)));
     hipLaunchKernelGGL(k_mark_fused, dim3(nblk_marks), dim3(kMarkThreads), 0, st, ctx->marks,
                        nblk_marks, V, o->s_cap, o->source, ctx->src_index, o->sizes,
@@ -2229,7 +2194,6 @@ frontier:
   // or counted by the pass before with atomics (65 vs 16 us).
   if (csr) {
     const uint32_t bits = ceil_log2((uint64_t)o->s_cap + 1);
-#ifndef NTS_CSR_RADIX2  // (A/B build: the two-pass radix sort + k_csr_finalize)
     if (bits >= 11 && bits <= 19) {
       // one radix pass on the high H bits, then k_csr_bucket per 2^L sources
       const uint32_t H = std::min(9u, bits - 6), L = bits - H;
@@ -2261,7 +2225,6 @@ frontier:
       NTS_LAUNCH_CHECK();
       return NTS_OK;
     }
-#endif
     NTS_RET(radix_sort_pairs(o->row_indices, nullptr, t_skey, t_seid, o->sizes + 1, o->e_cap,
                              bits, t_sort, st, ctx));
     hipLaunchKernelGGL(k_csr_finalize, dim3(ge), dim3(256), 0, st, t_skey, t_seid, o->edge_dst,

@@ -33,11 +33,8 @@
 namespace nts_hip {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-// waves (16-row tiles) per block; a build-time knob for A/B builds
-#ifndef NTS_TOP_WAVES
-#define NTS_TOP_WAVES 4
-#endif
-constexpr int kTopWaves = NTS_TOP_WAVES;
+// waves per block
+constexpr int kTopWaves = 4;
 constexpr int kTopThreads = kTopWaves * 64;
 constexpr int kTopRowsPerWave = 16;
 constexpr int kTopRows = kTopWaves * kTopRowsPerWave;  // rows per block
@@ -60,8 +57,8 @@ struct TopArgs {
 // quad of the 8-lane half (half mirror) and the other half (row mirror) — the
 // pairing tree of an xor butterfly 1, 2, 4, 8, so every lane ends with the
 // same sum as that butterfly's.  (The butterfly by __shfl_xor is a chain of
-// ds_bpermute round trips: 4-8 us of each block's softmax phase,
-// NTS_TOP_TIMING.)
+// ds_bpermute round trips: 4-8 us of each block's softmax phase, by phase
+// timers.)
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
@@ -252,200 +249,23 @@ __device__ __forceinline__ void log_softmax2(const f32x4 (&z)[NCT], int C, int i
   }
 }
 
+// LDS of the retired one-wave-per-tile form: still the K x C bound that the
+// argument check (top_check) applies
 static inline size_t top_lds(int K, int Cp) {
   return ((size_t)K * Cp + (size_t)kTopWaves * 16 * (K + 4) + (size_t)kTopRows * Cp) *
          sizeof(float);
 }
 
-template <int NCT, bool LOSS, bool GRAD, bool VEC4>
-__global__ __launch_bounds__(kTopThreads) void k_top_xent(TopArgs a) {
-  constexpr int CP = 16 * NCT;
-  extern __shared__ float smem[];
-  __shared__ float wl[kTopWaves];
-  __shared__ uint32_t wc[kTopWaves];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = lane & 15, g = lane >> 4;
-  const int K = a.K;
-  float* sW = smem;                                      // [K][CP]
-  float* sY = smem + K * CP + w * 16 * (K + 4);          // this wave's [16][K + 4]
-  float* dz = smem + K * CP + kTopWaves * 16 * (K + 4) + w * 16 * CP;  // [16][CP]
-  const int r0 = blockIdx.x * kTopRows + w * kTopRowsPerWave;
-  stage_y<VEC4>(a, sY, r0, lane);
-  stage_w<CP>(a, sW);
-  __syncthreads();
-  f32x4 z[NCT];
-  wave_logits<NCT>(K, sW, sY, i, g, z);
-  float lp[NCT][4], lp2[NCT][4];
-  log_softmax2<NCT>(z, a.C, i, lp, lp2);
-  int tgt[4];
-#pragma unroll
-  for (int v = 0; v < 4; ++v) {
-    const int r = r0 + 4 * g + v;
-    tgt[v] = r < a.n ? (int)a.labels[r] : -1;
-  }
-  if (LOSS) {
-    // -lp2[target] of each valid row, summed in a fixed order (v, then lanes)
-    float l = 0.f;
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct)
-        if (16 * ct + i == tgt[v]) l -= lp2[ct][v];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, kWave);
-    if (lane == 0) wl[w] = l;
-    if (a.cpart) {
-      // getCorrect (toolkits/GCN_SAMPLE_ALLGPU.hpp:166-172): argmax of the
-      // log_softmax output (first index among equal values, as torch's
-      // argmax) == label
-      uint32_t ok = 0;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        float best = -INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-          if (16 * ct + i < a.C && lp[ct][v] > best) {
-            best = lp[ct][v];
-            bi = 16 * ct + i;
-          }
-        bi = grp_argmax(best, bi);
-        ok += (i == 0 && tgt[v] >= 0 && bi == tgt[v]) ? 1u : 0u;
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) ok += __shfl_down(ok, o, kWave);
-      if (lane == 0) wc[w] = ok;
-    }
-  }
-  if (GRAD) {
-    const float gl = (a.grad ? *a.grad : 1.0f) / (float)a.n;
-    // nll backward, then y = log_softmax(x): dx = dy - exp(y) * sum(dy), twice
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int r = r0 + 4 * g + v;
-      float d2[NCT], s2 = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) {
-        d2[ct] = (16 * ct + i == tgt[v]) ? -gl : 0.f;
-        s2 += d2[ct];
-      }
-      s2 = grp_sum(s2);
-      float d1[NCT], s1 = 0.f;
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) {
-        const bool on = 16 * ct + i < a.C;
-        d1[ct] = on ? d2[ct] - expf(lp2[ct][v]) * s2 : 0.f;
-        s1 += d1[ct];
-      }
-      s1 = grp_sum(s1);
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) {
-        const bool on = 16 * ct + i < a.C && r < a.n;
-        dz[(4 * g + v) * CP + 16 * ct + i] = on ? d1[ct] - expf(lp[ct][v]) * s1 : 0.f;
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's dZ stores landed
-    __builtin_amdgcn_wave_barrier();
-    // dY [16 x K] = dZ [16 x CP] W^T: A lane (i,g) = dZ[i][c], B = W[k = 16 kt + i][c].
-    // Four k tiles at a time: four independent MFMA chains share each dZ read
-    // (one chain per tile was a serial LDS-read -> MFMA latency chain, and a
-    // block of 4 waves has one wave per SIMD to hide it).  Tiles past K/16
-    // repeat the last one and are not stored; each chain's order is unchanged.
-    const int nkt = K / 16;
-    constexpr int KT = 4;
-    for (int kt0 = 0; kt0 < nkt; kt0 += KT) {
-      f32x4 acc[KT];
-      int ktu[KT];
-#pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        ktu[u] = min(kt0 + u, nkt - 1);
-      }
-#pragma unroll
-      for (int c0 = 0; c0 < CP; c0 += 4) {
-        const float av = dz[i * CP + c0 + g];
-#pragma unroll
-        for (int u = 0; u < KT; ++u)
-          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, sW[(16 * ktu[u] + i) * CP + c0 + g], acc[u],
-                                                        0, 0, 0);
-      }
-#pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        if (kt0 + u >= nkt) break;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int r = r0 + 4 * g + v;
-          if (r < a.n) a.dY[(uint64_t)r * K + 16 * (kt0 + u) + i] = acc[u][v];
-        }
-      }
-    }
-    // dW partial [K x CP] = Y^T [K x 16] dZ [16 x CP]:
-    //   A lane (i,g) = Y[r0 + 4s + g][16 kt + i], B = dZ[4s + g][16 ct + i]
-    // two k tiles at a time (2 NCT chains sharing the dZ reads)
-    const uint64_t nslab = (uint64_t)gridDim.x * kTopWaves;
-    const uint64_t slab = (uint64_t)blockIdx.x * kTopWaves + w;
-    constexpr int KW = 2;
-    for (int kt0 = 0; kt0 < nkt; kt0 += KW) {
-      f32x4 acc[KW][NCT];
-      int ktu[KW];
-#pragma unroll
-      for (int u = 0; u < KW; ++u) {
-        ktu[u] = min(kt0 + u, nkt - 1);
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[u][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float bv[NCT];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) bv[ct] = dz[(4 * s + g) * CP + 16 * ct + i];
-#pragma unroll
-        for (int u = 0; u < KW; ++u) {
-          const float av = sY[(4 * s + g) * (K + 4) + 16 * ktu[u] + i];
-#pragma unroll
-          for (int ct = 0; ct < NCT; ++ct)
-            acc[u][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[ct], acc[u][ct], 0, 0, 0);
-        }
-      }
-      // acc[u][ct][v] = dW[16 kt + 4 g + v][16 ct + i] -> chunk (k, ct), lane i
-#pragma unroll
-      for (int u = 0; u < KW; ++u) {
-        if (kt0 + u >= nkt) break;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const uint64_t q = (uint64_t)(16 * (kt0 + u) + 4 * g + v) * NCT + ct;
-            a.part[(q * nslab + slab) * 16 + i] = acc[u][ct][v];
-          }
-      }
-    }
-  }
-  if (LOSS) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float s = 0.f;
-      uint32_t c = 0;
-      for (int q = 0; q < kTopWaves; ++q) {
-        s += wl[q];
-        c += wc[q];
-      }
-      a.lpart[blockIdx.x] = s;
-      if (a.cpart) a.cpart[blockIdx.x] = c;
-    }
-  }
-}
-
-// K-split form (the default): one block of kTopWaves waves per 16-row tile,
-// wave w taking the k tiles kt = w, w + kTopWaves, ... of every product.
-// The per-wave form above runs a whole tile's three products on one wave —
+// K-split form: one block of kTopWaves waves per 16-row tile, wave w taking
+// the k tiles kt = w, w + kTopWaves, ... of every product.
+// The retired per-wave form ran a whole tile's three products on one wave —
 // ~600 dependent v_mfma_f32_16x16x4_f32 at K = 256 with one wave per SIMD,
 // 35 us however few rows (C3: 1,024 rows, 64 waves on 256 CUs).  Here the
 // logits are four partial chains summed in a fixed order (w = 0..3) through
 // LDS; every wave then holds the same Z and log-softmax, wave 0 writes dZ
 // and the loss; dY and dW run on each wave's k tiles (two at a time).  One dW
 // slab per block.  Deterministic; the logits' summation order differs from
-// the per-wave form (NTS_TOP_KSPLIT=0) by rounding only.
+// the per-wave form by rounding only.
 static inline size_t top_ks_lds(int K, int Cp) {
   return ((size_t)K * Cp + (size_t)16 * (K + 4) + (size_t)(kTopWaves + 1) * 16 * Cp) * sizeof(float);
 }
@@ -464,17 +284,9 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   float* zp = sY + 16 * P;         // [NW][16][CP] partial logits
   float* dz = zp + NW * 16 * CP;   // [16][CP]
   const int r0 = blockIdx.x * 16;
-#ifdef NTS_TOP_TIMING  // (probe builds: phase times of two blocks, printf)
-  uint64_t tt[8];
-  int nt_ = 0;
-  auto mark = [&] { tt[nt_++] = wall_clock64(); };
-#else
-  auto mark = [] {};
-#endif
-  mark();
   // the rows' labels and the upstream gradient first: their global loads
   // then overlap the staging instead of following the logits (a dependent
-  // memory latency of 4-6 us per block there, NTS_TOP_TIMING)
+  // memory latency of 4-6 us per block there, measured with phase timers)
   constexpr int VPW = 4 / NW;  // rows 4 g + v per lane group finished by this wave
   static_assert(4 % NW == 0, "kTopWaves must divide 4");
   int tgt[VPW];
@@ -521,7 +333,6 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   }
   stage_w<CP>(a, sW);
   __syncthreads();
-  mark();
   f32x4 z[NCT];
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct) z[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -542,11 +353,10 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
 #pragma unroll
     for (int v = 0; v < 4; ++v) zp[(w * 16 + 4 * g + v) * CP + 16 * ct + i] = z[ct][v];
   __syncthreads();
-  mark();
   // each wave finishes the rows 4 g + v of its own v (v = w, w + NW, ...): the
   // logits' sum over the waves' k-splits, log_softmax twice (log_softmax2's
   // arithmetic per row), the loss and accuracy terms and dZ — a quarter of the
-  // tile each (the whole tile on wave 0 was 4-6 us of every block, NTS_TOP_TIMING)
+  // tile each (the whole tile on wave 0 was 4-6 us of every block, phase timers)
   float lw = 0.f;
   uint32_t okw = 0;
 #pragma unroll
@@ -642,7 +452,6 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   }
   if (GRAD) {
     __syncthreads();
-    mark();
     // dY [16 x K] = dZ W^T on this wave's k tiles, two at a time
     constexpr int KT = 2;
     for (int j0 = w; j0 < nkt; j0 += KT * NW) {
@@ -672,7 +481,6 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
         }
       }
     }
-    mark();
     // dW slab of this block [K x CP] = Y^T dZ, rows of this wave's k tiles
     const uint64_t nslab = gridDim.x, slab = blockIdx.x;
     for (int j0 = w; j0 < nkt; j0 += KT * NW) {
@@ -711,7 +519,6 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
       }
     }
   }
-  mark();
   if (LOSS) {
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -725,14 +532,6 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
       if (a.cpart) a.cpart[blockIdx.x] = c;
     }
   }
-#ifdef NTS_TOP_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  mark();
-  if ((blockIdx.x == 3 || blockIdx.x == gridDim.x - 5) && threadIdx.x == 64 && nt_ == 7)
-    printf("top blk %d: stage %d logits %d softmax %d dY %d dW %d tail %d (x10ns)\n", blockIdx.x,
-           (int)(tt[1] - tt[0]), (int)(tt[2] - tt[1]), (int)(tt[3] - tt[2]), (int)(tt[4] - tt[3]),
-           (int)(tt[5] - tt[4]), (int)(tt[6] - tt[5]));
-#endif
 }
 
 // Blocks [0, K*NCT): dW chunk (k, ct) = sum over the wave slabs — thread
@@ -798,16 +597,8 @@ __global__ __launch_bounds__(256) void k_top_finish(const float* __restrict__ pa
   (void)K;
 }
 
-static bool top_ksplit() {  // compile-time A/B: -DNTS_TOP_KSPLIT=0 runs the per-wave form
-#ifdef NTS_TOP_KSPLIT
-  return NTS_TOP_KSPLIT != 0;
-#else
-  return true;
-#endif
-}
-
 template <int NCT, bool LOSS, bool GRAD>
-static int launch_top_ks(hipStream_t st, int nblk, const TopArgs& a) {
+static int launch_top(hipStream_t st, int nblk, const TopArgs& a) {
   const size_t lds = top_ks_lds(a.K, 16 * NCT);
   const bool v4 = a.ldy % 4 == 0 && (uintptr_t)a.Y % 16 == 0;
   const void* f = v4 ? reinterpret_cast<const void*>(&k_top_xent_ks<NCT, LOSS, GRAD, true>)
@@ -818,24 +609,6 @@ static int launch_top_ks(hipStream_t st, int nblk, const TopArgs& a) {
                        st, a);
   else
     hipLaunchKernelGGL((k_top_xent_ks<NCT, LOSS, GRAD, false>), dim3(nblk), dim3(kTopThreads), lds,
-                       st, a);
-  NTS_LAUNCH_CHECK();
-  return NTS_OK;
-}
-
-template <int NCT, bool LOSS, bool GRAD>
-static int launch_top(hipStream_t st, int nblk, const TopArgs& a) {
-  if (top_ksplit()) return launch_top_ks<NCT, LOSS, GRAD>(st, nblk, a);
-  const size_t lds = top_lds(a.K, 16 * NCT);
-  const bool v4 = a.ldy % 4 == 0 && (uintptr_t)a.Y % 16 == 0;
-  const void* f = v4 ? reinterpret_cast<const void*>(&k_top_xent<NCT, LOSS, GRAD, true>)
-                     : reinterpret_cast<const void*>(&k_top_xent<NCT, LOSS, GRAD, false>);
-  NTS_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (v4)
-    hipLaunchKernelGGL((k_top_xent<NCT, LOSS, GRAD, true>), dim3(nblk), dim3(kTopThreads), lds,
-                       st, a);
-  else
-    hipLaunchKernelGGL((k_top_xent<NCT, LOSS, GRAD, false>), dim3(nblk), dim3(kTopThreads), lds,
                        st, a);
   NTS_LAUNCH_CHECK();
   return NTS_OK;
@@ -891,9 +664,7 @@ static int top_run(nts_hip_ctx* ctx, bool loss_on, bool grad_on, const float* Y,
                    const float* grad_loss, float* loss, float* dY, float* dW, uint32_t* correct) {
   NTS_RET(top_check(ctx, n, K, C, ldy));
   const int Cp = (C + 15) / 16 * 16;
-  const bool ks = top_ksplit();
-  const int nblk = ks ? (n + 15) / 16 : (n + kTopRows - 1) / kTopRows;
-  const int nslab = ks ? nblk : nblk * kTopWaves;
+  const int nblk = (n + 15) / 16, nslab = nblk;  // one dW slab per 16-row block
   const size_t lp = ((size_t)nblk + 63) / 64 * 64;
   NTS_RET(ensure_scratch(
       ctx, (2 * lp + (grad_on ? (size_t)nslab * K * Cp : 0)) * sizeof(float)));

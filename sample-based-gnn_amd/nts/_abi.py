@@ -14,7 +14,7 @@ import pathlib
 import torch  # noqa: F401  (must be loaded first: its HIP runtime is the one we share)
 
 _HERE = pathlib.Path(__file__).resolve().parent
-# NTS_HIP_LIB: another build of the same ABI (A/B builds of a tuning knob)
+# NTS_HIP_LIB: another build of the same ABI (the A/B of two checkouts)
 LIB_PATH = pathlib.Path(os.environ["NTS_HIP_LIB"]) if os.environ.get("NTS_HIP_LIB") else _HERE / "lib" / "libnts_hip.so"
 
 NTS_OK = 0

@@ -944,64 +944,39 @@ struct HipBottomTFFn : public torch::autograd::Function<HipBottomTFFn> {
     uint32_t rpp = 0;
     // dZ = dX1 ⊙ mask once per dst row, then the plain CSR gather (measured
     // faster than applying the mask to every gathered row:
-    // nts_hip_spmm_csr_bwd_masked reads two rows per edge); the A/B build
-    // -DNTS_TF_MASKED_BWD selects the fused form
-#ifdef NTS_TF_MASKED_BWD
-    constexpr bool fused_mask = true;
-#else
-    constexpr bool fused_mask = false;
-#endif
-    if (fused_mask && !sg->grad_premasked) {
-      if (prof) prof->begin(KernelProfiler::BOTTOM_BWD, st);
-      hip_check(nts_hip_spmm_csr_bwd_masked(cs->ctx(), sg->dev_r_o(), sg->dev_c_i(),
-                                            sg->dev_e_w_b(), nullptr, (uint32_t)s,
-                                            g.data_ptr<float>(), (uint64_t)N, X1.data_ptr<float>(),
-                                            (uint64_t)N, scale, (uint32_t)N, dH.data_ptr<float>(),
-                                            (uint64_t)N),
-                "nts_hip_spmm_csr_bwd_masked");
-      if (prof)
-        prof->end(KernelProfiler::BOTTOM_BWD, st,
-                  8.0 * N * v + 8.0 * sg->e_size + 4.0 * (s + 1) + 4.0 * N * s);
+    // nts_hip_spmm_csr_bwd_masked reads two rows per edge); premasked: the
+    // graph op above applied the activation backward already (post_mask)
+    NtsVar dZ = sg->grad_premasked ? g : torch::empty({std::max<int64_t>(v, 1), N}, f32_opts(dev));
+    if (!sg->grad_premasked)
+      hip_check(nts_hip_act_backward(cs->ctx(), (uint32_t)v, (uint32_t)N, g.data_ptr<float>(),
+                                     (uint64_t)N, X1.data_ptr<float>(), (uint64_t)N, scale,
+                                     dZ.data_ptr<float>(), (uint64_t)N),
+                "nts_hip_act_backward");
+    if (prof) prof->begin(KernelProfiler::BOTTOM_BWD, st);
+    // the planar-table TN GEMM takes dH's column maxima per part of rows
+    // from this gather's epilogue (one read of dH instead of two)
+    // (its float4 rows need 16-byte aligned dZ / dH rows: else the plain gather)
+    const bool cm_rows = N <= 512 && N % 4 == 0 && (uintptr_t)dZ.data_ptr<float>() % 16 == 0 &&
+                         (uintptr_t)dH.data_ptr<float>() % 16 == 0;
+    if (pairs_q && cm_rows) {
+      rpp = nts_hip_csr_bwd_colmax_rows_per_part((uint32_t)N);
+      const int64_t nparts = (std::max<int64_t>(s, 1) + rpp - 1) / rpp;
+      colmax = torch::empty({nparts, N}, torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA, dev));
+      hip_check(nts_hip_spmm_csr_bwd_colmax(
+                    cs->ctx(), sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(), nullptr, (uint32_t)s,
+                    dZ.data_ptr<float>(), (uint64_t)N, (uint32_t)N, dH.data_ptr<float>(), (uint64_t)N,
+                    reinterpret_cast<uint32_t*>(colmax.data_ptr<int32_t>()),
+                    pairs_q->rs.data_ptr<float>(), sg->dev_src()),
+                "nts_hip_spmm_csr_bwd_colmax");
     } else {
-      // the graph op above applied the activation backward already (post_mask)
-      NtsVar dZ = sg->grad_premasked ? g : torch::empty({std::max<int64_t>(v, 1), N}, f32_opts(dev));
-      if (!sg->grad_premasked)
-        hip_check(nts_hip_act_backward(cs->ctx(), (uint32_t)v, (uint32_t)N, g.data_ptr<float>(),
-                                       (uint64_t)N, X1.data_ptr<float>(), (uint64_t)N, scale,
-                                       dZ.data_ptr<float>(), (uint64_t)N),
-                  "nts_hip_act_backward");
-      if (prof) prof->begin(KernelProfiler::BOTTOM_BWD, st);
-      // the planar-table TN GEMM takes dH's column maxima per part of rows
-      // from this gather's epilogue (one read of dH instead of two); the A/B
-      // build -DNTS_TN_CHUNK_SCALES keeps its own per-chunk pre-pass
-#ifdef NTS_TN_CHUNK_SCALES
-      constexpr bool chunk_scales = true;
-#else
-      constexpr bool chunk_scales = false;
-#endif
-      // (its float4 rows need 16-byte aligned dZ / dH rows: else the plain gather)
-      const bool cm_rows = N <= 512 && N % 4 == 0 && (uintptr_t)dZ.data_ptr<float>() % 16 == 0 &&
-                           (uintptr_t)dH.data_ptr<float>() % 16 == 0;
-      if (pairs_q && !chunk_scales && cm_rows) {
-        rpp = nts_hip_csr_bwd_colmax_rows_per_part((uint32_t)N);
-        const int64_t nparts = (std::max<int64_t>(s, 1) + rpp - 1) / rpp;
-        colmax = torch::empty({nparts, N}, torch::TensorOptions().dtype(torch::kInt32).device(torch::kCUDA, dev));
-        hip_check(nts_hip_spmm_csr_bwd_colmax(
-                      cs->ctx(), sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(), nullptr, (uint32_t)s,
-                      dZ.data_ptr<float>(), (uint64_t)N, (uint32_t)N, dH.data_ptr<float>(), (uint64_t)N,
-                      reinterpret_cast<uint32_t*>(colmax.data_ptr<int32_t>()),
-                      pairs_q->rs.data_ptr<float>(), sg->dev_src()),
-                  "nts_hip_spmm_csr_bwd_colmax");
-      } else {
-        hip_check(nts_hip_spmm_csr_bwd(cs->ctx(), sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(),
-                                       nullptr, (uint32_t)s, dZ.data_ptr<float>(), (uint64_t)N,
-                                       (uint32_t)N, dH.data_ptr<float>(), (uint64_t)N),
-                  "nts_hip_spmm_csr_bwd");
-      }
-      if (prof)
-        prof->end(KernelProfiler::BOTTOM_BWD, st,
-                  4.0 * N * v + 8.0 * sg->e_size + 4.0 * (s + 1) + 4.0 * N * s);
+      hip_check(nts_hip_spmm_csr_bwd(cs->ctx(), sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(),
+                                     nullptr, (uint32_t)s, dZ.data_ptr<float>(), (uint64_t)N,
+                                     (uint32_t)N, dH.data_ptr<float>(), (uint64_t)N),
+                "nts_hip_spmm_csr_bwd");
     }
+    if (prof)
+      prof->end(KernelProfiler::BOTTOM_BWD, st,
+                4.0 * N * v + 8.0 * sg->e_size + 4.0 * (s + 1) + 4.0 * N * s);
     NtsVar dW = torch::empty({F, N}, W.options());
     if (g_before_bwd_gemm) g_before_bwd_gemm();
     if (prof) prof->begin(KernelProfiler::GATHER_GEMM_TN, st);

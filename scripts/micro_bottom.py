@@ -1,12 +1,9 @@
 """Micro benchmark of the transform-first bottom layer's planar pair-table GEMMs
 at C2 size, alone on the GPU: k_h2_nn3 (H = X[src] W) and k_h2_tn4 (dW =
 X[src]^T dH, per-part column maxima given) — time per call and effective
-rate on the algorithmic bytes.  Timing probes (NTS_NN3_DIAG / NTS_TN4_DIAG)
-exist only in the probe build of the library:
+rate on the algorithmic bytes.
 
-  make -C sample-based-gnn_amd/csrc probe
-  NTS_HIP_LIB=scripts/probe/lib/libnts_hip.so NTS_NN3_DIAG=1 python scripts/micro_bottom.py
-  python scripts/micro_bottom.py [--iters 20]
+  python scripts/micro_bottom.py [--iters 20]   (NTS_HIP_LIB selects another checkout's library)
 """
 import argparse
 import json

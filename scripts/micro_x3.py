@@ -3,7 +3,7 @@
 alone on the GPU: time per call and the rate on the algorithmic bytes (the
 gathered fp32 rows once, the other operand and the output once).
 
-  python scripts/micro_x3.py [--iters 20]   (NTS_HIP_LIB selects a variant build)
+  python scripts/micro_x3.py [--iters 20]   (NTS_HIP_LIB selects another checkout's library)
 """
 import argparse
 import json

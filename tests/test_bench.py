@@ -175,10 +175,10 @@ def test_child_argv_keeps_the_workload(bench):
 
 
 def test_product_library_env_knobs():
-    """The product library reads at most these environment variables (the
-    A/B variants are compile-time flags of `make variant`, the timing probes
-    exist only in `make probe`): a debugging aid for hangs and the two
-    MT19937 walker selections the kernel tests A/B."""
+    """The product library reads at most these environment variables: a
+    debugging aid for hangs and the two MT19937 walker selections the kernel
+    tests A/B.  (The sources carry no compile-time A/B switches and no
+    timing-probe build: the one configuration is the source text.)"""
     import re
     lib = ROOT / "sample-based-gnn_amd" / "nts" / "lib" / "libnts_hip.so"
     if not lib.exists():
@@ -189,8 +189,7 @@ def test_product_library_env_knobs():
 
 
 def test_host_extension_env_knobs():
-    """The C++ host layer reads only two timing aids (NTS_TF_* /
-    NTS_TN_CHUNK_SCALES are compile-time A/B flags since round 6)."""
+    """The C++ host layer reads only two timing aids."""
     import re
     ext = ROOT / "sample-based-gnn_amd" / "nts" / "lib" / "host_build" / "nts_host_ext.so"
     if not ext.exists():
