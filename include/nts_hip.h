@@ -635,6 +635,33 @@ int nts_hip_linear_xent_train(nts_hip_ctx *ctx, const float *Y, uint64_t ldy, in
                               const float *W, int C, const int64_t *labels, float *loss,
                               float *dY, float *dW, uint32_t *correct);
 
+/* Multi-label form of the same layer (no reference counterpart): logits
+ * Z = Y W and the mean sigmoid binary cross-entropy over all n * C entries,
+ *   loss = mean(max(z, 0) - z t + log1p(exp(-|z|)))      (finite for finite z)
+ * i.e. binary_cross_entropy_with_logits(Y W, T) with mean reduction.
+ * Y [n x K] (ld ldy), W [K x C] row-major, C <= 128, K % 16 == 0 and K x C
+ * within the kernel's LDS; other shapes return NTS_ERR_INVALID
+ * and launch nothing.  Targets are bit-packed: label_bits [V x wpr] uint32,
+ * wpr >= ceil(C / 32) words per vertex, label c of vertex u = bit c & 31 of
+ * label_bits[u * wpr + (c >> 5)]; bits at positions >= C are ignored.  Row r
+ * takes the labels of vertex index[r] (the batch's seeds), or of vertex r
+ * when index == NULL.  Writes the scalar loss (device).  counts != NULL:
+ * counts[0..2] += the true positives, false positives and false negatives of
+ * the prediction z > 0 over the n * C entries (micro-F1 = 2 tp / (2 tp + fp +
+ * fn)), accumulated on the device. */
+int nts_hip_linear_bce_fwd(nts_hip_ctx *ctx, const float *Y, uint64_t ldy, int n, int K,
+                           const float *W, int C, const uint32_t *label_bits, uint32_t wpr,
+                           const uint32_t *index, float *loss, uint32_t *counts);
+/* Training call: the same loss and counts (bit-identical to
+ * nts_hip_linear_bce_fwd) AND the gradients for an upstream gradient of
+ * exactly 1: dZ = (sigmoid(z) - t) / (n C), dY [n x K] (ld K) = dZ W^T,
+ * dW [K x C] = Y^T dZ.  Deterministic: fixed-order reductions, no
+ * floating-point atomics. */
+int nts_hip_linear_bce_train(nts_hip_ctx *ctx, const float *Y, uint64_t ldy, int n, int K,
+                             const float *W, int C, const uint32_t *label_bits, uint32_t wpr,
+                             const uint32_t *index, float *loss, float *dY, float *dW,
+                             uint32_t *counts);
+
 /* ---- optimiser ---------------------------------------------------------- */
 /* Fused Adam step on one parameter (n elements), element-wise identical to
  *  bias_correction != 0: Parameter::learnC2C_with_decay_Adam (core/NtsScheduler.hpp:863-880)

@@ -17,6 +17,10 @@
 // forward = <LOSS>, backward = <GRAD>, train = <LOSS, GRAD> (bit-identical
 // to forward + backward with grad 1: same code, same orders).
 //
+// (The multi-label form of the layer, sigmoid BCE over bit-packed targets with
+// the micro-F1 counters, is k_top_bce_ks below: the same block shape, shared
+// staging and products, an element-wise middle.)
+//
 // One wave owns 16 rows.  Its Y tile is staged into LDS with coalesced
 // 16-byte loads (all issued up front), then the three products run on
 // v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulation):
@@ -100,8 +104,8 @@ __device__ __forceinline__ int grp_argmax(float best, int bi) {
 // 16-byte aligned W the whole matrix goes as float4s, up to 16 per thread in
 // flight (one memory round trip for C3's 256 x 47; the scalar form took six
 // dependent rounds of 8 loads, most of the kernel at 16 blocks).
-template <int CP>
-__device__ __forceinline__ void stage_w(const TopArgs& a, float* sW) {
+template <int CP, class Args>
+__device__ __forceinline__ void stage_w(const Args& a, float* sW) {
   const int C = a.C, KC = a.K * C;
   if (((uintptr_t)a.W & 15) == 0) {
     const float4* W4 = reinterpret_cast<const float4*>(a.W);
@@ -270,69 +274,55 @@ static inline size_t top_ks_lds(int K, int Cp) {
   return ((size_t)K * Cp + (size_t)16 * (K + 4) + (size_t)(kTopWaves + 1) * 16 * Cp) * sizeof(float);
 }
 
-template <int NCT, bool LOSS, bool GRAD, bool VEC4>
-__global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
-  constexpr int CP = 16 * NCT, NW = kTopWaves;
-  extern __shared__ float smem[];
-  __shared__ float wl[NW];
-  __shared__ uint32_t wc[NW];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = lane & 15, g = lane >> 4;
-  const int K = a.K, P = K + 4, nkt = K / 16;
-  float* sW = smem;                // [K][CP]
-  float* sY = sW + K * CP;         // [16][K + 4]
-  float* zp = sY + 16 * P;         // [NW][16][CP] partial logits
-  float* dz = zp + NW * 16 * CP;   // [16][CP]
-  const int r0 = blockIdx.x * 16;
-  // the rows' labels and the upstream gradient first: their global loads
-  // then overlap the staging instead of following the logits (a dependent
-  // memory latency of 4-6 us per block there, measured with phase timers)
-  constexpr int VPW = 4 / NW;  // rows 4 g + v per lane group finished by this wave
-  static_assert(4 % NW == 0, "kTopWaves must divide 4");
-  int tgt[VPW];
+// Stage the 16 Y rows r0 .. r0 + 15 of a K-split block into sY[16][K + 4], all
+// threads of the block (rows >= n are zero).  VEC4: 16-byte loads
+// (ldy % 4 == 0, Y 16-byte aligned).
+template <bool VEC4, class Args>
+__device__ __forceinline__ void stage_y_tile(const Args& a, float* sY, int r0) {
+  const int K = a.K, P = K + 4;
+  constexpr int B = 8;
+  if (VEC4) {
+    const int kq = K / 4, tot = 16 * kq;
+    for (int q0 = threadIdx.x; q0 < tot; q0 += B * kTopThreads) {
+      float4 v[B];
 #pragma unroll
-  for (int vv = 0; vv < VPW; ++vv) {
-    const int r = r0 + 4 * g + w + vv * NW;
-    tgt[vv] = r < a.n ? (int)a.labels[r] : -1;
-  }
-  const float gl = GRAD ? (a.grad ? *a.grad : 1.0f) / (float)a.n : 0.f;
-  {  // the tile's 16 rows, all threads (rows >= n are zero)
-    constexpr int B = 8;
-    if (VEC4) {
-      const int kq = K / 4, tot = 16 * kq;
-      for (int q0 = threadIdx.x; q0 < tot; q0 += B * kTopThreads) {
-        float4 v[B];
-#pragma unroll
-        for (int u = 0; u < B; ++u) {
-          const int q = q0 + u * kTopThreads, rr = q / kq, r = r0 + rr;
-          v[u] = (q < tot && r < a.n) ? *reinterpret_cast<const float4*>(a.Y + (uint64_t)r * a.ldy + 4 * (q % kq))
-                                      : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < B; ++u) {
-          const int q = q0 + u * kTopThreads;
-          if (q < tot) *reinterpret_cast<float4*>(sY + (q / kq) * P + 4 * (q % kq)) = v[u];
-        }
+      for (int u = 0; u < B; ++u) {
+        const int q = q0 + u * kTopThreads, rr = q / kq, r = r0 + rr;
+        v[u] = (q < tot && r < a.n) ? *reinterpret_cast<const float4*>(a.Y + (uint64_t)r * a.ldy + 4 * (q % kq))
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
       }
-    } else {
-      const int tot = 16 * K;
-      for (int q0 = threadIdx.x; q0 < tot; q0 += B * kTopThreads) {
-        float v[B];
 #pragma unroll
-        for (int u = 0; u < B; ++u) {
-          const int q = q0 + u * kTopThreads, r = r0 + q / K;
-          v[u] = (q < tot && r < a.n) ? a.Y[(uint64_t)r * a.ldy + q % K] : 0.f;
-        }
+      for (int u = 0; u < B; ++u) {
+        const int q = q0 + u * kTopThreads;
+        if (q < tot) *reinterpret_cast<float4*>(sY + (q / kq) * P + 4 * (q % kq)) = v[u];
+      }
+    }
+  } else {
+    const int tot = 16 * K;
+    for (int q0 = threadIdx.x; q0 < tot; q0 += B * kTopThreads) {
+      float v[B];
 #pragma unroll
-        for (int u = 0; u < B; ++u) {
-          const int q = q0 + u * kTopThreads;
-          if (q < tot) sY[(q / K) * P + q % K] = v[u];
-        }
+      for (int u = 0; u < B; ++u) {
+        const int q = q0 + u * kTopThreads, r = r0 + q / K;
+        v[u] = (q < tot && r < a.n) ? a.Y[(uint64_t)r * a.ldy + q % K] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < B; ++u) {
+        const int q = q0 + u * kTopThreads;
+        if (q < tot) sY[(q / K) * P + q % K] = v[u];
       }
     }
   }
-  stage_w<CP>(a, sW);
-  __syncthreads();
+}
+
+// This wave's share of the logits: the partial chains of its k tiles
+// (kt = w, w + kTopWaves, ...) of Z = Y W, stored to zp[w][16][CP]; the caller
+// sums the waves' slabs in wave order after a barrier.
+template <int NCT>
+__device__ __forceinline__ void split_logits(int K, const float* sW, const float* sY, float* zp,
+                                             int w, int i, int g) {
+  constexpr int CP = 16 * NCT, NW = kTopWaves;
+  const int P = K + 4, nkt = K / 16;
   f32x4 z[NCT];
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct) z[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -352,6 +342,113 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
     for (int v = 0; v < 4; ++v) zp[(w * 16 + 4 * g + v) * CP + 16 * ct + i] = z[ct][v];
+}
+
+// dY [16 x K] = dZ W^T and this block's dW slab [K x CP] = Y^T dZ from the dZ
+// tile in LDS, each wave on its k tiles.
+template <int NCT, class Args>
+__device__ __forceinline__ void grad_products(const Args& a, const float* sW, const float* sY,
+                                              const float* dz, int r0, int w, int i, int g) {
+  constexpr int CP = 16 * NCT, NW = kTopWaves;
+  const int K = a.K, P = K + 4, nkt = K / 16;
+  // dY [16 x K] = dZ W^T on this wave's k tiles, two at a time
+  constexpr int KT = 2;
+  for (int j0 = w; j0 < nkt; j0 += KT * NW) {
+    f32x4 acc[KT];
+    int ktu[KT];
+#pragma unroll
+    for (int u = 0; u < KT; ++u) {
+      acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      ktu[u] = min(j0 + u * NW, nkt - 1);
+    }
+#pragma unroll
+    for (int c0 = 0; c0 < CP; c0 += 4) {
+      const float av = dz[i * CP + c0 + g];
+#pragma unroll
+      for (int u = 0; u < KT; ++u)
+        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, sW[(16 * ktu[u] + i) * CP + c0 + g], acc[u],
+                                                      0, 0, 0);
+    }
+#pragma unroll
+    for (int u = 0; u < KT; ++u) {
+      const int kt = j0 + u * NW;
+      if (kt >= nkt) break;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int r = r0 + 4 * g + v;
+        if (r < a.n) a.dY[(uint64_t)r * K + 16 * kt + i] = acc[u][v];
+      }
+    }
+  }
+  // dW slab of this block [K x CP] = Y^T dZ, rows of this wave's k tiles
+  const uint64_t nslab = gridDim.x, slab = blockIdx.x;
+  for (int j0 = w; j0 < nkt; j0 += KT * NW) {
+    f32x4 acc[KT][NCT];
+    int ktu[KT];
+#pragma unroll
+    for (int u = 0; u < KT; ++u) {
+      ktu[u] = min(j0 + u * NW, nkt - 1);
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) acc[u][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) {
+      float bv[NCT];
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) bv[ct] = dz[(4 * s4 + g) * CP + 16 * ct + i];
+#pragma unroll
+      for (int u = 0; u < KT; ++u) {
+        const float av = sY[(4 * s4 + g) * P + 16 * ktu[u] + i];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+          acc[u][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[ct], acc[u][ct], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < KT; ++u) {
+      const int kt = j0 + u * NW;
+      if (kt >= nkt) break;
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const uint64_t q = (uint64_t)(16 * kt + 4 * g + v) * NCT + ct;
+          a.part[(q * nslab + slab) * 16 + i] = acc[u][ct][v];
+        }
+    }
+  }
+}
+
+template <int NCT, bool LOSS, bool GRAD, bool VEC4>
+__global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
+  constexpr int CP = 16 * NCT, NW = kTopWaves;
+  extern __shared__ float smem[];
+  __shared__ float wl[NW];
+  __shared__ uint32_t wc[NW];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int K = a.K, P = K + 4;
+  float* sW = smem;                // [K][CP]
+  float* sY = sW + K * CP;         // [16][K + 4]
+  float* zp = sY + 16 * P;         // [NW][16][CP] partial logits
+  float* dz = zp + NW * 16 * CP;   // [16][CP]
+  const int r0 = blockIdx.x * 16;
+  // the rows' labels and the upstream gradient first: their global loads
+  // then overlap the staging instead of following the logits (a dependent
+  // memory latency of 4-6 us per block there, measured with phase timers)
+  constexpr int VPW = 4 / NW;  // rows 4 g + v per lane group finished by this wave
+  static_assert(4 % NW == 0, "kTopWaves must divide 4");
+  int tgt[VPW];
+#pragma unroll
+  for (int vv = 0; vv < VPW; ++vv) {
+    const int r = r0 + 4 * g + w + vv * NW;
+    tgt[vv] = r < a.n ? (int)a.labels[r] : -1;
+  }
+  const float gl = GRAD ? (a.grad ? *a.grad : 1.0f) / (float)a.n : 0.f;
+  stage_y_tile<VEC4>(a, sY, r0);
+  stage_w<CP>(a, sW);
+  __syncthreads();
+  split_logits<NCT>(K, sW, sY, zp, w, i, g);
   __syncthreads();
   // each wave finishes the rows 4 g + v of its own v (v = w, w + NW, ...): the
   // logits' sum over the waves' k-splits, log_softmax twice (log_softmax2's
@@ -452,72 +549,7 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   }
   if (GRAD) {
     __syncthreads();
-    // dY [16 x K] = dZ W^T on this wave's k tiles, two at a time
-    constexpr int KT = 2;
-    for (int j0 = w; j0 < nkt; j0 += KT * NW) {
-      f32x4 acc[KT];
-      int ktu[KT];
-#pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        ktu[u] = min(j0 + u * NW, nkt - 1);
-      }
-#pragma unroll
-      for (int c0 = 0; c0 < CP; c0 += 4) {
-        const float av = dz[i * CP + c0 + g];
-#pragma unroll
-        for (int u = 0; u < KT; ++u)
-          acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, sW[(16 * ktu[u] + i) * CP + c0 + g], acc[u],
-                                                        0, 0, 0);
-      }
-#pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        const int kt = j0 + u * NW;
-        if (kt >= nkt) break;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int r = r0 + 4 * g + v;
-          if (r < a.n) a.dY[(uint64_t)r * K + 16 * kt + i] = acc[u][v];
-        }
-      }
-    }
-    // dW slab of this block [K x CP] = Y^T dZ, rows of this wave's k tiles
-    const uint64_t nslab = gridDim.x, slab = blockIdx.x;
-    for (int j0 = w; j0 < nkt; j0 += KT * NW) {
-      f32x4 acc[KT][NCT];
-      int ktu[KT];
-#pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        ktu[u] = min(j0 + u * NW, nkt - 1);
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) acc[u][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) {
-        float bv[NCT];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) bv[ct] = dz[(4 * s4 + g) * CP + 16 * ct + i];
-#pragma unroll
-        for (int u = 0; u < KT; ++u) {
-          const float av = sY[(4 * s4 + g) * P + 16 * ktu[u] + i];
-#pragma unroll
-          for (int ct = 0; ct < NCT; ++ct)
-            acc[u][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[ct], acc[u][ct], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        const int kt = j0 + u * NW;
-        if (kt >= nkt) break;
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const uint64_t q = (uint64_t)(16 * kt + 4 * g + v) * NCT + ct;
-            a.part[(q * nslab + slab) * 16 + i] = acc[u][ct][v];
-          }
-      }
-    }
+    grad_products<NCT>(a, sW, sY, dz, r0, w, i, g);
   }
   if (LOSS) {
     __syncthreads();
@@ -534,14 +566,134 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   }
 }
 
+// ---- multi-label output layer: Z = Y W + mean sigmoid-BCE --------------------
+// The same block shape as k_top_xent_ks (16 rows, the waves split K, W in LDS,
+// the three products on v_mfma_f32_16x16x4_f32) with an element-wise middle:
+//   loss = mean over the n C entries of max(z, 0) - z t + log1p(exp(-|z|))
+//   dZ   = (sigmoid(z) - t) / (n C)
+// and the micro-F1 counters of the prediction z > 0: true positives, false
+// positives, false negatives.  Targets are bits: label c of vertex u is bit
+// c & 31 of bits[u * wpr + (c >> 5)]; bits at positions >= C are ignored.  Row
+// r reads vertex index[r] (the batch's seeds), or r itself without an index.
+struct BceArgs {
+  const float* Y;
+  uint64_t ldy;
+  const float* W;
+  const uint32_t* bits;   // [V x wpr] packed targets
+  const uint32_t* index;  // [n] vertex of each row, or nullptr
+  uint32_t wpr;
+  int n, K, C;
+  float* lpart;     // [blocks] loss partials
+  float* part;      // GRAD: dW partials [K][Cp/16][blocks][16]
+  float* dY;        // GRAD: [n x K]
+  uint32_t* cpart;  // [blocks][3] tp, fp, fn partials, or nullptr
+};
+
+// the K-split tiles plus the waves' loss and counter terms (no static LDS:
+// the whole 160 KB is the dynamic segment's to use)
+static inline size_t top_bce_lds(int K, int Cp) {
+  return top_ks_lds(K, Cp) + (size_t)4 * kTopWaves * sizeof(float);
+}
+
+template <int NCT, bool GRAD, bool VEC4>
+__global__ __launch_bounds__(kTopThreads) void k_top_bce_ks(BceArgs a) {
+  constexpr int CP = 16 * NCT, NW = kTopWaves, NWD = (NCT + 1) / 2;  // label words per row
+  extern __shared__ float smem[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int K = a.K, P = K + 4;
+  float* sW = smem;                // [K][CP]
+  float* sY = sW + K * CP;         // [16][K + 4]
+  float* zp = sY + 16 * P;         // [NW][16][CP] partial logits
+  float* dz = zp + NW * 16 * CP;   // [16][CP]
+  float* wl = dz + 16 * CP;        // [NW] loss terms of the waves
+  uint32_t* wc = reinterpret_cast<uint32_t*>(wl + NW);  // [NW][3]
+  const int r0 = blockIdx.x * 16;
+  constexpr int VPW = 4 / NW;  // rows 4 g + v per lane group finished by this wave
+  static_assert(4 % NW == 0, "kTopWaves must divide 4");
+  // the rows' label words first (index, then the words: two dependent loads
+  // that overlap the staging)
+  uint32_t tw[VPW][NWD];
+#pragma unroll
+  for (int vv = 0; vv < VPW; ++vv) {
+    const int r = r0 + 4 * g + w + vv * NW;
+    const uint64_t u = r < a.n ? (a.index ? (uint64_t)a.index[r] : (uint64_t)r) : 0;
+#pragma unroll
+    for (int j = 0; j < NWD; ++j)
+      tw[vv][j] = (r < a.n && 32 * j < a.C) ? a.bits[u * a.wpr + j] : 0u;
+  }
+  const float gl = 1.0f / ((float)a.n * (float)a.C);
+  stage_y_tile<VEC4>(a, sY, r0);
+  stage_w<CP>(a, sW);
+  __syncthreads();
+  split_logits<NCT>(K, sW, sY, zp, w, i, g);
+  __syncthreads();
+  // each wave finishes the rows 4 g + v of its own v: the logits' sum over the
+  // waves' k-splits in wave order, then the element-wise terms
+  float lw = 0.f;
+  uint32_t tp = 0, fp = 0, fn = 0;
+#pragma unroll
+  for (int vv = 0; vv < VPW; ++vv) {
+    const int v = w + vv * NW, r = r0 + 4 * g + v;
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) {
+      const int c = 16 * ct + i;
+      float z = zp[(4 * g + v) * CP + c];
+#pragma unroll
+      for (int q = 1; q < NW; ++q) z += zp[(q * 16 + 4 * g + v) * CP + c];
+      const bool on = c < a.C && r < a.n;
+      const bool t = (tw[vv][ct >> 1] >> (c & 31)) & 1u;
+      const float e = expf(-fabsf(z));  // in (0, 1]: nothing overflows
+      if (on) {
+        lw += (fmaxf(z, 0.f) - (t ? z : 0.f)) + log1pf(e);
+        const bool pos = z > 0.f;
+        tp += (pos && t) ? 1u : 0u;
+        fp += (pos && !t) ? 1u : 0u;
+        fn += (!pos && t) ? 1u : 0u;
+      }
+      if (GRAD) {
+        const float sg = (z >= 0.f ? 1.0f : e) / (1.0f + e);  // sigmoid(z)
+        dz[(4 * g + v) * CP + c] = on ? (sg - (t ? 1.0f : 0.f)) * gl : 0.f;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lw += __shfl_down(lw, o, kWave);
+    tp += __shfl_down(tp, o, kWave);
+    fp += __shfl_down(fp, o, kWave);
+    fn += __shfl_down(fn, o, kWave);
+  }
+  if (lane == 0) {
+    wl[w] = lw;
+    wc[3 * w] = tp;
+    wc[3 * w + 1] = fp;
+    wc[3 * w + 2] = fn;
+  }
+  __syncthreads();
+  if (GRAD) grad_products<NCT>(a, sW, sY, dz, r0, w, i, g);
+  if (threadIdx.x == 0) {  // the block's terms in wave order
+    float l = 0.f;
+    uint32_t c[3] = {0, 0, 0};
+    for (int q = 0; q < NW; ++q) {
+      l += wl[q];
+      for (int k = 0; k < 3; ++k) c[k] += wc[3 * q + k];
+    }
+    a.lpart[blockIdx.x] = l;
+    if (a.cpart)
+      for (int k = 0; k < 3; ++k) a.cpart[3 * (uint64_t)blockIdx.x + k] = c[k];
+  }
+}
+
 // Blocks [0, K*NCT): dW chunk (k, ct) = sum over the wave slabs — thread
 // (sg, i) sums slabs sg, sg+16, ... in order (40 loads in flight), then a fixed
 // pairwise tree over the 16 slab groups.  Block K*NCT (or 0 without GRAD):
-// loss = (sum of block partials, fixed tree) / n.
-template <int NCT>
+// loss = (sum of block partials, fixed tree) / denom, and the NCNT counters
+// of every block (cpart [blocks][NCNT]) added to correct[0 .. NCNT).
+template <int NCT, int NCNT>
 __global__ __launch_bounds__(256) void k_top_finish(const float* __restrict__ part, int nslab,
                                                     const float* __restrict__ lpart, int nblk,
-                                                    int n, int K, int C, int nchunks,
+                                                    float denom, int C, int nchunks,
                                                     float* __restrict__ dW, float* loss,
                                                     const uint32_t* __restrict__ cpart,
                                                     uint32_t* correct) {
@@ -572,29 +724,34 @@ __global__ __launch_bounds__(256) void k_top_finish(const float* __restrict__ pa
     const int k = q / NCT, c = 16 * (q % NCT) + t;
     if (t < 16 && c < C) dW[(uint64_t)k * C + c] = red[t];
   } else {
-    uint32_t c = 0;
+    uint32_t c[NCNT] = {};
     for (int b = t; b < nblk; b += 256) {
       acc += lpart[b];
-      if (cpart) c += cpart[b];
+      if (cpart)
+#pragma unroll
+        for (int k = 0; k < NCNT; ++k) c[k] += cpart[(uint64_t)b * NCNT + k];
     }
     red[t] = acc;
-    __shared__ uint32_t cred[256];
-    cred[t] = c;
+    __shared__ uint32_t cred[NCNT][256];
+#pragma unroll
+    for (int k = 0; k < NCNT; ++k) cred[k][t] = c[k];
     __syncthreads();
 #pragma unroll
     for (int h = 128; h >= 1; h >>= 1) {
       if (t < h) {
         red[t] += red[t + h];
-        cred[t] += cred[t + h];
+#pragma unroll
+        for (int k = 0; k < NCNT; ++k) cred[k][t] += cred[k][t + h];
       }
       __syncthreads();
     }
     if (t == 0) {
-      *loss = red[0] / (float)n;
-      if (correct) *correct += cred[0];  // accumulates over batches
+      *loss = red[0] / denom;
+      if (correct)  // accumulates over batches
+#pragma unroll
+        for (int k = 0; k < NCNT; ++k) correct[k] += cred[k][0];
     }
   }
-  (void)K;
 }
 
 template <int NCT, bool LOSS, bool GRAD>
@@ -624,19 +781,55 @@ static int launch_top_any(hipStream_t st, int nblk, int Cp, const TopArgs& a) {
   }
 }
 
+template <int NCT, bool GRAD>
+static int launch_bce(hipStream_t st, int nblk, const BceArgs& a) {
+  const size_t lds = top_bce_lds(a.K, 16 * NCT);
+  const bool v4 = a.ldy % 4 == 0 && (uintptr_t)a.Y % 16 == 0;
+  const void* f = v4 ? reinterpret_cast<const void*>(&k_top_bce_ks<NCT, GRAD, true>)
+                     : reinterpret_cast<const void*>(&k_top_bce_ks<NCT, GRAD, false>);
+  NTS_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (v4)
+    hipLaunchKernelGGL((k_top_bce_ks<NCT, GRAD, true>), dim3(nblk), dim3(kTopThreads), lds, st, a);
+  else
+    hipLaunchKernelGGL((k_top_bce_ks<NCT, GRAD, false>), dim3(nblk), dim3(kTopThreads), lds, st, a);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
+template <bool GRAD>
+static int launch_bce_any(hipStream_t st, int nblk, int Cp, const BceArgs& a) {
+  switch (Cp / 16) {
+    case 1: return launch_bce<1, GRAD>(st, nblk, a);
+    case 2: return launch_bce<2, GRAD>(st, nblk, a);
+    case 3: return launch_bce<3, GRAD>(st, nblk, a);
+    case 4: return launch_bce<4, GRAD>(st, nblk, a);
+    case 5: return launch_bce<5, GRAD>(st, nblk, a);
+    case 6: return launch_bce<6, GRAD>(st, nblk, a);
+    case 7: return launch_bce<7, GRAD>(st, nblk, a);
+    default: return launch_bce<8, GRAD>(st, nblk, a);
+  }
+}
+
+// NCNT: counters per block (1: the xent rows whose argmax is the label; 3: the
+// BCE tp / fp / fn); denom: what the summed loss partials are divided by
+template <int NCNT>
 static int launch_finish(hipStream_t st, int Cp, const float* part, int nslab, const float* lpart,
-                         int nblk, int n, int K, int C, bool grad, bool loss_on, float* dW,
+                         int nblk, float denom, int K, int C, bool grad, bool loss_on, float* dW,
                          float* loss, const uint32_t* cpart, uint32_t* correct) {
   const int nchunks = grad ? K * (Cp / 16) : 0;
   const dim3 grid(nchunks + (loss_on ? 1 : 0));
-#define NTS_F(NCT)                                                                             \
-  hipLaunchKernelGGL(k_top_finish<NCT>, grid, dim3(256), 0, st, part, nslab, lpart, nblk, n, K, \
-                     C, nchunks, dW, loss, cpart, correct)
+#define NTS_F(NCT)                                                                            \
+  hipLaunchKernelGGL((k_top_finish<NCT, NCNT>), grid, dim3(256), 0, st, part, nslab, lpart, nblk, \
+                     denom, C, nchunks, dW, loss, cpart, correct)
   switch (Cp / 16) {
     case 1: NTS_F(1); break;
     case 2: NTS_F(2); break;
     case 3: NTS_F(3); break;
-    default: NTS_F(4); break;
+    case 4: NTS_F(4); break;
+    case 5: NTS_F(5); break;
+    case 6: NTS_F(6); break;
+    case 7: NTS_F(7); break;
+    default: NTS_F(8); break;
   }
 #undef NTS_F
   NTS_LAUNCH_CHECK();
@@ -675,8 +868,8 @@ static int top_run(nts_hip_ctx* ctx, bool loss_on, bool grad_on, const float* Y,
   if (loss_on && grad_on) NTS_RET((launch_top_any<true, true>(st, nblk, Cp, a)));
   else if (loss_on) NTS_RET((launch_top_any<true, false>(st, nblk, Cp, a)));
   else NTS_RET((launch_top_any<false, true>(st, nblk, Cp, a)));
-  return launch_finish(st, Cp, a.part, nslab, a.lpart, nblk, n, K, C, grad_on, loss_on, dW, loss,
-                       cpart, cpart ? correct : nullptr);
+  return launch_finish<1>(st, Cp, a.part, nslab, a.lpart, nblk, (float)n, K, C, grad_on, loss_on,
+                          dW, loss, cpart, cpart ? correct : nullptr);
 }
 
 int nts_hip_linear_xent_fwd(nts_hip_ctx* ctx, const float* Y, uint64_t ldy, int n, int K,
@@ -700,6 +893,54 @@ int nts_hip_linear_xent_train(nts_hip_ctx* ctx, const float* Y, uint64_t ldy, in
                               float* dY, float* dW, uint32_t* correct) {
   NTS_CHECK_ARG(ctx && Y && W && labels && loss && dY && dW, "NULL argument");
   return top_run(ctx, true, true, Y, ldy, n, K, W, C, labels, nullptr, loss, dY, dW, correct);
+}
+
+// ---- multi-label output layer -------------------------------------------------
+static int bce_check(nts_hip_ctx* ctx, int n, int K, int C, uint64_t ldy, uint32_t wpr) {
+  NTS_CHECK_ARG(n > 0 && K > 0 && C > 0 && ldy >= (uint64_t)K, "shape");
+  NTS_CHECK_ARG(C <= 128, "label count above 128 is not supported by the fused BCE loss");
+  NTS_CHECK_ARG(wpr >= (uint32_t)(C + 31) / 32, "label_bits rows need ceil(C / 32) words");
+  NTS_CHECK_ARG(K % 16 == 0, "the fused BCE loss needs K % 16 == 0");
+  NTS_CHECK_ARG(top_bce_lds(K, (C + 15) / 16 * 16) <= 160 * 1024,
+                "K x C too large for the fused BCE loss");
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  return NTS_OK;
+}
+
+// scratch: [loss partials, 64-float aligned][3 counter partials per block][dW partial chunks]
+static int bce_run(nts_hip_ctx* ctx, bool grad_on, const float* Y, uint64_t ldy, int n, int K,
+                   const float* W, int C, const uint32_t* label_bits, uint32_t wpr,
+                   const uint32_t* index, float* loss, float* dY, float* dW, uint32_t* counts) {
+  NTS_RET(bce_check(ctx, n, K, C, ldy, wpr));
+  const int Cp = (C + 15) / 16 * 16;
+  const int nblk = (n + 15) / 16, nslab = nblk;  // one dW slab per 16-row block
+  const size_t lp = ((size_t)nblk + 63) / 64 * 64;
+  NTS_RET(ensure_scratch(
+      ctx, (4 * lp + (grad_on ? (size_t)nslab * K * Cp : 0)) * sizeof(float)));
+  float* base = (float*)ctx->scratch;
+  uint32_t* cpart = counts ? reinterpret_cast<uint32_t*>(base + lp) : nullptr;
+  BceArgs a{Y, ldy, W, label_bits, index, wpr, n, K, C, base, base + 4 * lp, dY, cpart};
+  hipStream_t st = ctx->stream;
+  if (grad_on) NTS_RET((launch_bce_any<true>(st, nblk, Cp, a)));
+  else NTS_RET((launch_bce_any<false>(st, nblk, Cp, a)));
+  return launch_finish<3>(st, Cp, a.part, nslab, a.lpart, nblk, (float)n * (float)C, K, C, grad_on,
+                          true, dW, loss, cpart, counts);
+}
+
+int nts_hip_linear_bce_fwd(nts_hip_ctx* ctx, const float* Y, uint64_t ldy, int n, int K,
+                           const float* W, int C, const uint32_t* label_bits, uint32_t wpr,
+                           const uint32_t* index, float* loss, uint32_t* counts) {
+  NTS_CHECK_ARG(ctx && Y && W && label_bits && loss, "NULL argument");
+  return bce_run(ctx, false, Y, ldy, n, K, W, C, label_bits, wpr, index, loss, nullptr, nullptr,
+                 counts);
+}
+
+int nts_hip_linear_bce_train(nts_hip_ctx* ctx, const float* Y, uint64_t ldy, int n, int K,
+                             const float* W, int C, const uint32_t* label_bits, uint32_t wpr,
+                             const uint32_t* index, float* loss, float* dY, float* dW,
+                             uint32_t* counts) {
+  NTS_CHECK_ARG(ctx && Y && W && label_bits && loss && dY && dW, "NULL argument");
+  return bce_run(ctx, true, Y, ldy, n, K, W, C, label_bits, wpr, index, loss, dY, dW, counts);
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
   core/graph.hpp:1139-1140), |E| = bytes / 8.
 * Feature file: text, one line per vertex `id f_1 ... f_F`
   (GNNDatum::readFeature_Label_Mask, core/ntsDataloador.hpp:999-1064).
+* Multi-label label file (MULTI_LABEL:1; what convert_ogb writes for a
+  multi-column node-label.csv): `id b_0 ... b_{C-1}` with 0/1 entries.
 * Label file: `id label`; mask file: `id train|val|eval|test`; unlisted
   vertices keep the memset(…,1) pattern (core/ntsDataloador.hpp:191) = 0x01010101.
 * FEATURE_FILE:random (core/ntsDataloador.hpp:835-861): all-ones features,
@@ -169,6 +171,43 @@ def read_feature_label_mask_numpy(feature_path, label_path, mask_path, n_vertice
     return feats, labels, masks
 
 
+def read_multilabel_file(label_path, n_vertices: int, n_labels: int) -> np.ndarray:
+    """Multi-label label file, one line per listed vertex: `id b_0 ... b_{C-1}`
+    with every b 0 or 1 (ids in any order).  Returns uint8 [V, C]; unlisted
+    vertices are all-zero.  A line with another column count, a bad id or an
+    entry that is not 0/1 raises ValueError naming the line."""
+    out = np.zeros((n_vertices, n_labels), np.uint8)
+    for no, line in enumerate(_text(label_path).splitlines(), 1):
+        tok = line.split()
+        if not tok:
+            continue
+        if len(tok) != n_labels + 1:
+            raise ValueError(f"{label_path}:{no}: {len(tok) - 1} label columns, expected {n_labels}")
+        try:
+            v = int(tok[0])
+        except ValueError:
+            raise ValueError(f"{label_path}:{no}: bad vertex id {tok[0]!r}") from None
+        if not 0 <= v < n_vertices:
+            raise ValueError(f"{label_path}:{no}: vertex id {v} outside [0, {n_vertices})")
+        for c, t in enumerate(tok[1:]):
+            if t != "0" and t != "1":
+                raise ValueError(f"{label_path}:{no}: label {c} is {t!r}, expected 0 or 1")
+        out[v] = np.frombuffer("".join(tok[1:]).encode(), np.uint8) - ord("0")
+    return out
+
+
+def pack_label_bits(labels: np.ndarray) -> np.ndarray:
+    """[V, C] 0/1 labels -> uint32 [V, ceil(C / 32)], the table the fused BCE
+    loss reads (nts_hip_linear_bce_*): label c is bit c & 31 of word c >> 5."""
+    lab = np.asarray(labels)
+    V, C = lab.shape
+    wpr = (C + 31) // 32
+    pad = np.zeros((V, wpr * 32), np.uint64)
+    pad[:, :C] = lab != 0
+    w = (pad.reshape(V, wpr, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2, dtype=np.uint64)
+    return w.astype(np.uint32)
+
+
 # ---------------------------------------------------------------------------
 # PRE_SAMPLE_FILE (core/ntsBaseOp.hpp:427-497): the hot vertices of every
 # super-batch found by preSample, as
@@ -249,6 +288,9 @@ class InputInfo:
     # FULL_INFERENCE (this build's key, no reference counterpart): after the last
     # epoch, score the final weights over the whole graph with full neighbourhoods
     full_inference: int = 0
+    # MULTI_LABEL (this build's key): the label file is `id b_0 ... b_{C-1}`
+    # (C = the last layer's width); train with the sigmoid BCE loss, report micro-F1
+    multi_label: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -274,6 +316,7 @@ class InputInfo:
             "UP_DEGREE": ("up_degree", lambda s: bool(int(s))), "GPU_NUM": ("gpu_num", int),
             "PRE_SAMPLE_FILE": ("pre_sample_file", str),
             "FULL_INFERENCE": ("full_inference", int),
+            "MULTI_LABEL": ("multi_label", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

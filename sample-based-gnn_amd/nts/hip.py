@@ -382,6 +382,24 @@ class HipContext:
                                                  W.shape[1], ptr(labels), ptr(loss), ptr(dY),
                                                  ptr(dW), ptr(correct)))
 
+    def linear_bce_fwd(self, Y, W, label_bits, loss, index=None, counts=None):
+        """loss = binary_cross_entropy_with_logits(Y @ W, T) (mean), fused.  T is
+        bit-packed: label_bits int32 [V, wpr], label c of vertex u = bit c & 31
+        of word c >> 5; row r reads vertex index[r] (int32 [n]) or r.  counts
+        (int32 [3] on the device) += tp, fp, fn of the prediction z > 0."""
+        n, K = Y.shape
+        check(self.lib.nts_hip_linear_bce_fwd(self.h, ptr(Y), Y.stride(0), n, K, ptr(W), W.shape[1],
+                                              ptr(label_bits), label_bits.shape[1], ptr(index),
+                                              ptr(loss), ptr(counts)))
+
+    def linear_bce_train(self, Y, W, label_bits, loss, dY, dW, index=None, counts=None):
+        """The same loss and counts, and the gradients dY, dW for d loss = 1."""
+        n, K = Y.shape
+        check(self.lib.nts_hip_linear_bce_train(self.h, ptr(Y), Y.stride(0), n, K, ptr(W),
+                                                W.shape[1], ptr(label_bits), label_bits.shape[1],
+                                                ptr(index), ptr(loss), ptr(dY), ptr(dW),
+                                                ptr(counts)))
+
     def adam(self, w, g, m, v, alpha, beta1, beta2, eps, wd, beta1_t, beta2_t, bias_correction):
         check(self.lib.nts_hip_adam(self.h, ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), alpha,
                                     beta1, beta2, eps, wd, beta1_t, beta2_t, int(bias_correction)))

@@ -132,6 +132,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("work_offset", [](PySampler& p) { return p.s->work_offset; })
       .def_property_readonly("sampled_edges", [](PySampler& p) { return p.s->sampled_edges; });
 
+  // the driver's predicates and label packing of the multi-label mode
+  m.def("hip_linear_bce_supported", &hip_linear_bce_supported, py::arg("K"), py::arg("C"));
+  m.def("pack_label_bits", &pack_label_bits, py::arg("labels"));
   m.def(
       "sampler_throughput",
       [](std::shared_ptr<FullyRepGraph> g, const torch::Tensor& seeds, int batch,
@@ -224,6 +227,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("early_aggregate", &GCNConfig::early_aggregate)
       .def_readwrite("sampler_priority", &GCNConfig::sampler_priority)
       .def_readwrite("fuse_loss", &GCNConfig::fuse_loss)
+      .def_readwrite("multi_label", &GCNConfig::multi_label)
       .def_readwrite("sampler_cus", &GCNConfig::sampler_cus)
       .def_readwrite("sampler_gate", &GCNConfig::sampler_gate)
       .def_readwrite("pad_features", &GCNConfig::pad_features)
@@ -257,6 +261,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("presample", &GCN_SAMPLE_ALLGPU_impl::presample)
       .def("set_presample", &GCN_SAMPLE_ALLGPU_impl::set_presample)
       .def("reset_correct", &GCN_SAMPLE_ALLGPU_impl::reset_correct)
+      .def("f1_counts",
+           [](GCN_SAMPLE_ALLGPU_impl& d) {
+             auto c = d.f1_counts();
+             return py::make_tuple(c[0], c[1], c[2]);
+           })
       .def("evaluate",
            [](GCN_SAMPLE_ALLGPU_impl& d, const torch::Tensor& nids) {
              auto ids = to_ids(nids);

@@ -1076,6 +1076,56 @@ struct HipLinearXentFn : public torch::autograd::Function<HipLinearXentFn> {
     return {ctx->needs_input_grad(0) ? dY : NtsVar(), dW, NtsVar(), NtsVar(), NtsVar(), NtsVar()};
   }
 };
+// Multi-label output layer + mean sigmoid-BCE in fused kernels (nts_hip.h).
+// Under grad mode the forward runs the training kernel (loss, dY and dW for
+// d loss = 1); the backward returns them, scaled when the upstream gradient
+// is not the unit seed of self_backward.
+struct HipLinearBceFn : public torch::autograd::Function<HipLinearBceFn> {
+  static NtsVar forward(AutogradContext* ctx, NtsVar y, NtsVar W, NtsVar bits, int64_t index_ptr,
+                        int64_t cs_ptr, bool train, int64_t counts_ptr) {
+    auto* counts = reinterpret_cast<uint32_t*>(counts_ptr);
+    auto* index = reinterpret_cast<const uint32_t*>(index_ptr);
+    auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
+    NtsVar yc = row_major(y), Wc = W.contiguous();
+    const int64_t n = yc.size(0), K = yc.size(1), C = Wc.size(1);
+    TORCH_CHECK(Wc.size(0) == K && bits.dim() == 2 && bits.is_contiguous() &&
+                    bits.scalar_type() == torch::kInt32 && bits.size(1) == (C + 31) / 32,
+                "hip_linear_bce: shape mismatch");
+    const auto* lb = reinterpret_cast<const uint32_t*>(bits.data_ptr<int32_t>());
+    NtsVar loss = torch::empty({}, yc.options());
+    if (train) {
+      NtsVar dY = torch::empty({n, K}, yc.options());
+      NtsVar dW = torch::empty({K, C}, Wc.options());
+      hip_check(nts_hip_linear_bce_train(cs->ctx(), yc.data_ptr<float>(), (uint64_t)yc.stride(0),
+                                         (int)n, (int)K, Wc.data_ptr<float>(), (int)C, lb,
+                                         (uint32_t)bits.size(1), index, loss.data_ptr<float>(),
+                                         dY.data_ptr<float>(), dW.data_ptr<float>(), counts),
+                "nts_hip_linear_bce_train");
+      ctx->saved_data["dY"] = dY;
+      ctx->saved_data["dW"] = dW;
+    } else {
+      hip_check(nts_hip_linear_bce_fwd(cs->ctx(), yc.data_ptr<float>(), (uint64_t)yc.stride(0),
+                                       (int)n, (int)K, Wc.data_ptr<float>(), (int)C, lb,
+                                       (uint32_t)bits.size(1), index, loss.data_ptr<float>(),
+                                       counts),
+                "nts_hip_linear_bce_fwd");
+    }
+    return loss;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(ctx->saved_data.count("dY"), "hip_linear_bce: backward without a training forward");
+    NtsVar g = grads[0];
+    NtsVar dY = ctx->saved_data["dY"].toTensor(), dW = ctx->saved_data["dW"].toTensor();
+    if (g.data_ptr() != unit_scalar(g.device()).data_ptr()) {  // d loss != the unit seed
+      dY = dY * g;
+      dW = dW * g;
+    }
+    ctx->saved_data.erase("dY");
+    ctx->saved_data.erase("dW");
+    return {ctx->needs_input_grad(0) ? dY : NtsVar(), dW, NtsVar(), NtsVar(), NtsVar(), NtsVar(),
+            NtsVar()};
+  }
+};
 }  // namespace
 
 NtsVar hip_linear_act(const NtsVar& x, const NtsVar& W, double p, uint64_t seed, uint64_t offset,
@@ -1300,6 +1350,51 @@ bool hip_linear_xent_supported(int64_t K, int64_t C) {
   const int64_t Cp = (C + 15) / 16 * 16;
   return K >= 16 && K % 16 == 0 && C >= 1 && C <= 64 &&
          (K * Cp + 64 * (K + 4) + 64 * Cp) * 4 <= 160 * 1024;
+}
+
+bool hip_linear_bce_supported(int64_t K, int64_t C) {
+  // mirrors the argument checks of nts_hip_linear_bce_fwd/train (C <= 128,
+  // K % 16 == 0; W, 16 Y rows, 5 x 16 logit rows and 16 words in LDS)
+  const int64_t Cp = (C + 15) / 16 * 16;
+  return K >= 16 && K % 16 == 0 && C >= 1 && C <= 128 &&
+         (K * Cp + 16 * (K + 4) + 5 * 16 * Cp + 16) * 4 <= 160 * 1024;
+}
+
+NtsVar hip_linear_bce(const NtsVar& y, const NtsVar& W, const NtsVar& label_bits,
+                      const VertexId* index, NtsStream* cs, uint32_t* counts) {
+  const bool train = torch::GradMode::is_enabled() && (y.requires_grad() || W.requires_grad());
+  return HipLinearBceFn::apply(y, W, label_bits, reinterpret_cast<int64_t>(index),
+                               reinterpret_cast<int64_t>(cs), train,
+                               reinterpret_cast<int64_t>(counts));
+}
+
+NtsVar pack_label_bits(const NtsVar& labels) {
+  TORCH_CHECK(labels.dim() == 2 && labels.size(1) >= 1, "multi-label targets must be [V, C]");
+  const auto dt = labels.scalar_type();
+  TORCH_CHECK(dt == torch::kUInt8 || dt == torch::kBool || dt == torch::kInt64,
+              "multi-label targets must be uint8, bool or int64");
+  const int64_t V = labels.size(0), C = labels.size(1), wpr = (C + 31) / 32;
+  NtsVar out = torch::empty({V, wpr}, labels.options().dtype(torch::kInt32));
+  NtsVar weight = torch::ones({1}, labels.options().dtype(torch::kInt64))
+                      .bitwise_left_shift(torch::arange(32, labels.options().dtype(torch::kInt64)));
+  const int64_t chunk = 1 << 16;  // rows per pass: bounds the int64 temporaries
+  for (int64_t r = 0; r < V; r += chunk) {
+    const int64_t m = std::min(chunk, V - r);
+    NtsVar x = labels.narrow(0, r, m).to(torch::kInt64);
+    TORCH_CHECK(!x.lt(0).logical_or(x.gt(1)).any().item<bool>(),
+                "multi-label targets must be 0 or 1");
+    x = torch::constant_pad_nd(x, {0, wpr * 32 - C}).view({m, wpr, 32});
+    NtsVar wd = (x * weight).sum(2);  // in [0, 2^32): wrap bit 31 into int32
+    wd = wd - wd.bitwise_right_shift(31).bitwise_left_shift(32);
+    out.narrow(0, r, m).copy_(wd);
+  }
+  return out;
+}
+
+NtsVar unpack_label_bits(const NtsVar& words, int64_t C) {
+  NtsVar sh = torch::arange(32, words.options().dtype(torch::kInt64));
+  NtsVar b = words.to(torch::kInt64).unsqueeze(2).bitwise_right_shift(sh).bitwise_and(1);
+  return b.view({words.size(0), words.size(1) * 32}).narrow(1, 0, C).to(torch::kFloat32);
 }
 
 NtsVar hip_linear_xent(const NtsVar& y, const NtsVar& W, const NtsVar& target, NtsStream* cs,

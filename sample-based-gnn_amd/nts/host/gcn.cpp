@@ -31,6 +31,17 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   TORCH_CHECK(cfg.fanout.size() == cfg.layer_size.size() - 1, "fanout per layer");
   TORCH_CHECK(F.is_cuda() && F.dtype() == torch::kFloat32 && F.size(1) == cfg.layer_size[0],
               "feature table must be fp32 [V, layer_size[0]] on the GPU");
+  if (cfg.multi_label) {
+    TORCH_CHECK(!cfg.gat, "multi_label is not supported with GAT layers (GCN / GraphSAGE only)");
+    TORCH_CHECK(L_GT.dim() == 2, "multi_label needs a 2-D label tensor [V, C] of 0/1, got ",
+                L_GT.dim(), "-D");
+    TORCH_CHECK(L_GT.is_cuda() && L_GT.size(0) == (int64_t)graph->global_vertices &&
+                    L_GT.size(1) == cfg.layer_size.back(),
+                "multi_label: labels must be [V, layer_size.back()] on the GPU");
+  } else {
+    TORCH_CHECK(L_GT.dim() == 1, "labels must be int64 [V] (a [V, C] 0/1 label tensor needs "
+                                 "multi_label)");
+  }
   if (cfg.sample_gpu) {
     TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
     TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
@@ -178,6 +189,11 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                                f32_opts(graph->device));
   }
   correct_ = torch::zeros({1}, u32_opts(graph->device));
+  if (cfg.multi_label) {  // the labels as bits, packed once; the [V, C] tensor is released
+    label_bits_ = pack_label_bits(L_GT);
+    L_GT = NtsVar();
+    f1_ = torch::zeros({3}, u32_opts(graph->device));
+  }
   init_nn();
   defer_ = comm && (cfg.overlap_allreduce == 1 || (cfg.overlap_allreduce < 0 && comm->nranks > 1));
   if (defer_) {
@@ -240,8 +256,9 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
   sampler->issue_gpu_sample(cfg.batch_size, slot, st,
                             cfg.gat ? WeightType::None : cfg.weight_type);
   sampler->omit_map = nullptr;
-  {  // load_label_gpu for this batch, on the sampling stream next to its
-     // subgraph (off the training stream; ordered by ready_[slot] below)
+  if (!cfg.multi_label) {  // load_label_gpu for this batch, on the sampling stream next to its
+     // subgraph (off the training stream; ordered by ready_[slot] below);
+     // multi_label: the loss reads the packed table by the seeds' ids itself
     SampledSubgraph* q = sampler->ssgs[slot];
     const int64_t n = q->pending_batch;
     NtsVar& t = lbl_[slot];
@@ -330,7 +347,8 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::weights() {
 // dropout(relu(XW)), the last layer log_softmax(XW).
 NtsVar GCN_SAMPLE_ALLGPU_impl::vertexForward(int l, NtsVar& a) {
   const int L = (int)P.size();
-  if (l == L - 1) return P[l]->forward(a).log_softmax(1);
+  if (l == L - 1)  // multi_label: raw logits (the sigmoid is the loss's)
+    return cfg.multi_label ? P[l]->forward(a) : P[l]->forward(a).log_softmax(1);
   if (cfg.hip_gemm && cfg.fuse_activation) {
     const double p = ctx.is_train() ? cfg.drop_rate : 0.0;
     return hip_linear_act(a, P[l]->W, p, (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1,
@@ -455,6 +473,9 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
     if (loss_target && l == L - 1)  // vertexForward + Loss of the last layer, fused
       X = ctx.runVertexForward(
           [&](NtsVar& a) {
+            if (cfg.multi_label)
+              return hip_linear_bce(a, P[l]->W, *loss_target, sg->sampled_sgs[0]->dev_dst(),
+                                    cs.get(), count_to_);
             return hip_linear_xent(a, P[l]->W, *loss_target, cs.get(), count_to_);
           },
           Y);
@@ -488,6 +509,11 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_gat(SampledSubgraph* sg) {
 }
 
 void GCN_SAMPLE_ALLGPU_impl::Loss(NtsVar& left, NtsVar& right) {
+  if (cfg.multi_label) {  // left: raw logits, right: float 0/1 targets
+    loss = torch::binary_cross_entropy_with_logits(left, right);
+    if (ctx.training) ctx.appendNNOp(left, loss);
+    return;
+  }
   NtsVar a = left.log_softmax(1);
   loss = torch::nll_loss(a, right);
   if (ctx.training) ctx.appendNNOp(left, loss);
@@ -617,7 +643,7 @@ float GCN_SAMPLE_ALLGPU_impl::train_batch() {
   double t1 = now_s();
   if (cfg.pd_cache) pd_train(slot);
   mark("T<", *cs);
-  target = lbl_[slot].narrow(0, 0, (int64_t)sg->sampled_sgs[0]->v_size);
+  if (!cfg.multi_label) target = lbl_[slot].narrow(0, 0, (int64_t)sg->sampled_sgs[0]->v_size);
   ctx.train();
   if (early_ && cfg.profile) prof.add_units(KernelProfiler::BOTTOM_AGG, bottom_bytes(sg, true));
   const int L = (int)P.size();
@@ -627,6 +653,21 @@ float GCN_SAMPLE_ALLGPU_impl::train_batch() {
     count_correct(acts.back(), target);
     loss.backward();
     ctx.reset();
+  } else if (cfg.multi_label) {
+    const bool fuse_loss = fuse_bce();
+    count_to_ = dptr<uint32_t>(f1_);
+    auto acts = forward(sg, false, early_ ? &pre_y_[slot] : nullptr,
+                        fuse_loss ? &label_bits_ : nullptr);
+    count_to_ = nullptr;
+    if (fuse_loss) {
+      loss = acts.back();
+    } else {  // the libtorch chain: matmul, binary_cross_entropy_with_logits
+      NtsVar out = acts.back();
+      target = batch_targets(sg);
+      count_f1(f1_, out, target);
+      Loss(out, target);
+    }
+    ctx.self_backward(false);
   } else {
     const bool fuse_loss = cfg.fuse_loss && cfg.hip_gemm && L >= 2 &&
                            hip_linear_xent_supported(P[L - 1]->W.size(0), P[L - 1]->W.size(1));
@@ -746,6 +787,43 @@ uint64_t GCN_SAMPLE_ALLGPU_impl::train_correct() {
 void GCN_SAMPLE_ALLGPU_impl::reset_correct() {
   auto guard = cs->guard();
   correct_.zero_();
+  if (f1_.defined()) f1_.zero_();
+}
+
+// ---- multi_label ----
+bool GCN_SAMPLE_ALLGPU_impl::fuse_bce() const {
+  const size_t L = P.size();
+  return cfg.fuse_loss && cfg.hip_gemm && L >= 2 &&
+         hip_linear_bce_supported(P[L - 1]->W.size(0), P[L - 1]->W.size(1));
+}
+
+NtsVar GCN_SAMPLE_ALLGPU_impl::batch_targets(SampledSubgraph* sg) const {
+  sampCSC* s0 = sg->sampled_sgs[0];
+  NtsVar ids = s0->destination.narrow(0, 0, (int64_t)s0->v_size).to(torch::kInt64);
+  return unpack_label_bits(label_bits_.index_select(0, ids), cfg.layer_size.back());
+}
+
+void GCN_SAMPLE_ALLGPU_impl::count_f1(NtsVar& counts, const NtsVar& logits, const NtsVar& targets) {
+  torch::NoGradGuard ng;
+  NtsVar pos = logits.gt(0), t = targets.gt(0.5);
+  counts.add_(torch::stack({pos.logical_and(t).sum(), pos.logical_and(t.logical_not()).sum(),
+                            pos.logical_not().logical_and(t).sum()})
+                  .to(torch::kInt32));
+}
+
+double GCN_SAMPLE_ALLGPU_impl::micro_f1(const NtsVar& counts) {
+  NtsVar c = counts.cpu();
+  const auto* p = reinterpret_cast<const uint32_t*>(c.data_ptr<int32_t>());
+  const double tp = p[0], den = 2.0 * p[0] + (double)p[1] + (double)p[2];
+  return den > 0.0 ? 2.0 * tp / den : 0.0;
+}
+
+std::vector<uint64_t> GCN_SAMPLE_ALLGPU_impl::f1_counts() {
+  TORCH_CHECK(cfg.multi_label, "f1_counts: a multi_label driver's counters");
+  cs->synchronize();
+  NtsVar c = f1_.cpu();
+  const auto* p = reinterpret_cast<const uint32_t*>(c.data_ptr<int32_t>());
+  return {p[0], p[1], p[2]};
 }
 
 double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
@@ -760,15 +838,30 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
   s.rng_mode = cfg.rng_mode;
   s.up_degree = cfg.up_degree;
   s.batch_seq = eval_seq;
-  NtsVar correct = torch::zeros({1}, u32_opts(graph->device));
-  const bool fuse_loss = !cfg.gat && cfg.fuse_loss && cfg.hip_gemm && L >= 2 &&
-                         hip_linear_xent_supported(P[L - 1]->W.size(0), P[L - 1]->W.size(1));
+  NtsVar correct = torch::zeros({cfg.multi_label ? 3 : 1}, u32_opts(graph->device));
+  const bool fuse_loss = cfg.multi_label
+                             ? fuse_bce()
+                             : !cfg.gat && cfg.fuse_loss && cfg.hip_gemm && L >= 2 &&
+                                   hip_linear_xent_supported(P[L - 1]->W.size(0), P[L - 1]->W.size(1));
   ctx.eval();
   {
     torch::NoGradGuard ng;
     NtsVar tgt;
     while (s.sample_not_finished()) {
       SampledSubgraph* sg = s.sample_gpu_fast(cfg.batch_size, 0, *cs, wt);
+      if (cfg.multi_label) {
+        if (fuse_loss) {  // the loss kernel counts tp, fp, fn as it goes
+          count_to_ = dptr<uint32_t>(correct);
+          forward(sg, false, nullptr, &label_bits_);
+          count_to_ = nullptr;
+        } else {
+          auto acts = forward(sg, false);
+          count_f1(correct, acts.back(), batch_targets(sg));
+        }
+        TORCH_CHECK(hipEventRecord(sg->consumed, (hipStream_t)cs->stream()) == hipSuccess,
+                    "hipEventRecord");
+        continue;
+      }
       s.load_label_gpu(*cs, sg, tgt, L_GT);
       if (cfg.gat) {
         auto acts = forward_gat(sg);
@@ -789,6 +882,7 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
   ctx.train();
   eval_seq = s.batch_seq;
   cs->synchronize();
+  if (cfg.multi_label) return micro_f1(correct);
   return (double)(uint32_t)correct.cpu().item<int32_t>() / (double)nids.size();
 }
 
@@ -840,11 +934,11 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
       if (W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
         NtsVar H = P[l]->forward(X);
         NtsVar Y = aggregate(H, !last);
-        X = last ? Y.log_softmax(1) : Y;
+        X = last && !cfg.multi_label ? Y.log_softmax(1) : Y;
       } else {  // aggregate first: act((A X) W)
         NtsVar Y = aggregate(X, false);
         if (last)
-          X = P[l]->forward(Y).log_softmax(1);
+          X = cfg.multi_label ? P[l]->forward(Y) : P[l]->forward(Y).log_softmax(1);
         else if (cfg.hip_gemm && cfg.fuse_activation)  // p = 0: no mask, no offset drawn
           X = hip_linear_act(Y, W, 0.0, 0, 0, cs.get(), false);
         else
@@ -876,6 +970,12 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate_full(const std::vector<VertexId>& nids) 
   NtsVar idx = torch::from_blob((void*)nids.data(), {(int64_t)nids.size()}, torch::kInt32)
                    .to(torch::Device(torch::kCUDA, graph->device))
                    .to(torch::kInt64);
+  if (cfg.multi_label) {
+    NtsVar counts = torch::zeros({3}, u32_opts(graph->device));
+    count_f1(counts, out.index_select(0, idx),
+             unpack_label_bits(label_bits_.index_select(0, idx), cfg.layer_size.back()));
+    return micro_f1(counts);
+  }
   // labels gathered and rows counted on the device; one scalar comes back
   NtsVar n_ok = out.index_select(0, idx).argmax(1).eq(L_GT.index_select(0, idx)).sum();
   const int64_t correct = n_ok.cpu().item<int64_t>();

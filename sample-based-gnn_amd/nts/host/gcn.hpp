@@ -27,6 +27,12 @@ struct GCNConfig {
   bool pipeline = true;               // sample batch i+1 on its own stream while i trains
   bool fuse_activation = true;        // hidden layers: relu + dropout in the MFMA GEMM
   bool fuse_loss = true;              // training: output layer + log_softmax x2 + nll in 2 kernels
+  // Multi-label node classification (no reference counterpart): the label
+  // tensor is [V, layer_size.back()] of 0/1, the top layer gives raw logits,
+  // the loss is the mean sigmoid binary cross-entropy over all entries (fused:
+  // nts_hip_linear_bce_*), and evaluate() / evaluate_full() return the
+  // micro-F1 of the prediction z > 0.  GCN / GraphSAGE layers only.
+  bool multi_label = false;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its
@@ -125,19 +131,25 @@ class GCN_SAMPLE_ALLGPU_impl {
   // (no per-batch sync); train_correct() reads the count (synchronises).
   uint64_t train_correct();
   void reset_correct();
+  // multi_label: (tp, fp, fn) of the training batches since reset_correct()
+  // (counted on the device as they train; synchronises)
+  std::vector<uint64_t> f1_counts();
   // Forward(eval_sampler, 1/2): eval mode over `nids` in batches of the
   // training batch size, sampled like training (the reference's eval/test
-  // samplers); returns correct / |nids|.
+  // samplers); returns correct / |nids| (multi_label: the micro-F1
+  // 2 tp / (2 tp + fp + fn) over those batches, 0 when nothing is positive).
   double evaluate(const std::vector<VertexId>& nids);
   // Full-neighbour layer-wise inference over the whole graph (no sampling; the
   // reference has no counterpart): [V, C] log-softmax rows of every vertex in
   // eval mode, layer by layer — hidden layers relu((A X) W), the last
   // log_softmax((A X) W), A = nts_hip_spmm_graph_fwd under cfg.weight_type,
-  // each layer aggregated on its narrower side.  Deterministic: no RNG stream,
+  // each layer aggregated on its narrower side (multi_label: the raw logits,
+  // no log_softmax).  Deterministic: no RNG stream,
   // sampler slot, eval_seq or dropout offset is touched.  Not for GAT,
   // UP_DEGREE or a spilled feature table (cache_rate >= 0).
   NtsVar infer_full();
-  // correct / |nids| of infer_full()'s argmax rows (counted on the device)
+  // correct / |nids| of infer_full()'s argmax rows (counted on the device);
+  // multi_label: the micro-F1 of its logits > 0 over the rows `nids`
   double evaluate_full(const std::vector<VertexId>& nids);
   // cfg.profile: device ms of each layer's aggregation in the last infer_full()
   std::vector<double> full_agg_ms;
@@ -179,7 +191,8 @@ class GCN_SAMPLE_ALLGPU_impl {
 
  private:
   NtsVar vertexForward(int l, NtsVar& a);
-  // with `loss_target` (training), the last element is the fused scalar loss
+  // with `loss_target` (the batch's targets; multi_label: the packed label
+  // table), the last element is the fused scalar loss
   std::vector<NtsVar> forward(SampledSubgraph* sg, bool keep, const NtsVar* pre_y = nullptr,
                               const NtsVar* loss_target = nullptr);
   void issue(int slot, NtsStream& st);
@@ -198,6 +211,15 @@ class GCN_SAMPLE_ALLGPU_impl {
   void count_correct(const NtsVar& out, const NtsVar& tgt);  // non-fused output layers
   NtsVar correct_;        // int32 [1]: correct rows of the training batches since reset
   uint32_t* count_to_ = nullptr;  // where forward's fused loss adds its correct count
+  // ---- multi_label ----
+  NtsVar label_bits_;     // int32 [V, ceil(C / 32)]: the packed 0/1 labels of every vertex
+  NtsVar f1_;             // int32 [3]: tp, fp, fn of the training batches since reset
+  bool fuse_bce() const;  // the fused BCE kernels take this model's top layer
+  // float [n, C] targets of a sampled batch's seeds (the libtorch chain)
+  NtsVar batch_targets(SampledSubgraph* sg) const;
+  // counts[0..2] += tp, fp, fn of logits > 0 against float 0/1 targets
+  static void count_f1(NtsVar& counts, const NtsVar& logits, const NtsVar& targets);
+  static double micro_f1(const NtsVar& counts);
   // ---- PD cache state ----
   static constexpr int kPdRing = 4;  // super-batches in flight (sampler lookahead)
   void pd_issue(int slot, NtsStream& st);  // per batch, at sampling time

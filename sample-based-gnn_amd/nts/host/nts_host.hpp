@@ -420,6 +420,18 @@ bool hip_linear_xent_supported(int64_t K, int64_t C);
 // correct != NULL: *correct += rows whose argmax is the target (getCorrect)
 NtsVar hip_linear_xent(const NtsVar& y, const NtsVar& W, const NtsVar& target, NtsStream* cs,
                        uint32_t* correct = nullptr);
+// Multi-label output layer + loss: binary_cross_entropy_with_logits(y W, T)
+// (mean) in the fused kernels nts_hip_linear_bce_fwd/train.  label_bits: the
+// packed targets of every vertex, int32 [V, wpr] (pack_label_bits); index:
+// device ids of y's rows (the batch's seeds), n = y.size(0).  counts != NULL:
+// counts[0..2] += tp, fp, fn of the prediction z > 0.
+bool hip_linear_bce_supported(int64_t K, int64_t C);
+NtsVar hip_linear_bce(const NtsVar& y, const NtsVar& W, const NtsVar& label_bits,
+                      const VertexId* index, NtsStream* cs, uint32_t* counts = nullptr);
+// [V, C] 0/1 labels (uint8, bool or int64) -> int32 [V, ceil(C / 32)]: label c
+// is bit c & 31 of word c >> 5; and rows of that table back to float [n, C]
+NtsVar pack_label_bits(const NtsVar& labels);
+NtsVar unpack_label_bits(const NtsVar& words, int64_t C);
 // row-major fp32 views the HIP GEMMs take without a copy (unit column stride)
 NtsVar row_major(const NtsVar& x);
 // [rows, F] with 128-byte aligned rows when F >= 64 (padded leading dimension)

@@ -27,6 +27,12 @@ the MI355X path of this build; the mapping is:
                                       fraction cached in HBM
   GATSAMPLEALLGPU                     GAT
 
+MULTI_LABEL:1 (GCN / GraphSAGE algorithms): the label file holds
+`id b_0 ... b_{C-1}` (C = the last layer's width), training minimises the mean
+sigmoid binary cross-entropy, and the report lines are `Train F1:`, `Eval F1:`,
+`Test F1:` (micro-F1 of logits > 0; `Full Eval F1:` / `Full Test F1:` under
+FULL_INFERENCE:1) instead of the accuracies.
+
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
 """
@@ -76,12 +82,16 @@ def load_inputs(info: dataloader.InputInfo, base: pathlib.Path, n_classes: int, 
     F = info.layers[0]
     if info.feature_file in ("", "random"):
         feats, labels, masks = dataloader.random_generate(V, F, n_classes)
+        if info.multi_label:
+            labels = np.random.default_rng(1).integers(0, 2, (V, n_classes)).astype(np.uint8)
     else:
         fpath = _path(base, info.feature_file)
         if not fpath.exists() and pathlib.Path(str(fpath) + ".zip").exists():
             fpath = pathlib.Path(str(fpath) + ".zip")
         feats, labels, masks = dataloader.read_feature_label_mask(
             fpath, _path(base, info.label_file), _path(base, info.mask_file), V, F)
+        if info.multi_label:  # (the lock-step reader kept column 1 only)
+            labels = dataloader.read_multilabel_file(_path(base, info.label_file), V, n_classes)
     return src, dst, feats, labels, masks
 
 
@@ -92,6 +102,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         raise SystemExit(f"ALGORITHM {info.algorithm}: not supported by this build "
                          f"(supported: {', '.join(sorted(ALGORITHMS))})")
     model, weight, rng, bias, place = ALGORITHMS[algo]
+    if info.multi_label and model == "gat":
+        raise SystemExit(f"ALGORITHM {info.algorithm}: MULTI_LABEL is not supported with GAT "
+                         "(GCN / GraphSAGE algorithms only)")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -105,7 +118,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         weight="none" if model == "gat" else weight, bias_correction=bias,
         pipeline=info.pipeline_num > 1, up_degree=info.up_degree, gat=model == "gat",
         cache_rate=cache_rate, shuffle=True, pd_cache=pd, pd_rate=info.cache_rate,
-        pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu")
+        pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu",
+        multi_label=bool(info.multi_label))
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
@@ -173,20 +187,34 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
         te = time.perf_counter()
         drv.reset_correct()
         drv.run_epoch()
-        correct = drv.train_correct()  # synchronises
+        if info.multi_label:
+            tp, fp, fn = drv.f1_counts()  # synchronises
+        else:
+            correct = drv.train_correct()  # synchronises
         loss = float(drv.loss.detach().cpu())
         t_train = time.perf_counter() - te
         acc_val = drv.evaluate(torch.from_numpy(ids["val"])) if ids["val"].size else 0.0
         acc_test = drv.evaluate(torch.from_numpy(ids["test"])) if ids["test"].size else 0.0
         n_train = int(train.numel())
-        rec = {"epoch": ep, "train_acc": correct / max(n_train, 1), "train_correct": int(correct),
-               "n_train": n_train, "eval_acc": acc_val, "test_acc": acc_test, "loss": loss,
-               "epoch_time_s": time.perf_counter() - te, "train_time_s": t_train}
+        if info.multi_label:  # evaluate() returned micro-F1s
+            f1 = 2.0 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0
+            rec = {"epoch": ep, "train_f1": f1, "train_tp": int(tp), "train_fp": int(fp),
+                   "train_fn": int(fn), "n_train": n_train, "eval_f1": acc_val, "test_f1": acc_test,
+                   "loss": loss, "epoch_time_s": time.perf_counter() - te, "train_time_s": t_train}
+        else:
+            rec = {"epoch": ep, "train_acc": correct / max(n_train, 1), "train_correct": int(correct),
+                   "n_train": n_train, "eval_acc": acc_val, "test_acc": acc_test, "loss": loss,
+                   "epoch_time_s": time.perf_counter() - te, "train_time_s": t_train}
         hist.append(rec)
-        if rank == 0:
+        if rank == 0 and info.multi_label:
+            out(f"Train F1: {f1:f} {tp} {fp} {fn}")
+            out(f"Eval F1: {acc_val:f} {ids['val'].size}")
+            out(f"Test F1: {acc_test:f} {ids['test'].size}")
+        elif rank == 0:
             out(f"Train Acc: {rec['train_acc']:f} {correct} {n_train}")
             out(f"Eval Acc: {acc_val:f} {int(round(acc_val * ids['val'].size))} {ids['val'].size}")
             out(f"Test Acc: {acc_test:f} {int(round(acc_test * ids['test'].size))} {ids['test'].size}")
+        if rank == 0:
             out(f"GNNmini::Running.Epoch[{ep}]:Times[{rec['epoch_time_s']:f}(s)]:loss\t{loss:f}")
     res = {"cfg": str(cfg_path), "algorithm": info.algorithm, "epochs": hist}
     if info.full_inference:
@@ -196,6 +224,11 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
         for key, name in (("val", "Eval"), ("test", "Test")):
             n = int(ids[key].size)
             acc = drv.evaluate_full(torch.from_numpy(ids[key])) if n else 0.0
+            if info.multi_label:
+                res[f"full_{name.lower()}_f1"] = acc
+                if rank == 0:
+                    out(f"Full {name} F1: {acc:f} {n}")
+                continue
             res[f"full_{name.lower()}_acc"] = acc
             if rank == 0:
                 out(f"Full {name} Acc: {acc:f} {int(round(acc * n))} {n}")

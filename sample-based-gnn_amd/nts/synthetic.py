@@ -96,6 +96,18 @@ def labels_masks(V: int, C: int, device="cuda", seed: int = 11):
     return labels, masks
 
 
+def multilabels(V: int, C: int, feat: torch.Tensor, seed: int = 13) -> torch.Tensor:
+    """Learnable multi-hot labels, uint8 [V, C] on feat's device: label c of a
+    vertex is 1 where the fixed random projection c (N(0,1) weights from
+    `seed`) of its features is positive, so about half the bits are set and a
+    model that sees the features can fit them."""
+    assert feat.shape[0] == V
+    g = torch.Generator(device=feat.device)
+    g.manual_seed(seed)
+    proj = torch.randn(feat.shape[1], C, generator=g, device=feat.device, dtype=torch.float32)
+    return (feat.to(torch.float32) @ proj > 0).to(torch.uint8)
+
+
 def shaped(name: str, device="cuda", scale: float = 1.0) -> tuple[SyntheticGraph, int, int]:
     V, E, F, C, ratio = SHAPES[name]
     V = max(int(V * scale), 16)
