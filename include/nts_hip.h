@@ -610,7 +610,11 @@ int nts_hip_gemm_tn_masked_f32(nts_hip_ctx *ctx, int M, int N, int K, const floa
  * arithmetic: logits = Y W, log_softmax (vertexForward,
  * toolkits/GCN_SAMPLE_ALLGPU.hpp:247-252), log_softmax again + mean
  * nll_loss (Loss, :214-222).  Y [n x K] (ld ldy), W [K x C] row-major,
- * labels int64 [n] in [0, C), C <= 64.  Writes the scalar loss (device).
+ * labels int64 [n] in [0, C).  Writes the scalar loss (device).
+ * Shapes (all three entry points): K % 16 == 0 and either C <= 64 with K x C
+ * within the kernel's LDS (W resident), or 64 < C <= 512 with K <= 512 (the
+ * wide form, W streamed from global memory); other shapes return
+ * NTS_ERR_INVALID and launch nothing.
  * correct != NULL: *correct += the rows whose argmax (first index of the
  * largest log_softmax value) is the label — getCorrect
  * (toolkits/GCN_SAMPLE_ALLGPU.hpp:166-172) accumulated on the device.

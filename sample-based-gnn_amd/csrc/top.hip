@@ -17,6 +17,9 @@
 // forward = <LOSS>, backward = <GRAD>, train = <LOSS, GRAD> (bit-identical
 // to forward + backward with grad 1: same code, same orders).
 //
+// (What follows describes the form for C <= 64, W resident in LDS; above 64
+// classes, to 512, k_top_xent_wide below streams W from global memory.)
+//
 // (The multi-label form of the layer, sigmoid BCE over bit-packed targets with
 // the micro-F1 counters, is k_top_bce_ks below: the same block shape, shared
 // staging and products, an element-wise middle.)
@@ -566,6 +569,266 @@ __global__ __launch_bounds__(kTopThreads) void k_top_xent_ks(TopArgs a) {
   }
 }
 
+// ---- wide-class form: 64 < C <= 512 ------------------------------------------
+// The same contract as k_top_xent_ks at class counts whose W [K x Cp] does not
+// fit LDS (K = 256, Cp = 176 is 180 KB).  W stays in global memory (it is
+// L2-resident) and goes to the MFMAs through registers: with the waves split
+// over column tiles every element of W is the B operand of exactly one MFMA of
+// a 16-row tile, so an LDS copy would be written once and read once.
+//   logits  wave w takes the column tiles ct = w, w + 4, ..., two at a time
+//           (independent chains over the whole K), 32 k per round with the
+//           next round's 16 loads in flight behind the MFMAs; the tile goes to
+//           sZ [16][Cp + 4];
+//   finish  wave w takes the rows 4 g + w; a lane holds Cp / 16 entries of its
+//           row, re-read from sZ in each pass (max; sum; sum + argmax of lp;
+//           sum of d1; dZ) — the arithmetic per entry and the order of every sum
+//           (ct ascending in the lane, then the DPP tree) are k_top_xent_ks's;
+//           dZ overwrites the logits in place, each lane the entries it read;
+//   dY      wave w takes the k tiles kt = w, w + 4, ..., two at a time, W^T
+//           read from global (lane (i, g): W[16 kt + i][c0 + g]);
+//   dW      wave w takes the rows of its k tiles, the column tiles two at a
+//           time, into this block's slab (k_top_xent_ks's chunk layout).
+// A block walks the row tiles blockIdx.x, + gridDim.x, ...; the grid is capped
+// so that the slabs stay within kWideSlabBytes (wide_blocks), and a block's
+// later tiles are added onto its slab in walk order: the summation order is a
+// function of (n, K, C) alone.  Loss and accuracy partials are per row tile.
+// LDS: (16 (K + 4) + 16 (Cp + 4) + 16) floats — 66,112 bytes at K = Cp = 512,
+// the largest shape taken, so no LDS bound is checked beyond K, C <= 512.
+constexpr int kWideMaxC = 512, kWideMaxK = 512;
+constexpr size_t kWideSlabBytes = (size_t)128 << 20;
+
+static inline size_t top_wide_lds(int K, int Cp) {
+  return ((size_t)16 * (K + 4) + (size_t)16 * (Cp + 4) + 16) * sizeof(float);
+}
+// blocks (= dW slabs) of the wide form for ntiles 16-row tiles
+static inline int wide_blocks(int ntiles, int K, int Cp) {
+  const size_t cap = kWideSlabBytes / ((size_t)K * Cp * sizeof(float));  // >= 128
+  return (int)std::min<size_t>((size_t)ntiles, cap);
+}
+
+template <bool LOSS, bool GRAD, bool VEC4>
+__global__ __launch_bounds__(kTopThreads) void k_top_xent_wide(TopArgs a) {
+  constexpr int NW = kTopWaves;
+  static_assert(NW == 4, "one row 4 g + w per lane group and wave");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int K = a.K, C = a.C, P = K + 4, nkt = K / 16;
+  const int NCT = (C + 15) / 16, CP = 16 * NCT, PZ = CP + 4;
+  float* sY = smem;              // [16][K + 4]
+  float* sZ = sY + 16 * P;       // [16][CP + 4] logits, then dZ
+  float* wl = sZ + 16 * PZ;      // [NW] loss terms of the waves
+  uint32_t* wc = reinterpret_cast<uint32_t*>(wl + NW);  // [NW]
+  const int ntiles = (a.n + 15) / 16;
+  const float gl = GRAD ? (a.grad ? *a.grad : 1.0f) / (float)a.n : 0.f;
+  const uint64_t nslab = gridDim.x, slab = blockIdx.x;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r0 = tile * 16;
+    const int rl = 4 * g + w, r = r0 + rl;  // the row this lane group finishes
+    const int tgt = r < a.n ? (int)a.labels[r] : -1;
+    stage_y_tile<VEC4>(a, sY, r0);
+    __syncthreads();
+    // ---- logits: this wave's column tiles, two at a time
+    for (int ct0 = w; ct0 < NCT; ct0 += 2 * NW) {
+      const int c0 = 16 * ct0 + i, c1 = c0 + 16 * NW;
+      const bool on0 = c0 < C, on1 = ct0 + NW < NCT && c1 < C;
+      const float* w0 = a.W + (on0 ? c0 : 0);
+      const float* w1 = a.W + (on1 ? c1 : 0);
+      constexpr int B = 8;  // k steps of 4 per round
+      float b0[B], b1[B], n0[B], n1[B];
+#pragma unroll
+      for (int u = 0; u < B; ++u) {
+        const int k = 4 * u + g;
+        b0[u] = (on0 && k < K) ? w0[(size_t)k * C] : 0.f;
+        b1[u] = (on1 && k < K) ? w1[(size_t)k * C] : 0.f;
+      }
+      f32x4 z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
+      for (int k1 = 0; k1 < K; k1 += 4 * B) {
+#pragma unroll
+        for (int u = 0; u < B; ++u) {  // the next round's loads (zeros past K)
+          const int k = k1 + 4 * B + 4 * u + g;
+          n0[u] = (on0 && k < K) ? w0[(size_t)k * C] : 0.f;
+          n1[u] = (on1 && k < K) ? w1[(size_t)k * C] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+          const int k = k1 + 4 * u + g;
+          const float av = k < K ? sY[i * P + k] : 0.f;
+          z0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0[u], z0, 0, 0, 0);
+          z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1[u], z1, 0, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+          b0[u] = n0[u];
+          b1[u] = n1[u];
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        sZ[(4 * g + v) * PZ + 16 * ct0 + i] = z0[v];
+        if (ct0 + NW < NCT) sZ[(4 * g + v) * PZ + 16 * (ct0 + NW) + i] = z1[v];
+      }
+    }
+    __syncthreads();
+    // ---- finish row rl: log_softmax twice, loss and accuracy terms, dZ in place
+    float lw = 0.f;
+    uint32_t okw = 0;
+    {
+      float* zr = sZ + rl * PZ + i;  // entry ct of this lane: zr[16 ct]
+      float m = -INFINITY;
+      for (int ct = 0; ct < NCT; ++ct)
+        if (16 * ct + i < C) m = fmaxf(m, zr[16 * ct]);
+      m = grp_max(m);
+      float sm = 0.f;
+      for (int ct = 0; ct < NCT; ++ct)
+        if (16 * ct + i < C) sm += expf(zr[16 * ct] - m);
+      sm = grp_sum(sm);
+      const float lse = m + logf(sm);
+      // max over c of lp[c] = z[c] - lse: rounding is monotone, so it is m - lse
+      const float m2 = m - lse;
+      float s2 = 0.f, best = -INFINITY;
+      int bi = 0x7fffffff;
+      for (int ct = 0; ct < NCT; ++ct) {
+        const float lp = zr[16 * ct] - lse;
+        if (16 * ct + i < C) {
+          s2 += expf(lp - m2);
+          if (lp > best) {  // first index among equal values: ct ascends
+            best = lp;
+            bi = 16 * ct + i;
+          }
+        }
+      }
+      s2 = grp_sum(s2);
+      const float lse2 = m2 + logf(s2);
+      const bool mine = tgt >= 0 && tgt < C && (tgt & 15) == i;  // this lane holds the label's entry
+      if (LOSS) {
+        if (mine) lw -= (zr[tgt - i] - lse) - lse2;
+        if (a.cpart) {  // getCorrect: argmax of lp, first index among equal values
+          bi = grp_argmax(best, bi);
+          okw = (i == 0 && tgt >= 0 && bi == tgt) ? 1u : 0u;
+        }
+      }
+      if (GRAD) {
+        // d2 is -gl at the label and 0 elsewhere: its row sum is exact
+        const float s2g = grp_sum(mine ? -gl : 0.f);
+        float s1 = 0.f;
+        for (int ct = 0; ct < NCT; ++ct) {
+          const int c = 16 * ct + i;
+          const float lp2 = (zr[16 * ct] - lse) - lse2;
+          const float d2 = c == tgt ? -gl : 0.f;
+          if (c < C) s1 += d2 - expf(lp2) * s2g;
+        }
+        s1 = grp_sum(s1);
+        for (int ct = 0; ct < NCT; ++ct) {
+          const int c = 16 * ct + i;
+          const float lp = zr[16 * ct] - lse, lp2 = lp - lse2;
+          const float d2 = c == tgt ? -gl : 0.f;
+          const float d1 = d2 - expf(lp2) * s2g;
+          zr[16 * ct] = (c < C && r < a.n) ? d1 - expf(lp) * s1 : 0.f;
+        }
+      }
+    }
+    if (LOSS) {  // the wave's terms, then the tile's in wave order (below)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lw += __shfl_down(lw, o, kWave);
+      if (lane == 0) wl[w] = lw;
+      if (a.cpart) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) okw += __shfl_down(okw, o, kWave);
+        if (lane == 0) wc[w] = okw;
+      }
+    }
+    __syncthreads();
+    if (LOSS && threadIdx.x == 0) {
+      float l = 0.f;
+      uint32_t c = 0;
+      for (int q = 0; q < NW; ++q) {
+        l += wl[q];
+        if (a.cpart) c += wc[q];
+      }
+      a.lpart[tile] = l;
+      if (a.cpart) a.cpart[tile] = c;
+    }
+    if (GRAD) {
+      const bool first = tile == (int)blockIdx.x;
+      // ---- dY [16 x K] = dZ W^T: this wave's k tiles, two at a time
+      for (int kt0 = w; kt0 < nkt; kt0 += 2 * NW) {
+        const bool has1 = kt0 + NW < nkt;
+        const float* w0 = a.W + (size_t)(16 * kt0 + i) * C;
+        const float* w1 = a.W + (size_t)(16 * (has1 ? kt0 + NW : kt0) + i) * C;
+        constexpr int B = 8;  // class steps of 4 per round
+        float b0[B], b1[B], n0[B], n1[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+          const int c = 4 * u + g;
+          b0[u] = c < C ? w0[c] : 0.f;
+          b1[u] = c < C ? w1[c] : 0.f;
+        }
+        f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+        for (int c1 = 0; c1 < CP; c1 += 4 * B) {
+#pragma unroll
+          for (int u = 0; u < B; ++u) {
+            const int c = c1 + 4 * B + 4 * u + g;
+            n0[u] = c < C ? w0[c] : 0.f;
+            n1[u] = c < C ? w1[c] : 0.f;
+          }
+#pragma unroll
+          for (int u = 0; u < B; ++u) {
+            const int c = c1 + 4 * u + g;
+            const float av = c < C ? sZ[i * PZ + c] : 0.f;
+            d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0[u], d0, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1[u], d1, 0, 0, 0);
+          }
+#pragma unroll
+          for (int u = 0; u < B; ++u) {
+            b0[u] = n0[u];
+            b1[u] = n1[u];
+          }
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const int rr = r0 + 4 * g + v;
+          if (rr < a.n) {
+            a.dY[(uint64_t)rr * K + 16 * kt0 + i] = d0[v];
+            if (has1) a.dY[(uint64_t)rr * K + 16 * (kt0 + NW) + i] = d1[v];
+          }
+        }
+      }
+      // ---- dW slab [K x CP] += Y^T dZ: the rows of this wave's k tiles
+      for (int kt = w; kt < nkt; kt += NW) {
+        float av[4];
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) av[s4] = sY[(4 * s4 + g) * P + 16 * kt + i];
+        for (int ct0 = 0; ct0 < NCT; ct0 += 2) {
+          const bool has1 = ct0 + 1 < NCT;
+          const int ct1 = has1 ? ct0 + 1 : ct0;
+          f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s4 = 0; s4 < 4; ++s4) {
+            const float* dzr = sZ + (4 * s4 + g) * PZ + i;
+            e0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s4], dzr[16 * ct0], e0, 0, 0, 0);
+            e1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s4], dzr[16 * ct1], e1, 0, 0, 0);
+          }
+#pragma unroll
+          for (int v = 0; v < 4; ++v) {
+            const uint64_t q = (uint64_t)(16 * kt + 4 * g + v) * NCT + ct0;
+            float* p0 = a.part + (q * nslab + slab) * 16 + i;
+            float* p1 = a.part + ((q + 1) * nslab + slab) * 16 + i;
+            if (first) {
+              *p0 = e0[v];
+              if (has1) *p1 = e1[v];
+            } else {  // a later tile of the walk: onto the slab, in walk order
+              *p0 += e0[v];
+              if (has1) *p1 += e1[v];
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // sY, sZ and the waves' terms are rewritten by the next tile
+  }
+}
+
 // ---- multi-label output layer: Z = Y W + mean sigmoid-BCE --------------------
 // The same block shape as k_top_xent_ks (16 rows, the waves split K, W in LDS,
 // the three products on v_mfma_f32_16x16x4_f32) with an element-wise middle:
@@ -721,7 +984,9 @@ __global__ __launch_bounds__(256) void k_top_finish(const float* __restrict__ pa
       if (t < h) red[t] += red[t + h];
       __syncthreads();
     }
-    const int k = q / NCT, c = 16 * (q % NCT) + t;
+    // NCT == 0: the wide form's column-tile count (5 .. 32), from C at run time
+    const int nct = NCT ? NCT : (C + 15) / 16;
+    const int k = q / nct, c = 16 * (q % nct) + t;
     if (t < 16 && c < C) dW[(uint64_t)k * C + c] = red[t];
   } else {
     uint32_t c[NCNT] = {};
@@ -781,6 +1046,23 @@ static int launch_top_any(hipStream_t st, int nblk, int Cp, const TopArgs& a) {
   }
 }
 
+template <bool LOSS, bool GRAD>
+static int launch_top_wide(hipStream_t st, int nblk, int Cp, const TopArgs& a) {
+  const size_t lds = top_wide_lds(a.K, Cp);
+  const bool v4 = a.ldy % 4 == 0 && (uintptr_t)a.Y % 16 == 0;
+  const void* f = v4 ? reinterpret_cast<const void*>(&k_top_xent_wide<LOSS, GRAD, true>)
+                     : reinterpret_cast<const void*>(&k_top_xent_wide<LOSS, GRAD, false>);
+  NTS_HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (v4)
+    hipLaunchKernelGGL((k_top_xent_wide<LOSS, GRAD, true>), dim3(nblk), dim3(kTopThreads), lds, st,
+                       a);
+  else
+    hipLaunchKernelGGL((k_top_xent_wide<LOSS, GRAD, false>), dim3(nblk), dim3(kTopThreads), lds, st,
+                       a);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
 template <int NCT, bool GRAD>
 static int launch_bce(hipStream_t st, int nblk, const BceArgs& a) {
   const size_t lds = top_bce_lds(a.K, 16 * NCT);
@@ -815,12 +1097,20 @@ static int launch_bce_any(hipStream_t st, int nblk, int Cp, const BceArgs& a) {
 template <int NCNT>
 static int launch_finish(hipStream_t st, int Cp, const float* part, int nslab, const float* lpart,
                          int nblk, float denom, int K, int C, bool grad, bool loss_on, float* dW,
-                         float* loss, const uint32_t* cpart, uint32_t* correct) {
+                         float* loss, const uint32_t* cpart, uint32_t* correct,
+                         bool wide = false) {
   const int nchunks = grad ? K * (Cp / 16) : 0;
   const dim3 grid(nchunks + (loss_on ? 1 : 0));
 #define NTS_F(NCT)                                                                            \
   hipLaunchKernelGGL((k_top_finish<NCT, NCNT>), grid, dim3(256), 0, st, part, nslab, lpart, nblk, \
                      denom, C, nchunks, dW, loss, cpart, correct)
+  if constexpr (NCNT == 1) {
+    if (wide) {  // the wide xent form (Cp = 80 .. 512): never the switch's default
+      NTS_F(0);
+      NTS_LAUNCH_CHECK();
+      return NTS_OK;
+    }
+  }
   switch (Cp / 16) {
     case 1: NTS_F(1); break;
     case 2: NTS_F(2); break;
@@ -844,11 +1134,37 @@ extern "C" {
 
 static int top_check(nts_hip_ctx* ctx, int n, int K, int C, uint64_t ldy) {
   NTS_CHECK_ARG(n > 0 && K > 0 && C > 0 && ldy >= (uint64_t)K, "shape");
-  NTS_CHECK_ARG(C <= kWave, "class count above 64 is not supported by the fused loss");
+  NTS_CHECK_ARG(C <= kWideMaxC, "class count above 512 is not supported by the fused loss");
   NTS_CHECK_ARG(K % 16 == 0, "the fused loss needs K % 16 == 0");
-  NTS_CHECK_ARG(top_lds(K, (C + 15) / 16 * 16) <= 160 * 1024, "K x C too large for the fused loss");
+  if (C > kWave)  // the wide form: W is not held in LDS, (K, Cp) = (512, 512) takes 66,112 bytes
+    NTS_CHECK_ARG(K <= kWideMaxK, "K above 512 is not supported by the fused loss above 64 classes");
+  else
+    NTS_CHECK_ARG(top_lds(K, (C + 15) / 16 * 16) <= 160 * 1024, "K x C too large for the fused loss");
   NTS_HIP_TRY(hipSetDevice(ctx->device));
   return NTS_OK;
+}
+
+// 64 < C <= 512: k_top_xent_wide + the finish at its run-time tile count.
+// scratch: [loss partials per row tile, 64-float aligned][correct partials]
+//          [dW slabs: min(ceil(n / 16), 128 MiB / (4 K Cp)) x K x Cp floats]
+static int top_run_wide(nts_hip_ctx* ctx, bool loss_on, bool grad_on, const float* Y, uint64_t ldy,
+                        int n, int K, const float* W, int C, const int64_t* labels,
+                        const float* grad_loss, float* loss, float* dY, float* dW,
+                        uint32_t* correct) {
+  const int Cp = (C + 15) / 16 * 16;
+  const int ntiles = (n + 15) / 16, nblk = wide_blocks(ntiles, K, Cp);
+  const size_t lp = ((size_t)ntiles + 63) / 64 * 64;
+  NTS_RET(ensure_scratch(
+      ctx, (2 * lp + (grad_on ? (size_t)nblk * K * Cp : 0)) * sizeof(float)));
+  float* base = (float*)ctx->scratch;
+  uint32_t* cpart = (loss_on && correct) ? reinterpret_cast<uint32_t*>(base + lp) : nullptr;
+  TopArgs a{Y, ldy, W, labels, grad_loss, n, K, C, base, base + 2 * lp, dY, cpart};
+  hipStream_t st = ctx->stream;
+  if (loss_on && grad_on) NTS_RET((launch_top_wide<true, true>(st, nblk, Cp, a)));
+  else if (loss_on) NTS_RET((launch_top_wide<true, false>(st, nblk, Cp, a)));
+  else NTS_RET((launch_top_wide<false, true>(st, nblk, Cp, a)));
+  return launch_finish<1>(st, Cp, a.part, nblk, a.lpart, ntiles, (float)n, K, C, grad_on, loss_on,
+                          dW, loss, cpart, cpart ? correct : nullptr, true);
 }
 
 // scratch: [loss partials, 64-float aligned][correct partials][dW partial chunks]
@@ -856,6 +1172,9 @@ static int top_run(nts_hip_ctx* ctx, bool loss_on, bool grad_on, const float* Y,
                    int n, int K, const float* W, int C, const int64_t* labels,
                    const float* grad_loss, float* loss, float* dY, float* dW, uint32_t* correct) {
   NTS_RET(top_check(ctx, n, K, C, ldy));
+  if (C > kWave)  // never launch_top_any's default
+    return top_run_wide(ctx, loss_on, grad_on, Y, ldy, n, K, W, C, labels, grad_loss, loss, dY, dW,
+                        correct);
   const int Cp = (C + 15) / 16 * 16;
   const int nblk = (n + 15) / 16, nslab = nblk;  // one dW slab per 16-row block
   const size_t lp = ((size_t)nblk + 63) / 64 * 64;

@@ -365,7 +365,9 @@ class HipContext:
 
     def linear_xent_fwd(self, Y, W, labels, loss, correct=None):
         """loss = nll_loss(log_softmax(log_softmax(Y @ W)), labels) (mean), fused;
-        correct (int32 device scalar) += rows whose argmax is the label."""
+        correct (int32 device scalar) += rows whose argmax is the label.
+        K % 16 == 0; C <= 64 (W in LDS) or 64 < C <= 512 with K <= 512 (the
+        wide form); anything else raises (NTS_ERR_INVALID, nothing launched)."""
         n, K = Y.shape
         check(self.lib.nts_hip_linear_xent_fwd(self.h, ptr(Y), Y.stride(0), n, K, ptr(W), W.shape[1],
                                                ptr(labels), ptr(loss), ptr(correct)))
@@ -376,7 +378,8 @@ class HipContext:
                                                ptr(labels), ptr(grad_loss), ptr(dY), ptr(dW)))
 
     def linear_xent_train(self, Y, W, labels, loss, dY, dW, correct=None):
-        """The loss and its gradients for d loss = 1 in one pass (== fwd + bwd(1))."""
+        """The loss and its gradients for d loss = 1 in one pass (== fwd + bwd(1));
+        the shapes of linear_xent_fwd."""
         n, K = Y.shape
         check(self.lib.nts_hip_linear_xent_train(self.h, ptr(Y), Y.stride(0), n, K, ptr(W),
                                                  W.shape[1], ptr(labels), ptr(loss), ptr(dY),

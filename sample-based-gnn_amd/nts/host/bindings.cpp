@@ -133,6 +133,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("sampled_edges", [](PySampler& p) { return p.s->sampled_edges; });
 
   // the driver's predicates and label packing of the multi-label mode
+  m.def("hip_linear_xent_supported", &hip_linear_xent_supported, py::arg("K"), py::arg("C"));
   m.def("hip_linear_bce_supported", &hip_linear_bce_supported, py::arg("K"), py::arg("C"));
   m.def("pack_label_bits", &pack_label_bits, py::arg("labels"));
   m.def(

@@ -1345,11 +1345,13 @@ NtsVar hip_linear(const NtsVar& x, const NtsVar& W, NtsStream* cs) {
 }
 
 bool hip_linear_xent_supported(int64_t K, int64_t C) {
-  // mirrors the argument checks of nts_hip_linear_xent_fwd/bwd (C <= 64,
-  // K % 16 == 0, W, 64 Y rows and 64 dZ rows in LDS)
+  // mirrors the argument checks of nts_hip_linear_xent_fwd/bwd/train:
+  // K % 16 == 0; C <= 64 with W, 64 Y rows and 64 dZ rows in LDS; 64 < C <= 512
+  // (the wide form, W streamed from global memory) with K <= 512
   const int64_t Cp = (C + 15) / 16 * 16;
-  return K >= 16 && K % 16 == 0 && C >= 1 && C <= 64 &&
-         (K * Cp + 64 * (K + 4) + 64 * Cp) * 4 <= 160 * 1024;
+  if (K < 16 || K % 16 != 0 || C < 1 || C > 512) return false;
+  if (C > 64) return K <= 512;
+  return (K * Cp + 64 * (K + 4) + 64 * Cp) * 4 <= 160 * 1024;
 }
 
 bool hip_linear_bce_supported(int64_t K, int64_t C) {
