@@ -666,6 +666,42 @@ int nts_hip_linear_bce_train(nts_hip_ctx *ctx, const float *Y, uint64_t ldy, int
                              const uint32_t *index, float *loss, float *dY, float *dW,
                              uint32_t *counts);
 
+/* ---- GraphSAGE root weight (csrc/root.hip; no counterpart in the reference) --
+ * The graph op of X' = act([A X | X_dst] W), W = [W_n; W_s] stacked on K.
+ *
+ * Forward, one launch: for every d < *v
+ *   ycat[d, 0:F]  = sum_e w[e] x[row(e), :]   exactly nts_hip_spmm_csc_fwd's sum
+ *   ycat[d, F:2F] = x[self(d), :]             a copy
+ * row(e) = x_row_map ? x_row_map[row_indices[e]] : row_indices[e].  self(d) =
+ * self_index[d], a row of x either way: a local source row (dst_local_id) when
+ * x_row_map is NULL, a global table row (destination) when it is not.
+ * ld_ycat >= 2 F; any F >= 1 (float4 / float2 / scalar by alignment).  Rows
+ * >= *v are left untouched. */
+int nts_hip_spmm_csc_fwd_root(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                              const uint32_t *row_indices, const float *weight,
+                              const uint32_t *v, uint32_t v_cap, const float *x, uint64_t ldx,
+                              const uint32_t *x_row_map, const uint32_t *self_index,
+                              uint32_t feature_size, float *ycat, uint64_t ld_ycat);
+/* src_dst[s] = the d < *v with dst_local_id[d] == s, else NTS_NOT_CACHED, for
+ * s < *s (a merged layer: dst_local_id is one-to-one).  Two launches on the
+ * context's stream: fill, scatter. */
+int nts_hip_root_inverse_map(nts_hip_ctx *ctx, const uint32_t *dst_local_id, const uint32_t *v,
+                             uint32_t v_cap, const uint32_t *s, uint32_t s_cap,
+                             uint32_t *src_dst);
+/* Backward of the forward above for an upstream g_ycat [n, 2F] (pitch ld_g):
+ *   g_in[s, :] = m_s ⊙ ( sum_j w_b[j] g_ycat[ci[j], 0:F]
+ *                        + (src_dst[s] != NTS_NOT_CACHED ? g_ycat[src_dst[s], F:2F] : 0) )
+ * for s < *s.  The sum is nts_hip_spmm_csr_bwd's (order and arithmetic, its
+ * long-row rule included) for the same operands, the self term one more fp32
+ * add, and m_s = [x_act[s, :] > 0] scale when x_act != NULL
+ * (nts_hip_spmm_csr_bwd_postmask's), else 1.  Deterministic, no atomics. */
+int nts_hip_spmm_csr_bwd_root(nts_hip_ctx *ctx, const uint32_t *row_offset,
+                              const uint32_t *column_indices, const float *weight_backward,
+                              const uint32_t *s, uint32_t s_cap, const float *g_ycat,
+                              uint64_t ld_g, const uint32_t *src_dst, const float *x_act,
+                              uint64_t ld_act, float scale, uint32_t feature_size, float *g_in,
+                              uint64_t ld_gin);
+
 /* ---- optimiser ---------------------------------------------------------- */
 /* Fused Adam step on one parameter (n elements), element-wise identical to
  *  bias_correction != 0: Parameter::learnC2C_with_decay_Adam (core/NtsScheduler.hpp:863-880)

@@ -291,6 +291,9 @@ class InputInfo:
     # MULTI_LABEL (this build's key): the label file is `id b_0 ... b_{C-1}`
     # (C = the last layer's width); train with the sigmoid BCE loss, report micro-F1
     multi_label: int = 0
+    # ROOT_WEIGHT (this build's key): GraphSAGE layers with a root weight,
+    # X' = act([A X | X_dst] W) (GCN / GraphSAGE algorithms without PD cache)
+    root_weight: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -317,6 +320,7 @@ class InputInfo:
             "PRE_SAMPLE_FILE": ("pre_sample_file", str),
             "FULL_INFERENCE": ("full_inference", int),
             "MULTI_LABEL": ("multi_label", int),
+            "ROOT_WEIGHT": ("root_weight", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

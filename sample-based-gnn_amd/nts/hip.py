@@ -185,6 +185,29 @@ class HipContext:
                                                      x_act.stride(0), float(scale), F, ptr(g_in),
                                                      g_in.stride(0)))
 
+    def spmm_csc_fwd_root(self, co, ri, w, v_dev, v_cap, x, self_index, ycat, row_map=None):
+        """ycat[d] = [sum_e w[e] x[row(e)] | x[self_index[d]]] (GraphSAGE root weight);
+        with row_map, x is the global table and self_index holds global rows."""
+        F = x.shape[1]
+        check(self.lib.nts_hip_spmm_csc_fwd_root(self.h, ptr(co), ptr(ri), ptr(w), ptr(v_dev),
+                                                 v_cap, ptr(x), x.stride(0), ptr(row_map),
+                                                 ptr(self_index), F, ptr(ycat), ycat.stride(0)))
+
+    def root_inverse_map(self, dst_local_id, v_dev, v_cap, s_dev, s_cap, src_dst):
+        """src_dst[s] = the d with dst_local_id[d] == s, else NTS_NOT_CACHED."""
+        check(self.lib.nts_hip_root_inverse_map(self.h, ptr(dst_local_id), ptr(v_dev), v_cap,
+                                                ptr(s_dev), s_cap, ptr(src_dst)))
+
+    def spmm_csr_bwd_root(self, ro, ci, wb, s_dev, s_cap, g_ycat, src_dst, g_in, x_act=None,
+                          scale=1.0):
+        """g_in = m ⊙ (A^T g_ycat[:, :F] + g_ycat[src_dst, F:]), m = (x_act > 0) * scale
+        (1 without x_act); F = g_in.shape[1]."""
+        F = g_in.shape[1]
+        check(self.lib.nts_hip_spmm_csr_bwd_root(
+            self.h, ptr(ro), ptr(ci), ptr(wb), ptr(s_dev), s_cap, ptr(g_ycat), g_ycat.stride(0),
+            ptr(src_dst), ptr(x_act), x_act.stride(0) if x_act is not None else 0, float(scale),
+            F, ptr(g_in), g_in.stride(0)))
+
     def spmm_csr_bwd_masked(self, ro, ci, wb, s_dev, s_cap, g_out, x_act, g_in, scale=1.0):
         """g_in = A^T (g_out * (x_act > 0) * scale) over the CSR."""
         F = g_out.shape[1]

@@ -40,7 +40,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                fuse_loss=True, sampler_cus=0, sampler_gate=0, pad_features=True, cache_rate=-1.0,
                up_degree=False, gat=False, pd_cache=False, pd_rate=0.2, pd_super_batch=4,
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
-               multi_label=False):
+               multi_label=False, root_weight=False):
     E = ext()
     c = E.GCNConfig()
     c.layer_size = list(layers)
@@ -68,6 +68,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.fuse_activation = bool(fuse_activation)
     c.fuse_loss = bool(fuse_loss)
     c.multi_label = bool(multi_label)
+    c.root_weight = bool(root_weight)
     c.sampler_cus = int(sampler_cus)
     c.sampler_gate = int(sampler_gate)
     c.pad_features = bool(pad_features)

@@ -620,6 +620,50 @@ NtsVar SingleGPUSampleGraphOp::backward(NtsVar& g) {
   return SingleGPUAllSampleGraphOp::backward(g);
 }
 
+SingleGPURootGraphOp::SingleGPURootGraphOp(SampledSubgraph* sgs, int layer_, NtsStream* cs,
+                                           bool gather)
+    : subgraphs(sgs), layer(layer_), cuda_stream(cs), gather_from_table(gather) {}
+
+NtsVar SingleGPURootGraphOp::forward(NtsVar& f_input) {
+  sampCSC* sg = subgraphs->sampled_sgs[layer];
+  TORCH_CHECK(sg->dst_local_id.defined(), "root weight needs a merged src/dst layer");
+  TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
+                  f_input.stride(1) == 1,
+              "graph op input must be a row-major fp32 CUDA matrix");
+  TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
+              "graph op input has fewer rows than src_size");
+  const int64_t F = f_input.size(1);
+  NtsVar f_output = row_padded_empty((int64_t)sg->v_size, 2 * F, cuda_stream->device());
+  hip_check(nts_hip_spmm_csc_fwd_root(
+                cuda_stream->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_e_w_f(),
+                sg->dev_v_size(), sg->v_size, f_input.data_ptr<float>(),
+                (uint64_t)f_input.stride(0), gather_from_table ? sg->dev_src() : nullptr,
+                gather_from_table ? sg->dev_dst() : sg->dev_dst_local_id(), (uint32_t)F,
+                f_output.data_ptr<float>(), (uint64_t)f_output.stride(0)),
+            "nts_hip_spmm_csc_fwd_root");
+  if (output_requires_grad) f_output.set_requires_grad(true);
+  return f_output;
+}
+
+NtsVar SingleGPURootGraphOp::backward(NtsVar& g) {
+  sampCSC* sg = subgraphs->sampled_sgs[layer];
+  TORCH_CHECK(sg->has_csr && sg->src_dst.defined(),
+              "root weight backward needs the CSR transpose and the inverse map");
+  NtsVar go = g.contiguous();
+  TORCH_CHECK(go.size(0) == (int64_t)sg->v_size && go.size(1) % 2 == 0,
+              "output grad must be [v_size, 2 F]");
+  const int64_t F = go.size(1) / 2;
+  NtsVar gi = torch::empty({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
+  hip_check(nts_hip_spmm_csr_bwd_root(cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(),
+                                      sg->dev_e_w_b(), sg->dev_src_size(), sg->src_size,
+                                      go.data_ptr<float>(), (uint64_t)(2 * F),
+                                      dptr<uint32_t>(sg->src_dst), sg->post_mask, sg->post_mask_ld,
+                                      sg->post_mask_scale, (uint32_t)F, gi.data_ptr<float>(),
+                                      (uint64_t)F),
+            "nts_hip_spmm_csr_bwd_root");
+  return gi;
+}
+
 }  // namespace op
 
 // ---------------------------------------------------------------------------

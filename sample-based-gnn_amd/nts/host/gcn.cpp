@@ -42,6 +42,18 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     TORCH_CHECK(L_GT.dim() == 1, "labels must be int64 [V] (a [V, C] 0/1 label tensor needs "
                                  "multi_label)");
   }
+  if (cfg.root_weight) {
+    TORCH_CHECK(!cfg.gat, "root_weight is not supported with gat (GCN / GraphSAGE layers only)");
+    TORCH_CHECK(!cfg.pd_cache, "root_weight is not supported with pd_cache");
+    TORCH_CHECK(!cfg.sample_gpu, "root_weight is not supported with sample_gpu");
+    TORCH_CHECK(cfg.transform_first != 1,
+                "root_weight is not supported with transform_first = 1 (aggregate-first only)");
+    TORCH_CHECK(cfg.pair_table <= 0, "root_weight is not supported with pair_table > 0");
+    TORCH_CHECK(cfg.cache_rate < 0.0, "root_weight is not supported with cache_rate >= 0");
+    TORCH_CHECK(cfg.fused_gather, "root_weight is not supported with fused_gather = false");
+    TORCH_CHECK(cfg.deterministic_backward,
+                "root_weight needs deterministic_backward (its backward runs over the CSR)");
+  }
   if (cfg.sample_gpu) {
     TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
     TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
@@ -87,7 +99,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // (a table that stays in the Infinity Cache) instead of F_in-wide feature
   // rows, at the price of a GEMM over the src rows instead of the dst rows.
   const bool tf_ok = L >= 2 && !cfg.gat && !fcache && cfg.hip_gemm && cfg.fuse_activation &&
-                     !cfg.pd_cache;
+                     !cfg.pd_cache && !cfg.root_weight;
   if (cfg.transform_first == 1)
     TORCH_CHECK(tf_ok, "transform_first needs >= 2 layers, the MFMA GEMMs with the fused "
                        "activation, no GAT and no feature cache");
@@ -145,9 +157,14 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   sampler = std::make_unique<FastSampler>(graph, train_nids, L, cfg.batch_size, cfg.fanout,
                                           nslots_, csr,
                                           !cfg.gat && cfg.weight_type != WeightType::None,
-                                          cfg.gat);
+                                          cfg.gat || cfg.root_weight);
   sampler->rng_mode = cfg.rng_mode;
   sampler->up_degree = cfg.up_degree;
+  if (cfg.root_weight)  // the inverse of dst_local_id, for every hop with a graph-op backward
+    for (auto* q : sampler->ssgs)
+      for (auto* s : q->sampled_sgs)
+        if (s->has_csr)
+          s->src_dst = torch::empty({std::max<int64_t>(s->s_cap, 1)}, u32_opts(graph->device));
   if (cfg.pipeline && cfg.sampler_cus != 0)
     ss = std::make_unique<NtsStream>(graph->device,
                                      cu_mask_spread(graph->device, std::abs(cfg.sampler_cus), false),
@@ -182,7 +199,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                 "hipEventCreate");
     if (early_)
       pre_y_[i] = row_padded_empty((int64_t)sampler->ssgs[i]->sampled_sgs[L - 1]->v_cap,
-                                   F.size(1), graph->device);
+                                   (cfg.root_weight ? 2 : 1) * F.size(1), graph->device);
     if (early_ && fcache)
       stage_[i] = torch::empty({(int64_t)std::max<uint32_t>(sampler->ssgs[i]->sampled_sgs[L - 1]->s_cap, 1),
                                 (int64_t)fcache->ld},
@@ -256,6 +273,13 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
   sampler->issue_gpu_sample(cfg.batch_size, slot, st,
                             cfg.gat ? WeightType::None : cfg.weight_type);
   sampler->omit_map = nullptr;
+  if (cfg.root_weight)  // the backward's inverse maps, next to the sampling
+    for (auto* s : sampler->ssgs[slot]->sampled_sgs)
+      if (s->src_dst.defined())
+        hip_check(nts_hip_root_inverse_map(st.ctx(), s->dev_dst_local_id(), s->dev_v_size(),
+                                           s->v_cap, s->dev_src_size(), s->s_cap,
+                                           dptr<uint32_t>(s->src_dst)),
+                  "nts_hip_root_inverse_map");
   if (!cfg.multi_label) {  // load_label_gpu for this batch, on the sampling stream next to its
      // subgraph (off the training stream; ordered by ready_[slot] below);
      // multi_label: the loss reads the packed table by the seeds' ids itself
@@ -281,6 +305,13 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
       fcache->aggregate(st.ctx(), s, dptr<uint32_t>(s->sizes), s->v_cap,
                         dptr<uint32_t>(s->sizes) + 2, s->s_cap, stage_[slot].data_ptr<float>(),
                         y.data_ptr<float>(), (uint64_t)y.stride(0));
+    else if (cfg.root_weight)  // [A X | X[destination]] from the table, one launch
+      hip_check(nts_hip_spmm_csc_fwd_root(st.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(),
+                                          dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
+                                          (uint64_t)F.stride(0), s->dev_src(), s->dev_dst(),
+                                          (uint32_t)F.size(1), y.data_ptr<float>(),
+                                          (uint64_t)y.stride(0)),
+                "nts_hip_spmm_csc_fwd_root(early)");
     else
       hip_check(nts_hip_spmm_csc_fwd(st.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(),
                                      dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
@@ -306,7 +337,9 @@ double GCN_SAMPLE_ALLGPU_impl::bottom_bytes(SampledSubgraph* sg, bool fused_map)
 
 void GCN_SAMPLE_ALLGPU_impl::init_nn() {
   for (size_t i = 0; i + 1 < cfg.layer_size.size(); ++i) {
-    P.push_back(new Parameter(cfg.layer_size[i], cfg.layer_size[i + 1], cfg.learn_rate, cfg.beta1,
+    // root_weight: the stacked [W_n; W_s]
+    P.push_back(new Parameter((cfg.root_weight ? 2 : 1) * cfg.layer_size[i], cfg.layer_size[i + 1],
+                              cfg.learn_rate, cfg.beta1,
                               cfg.beta2, cfg.epsilon, cfg.weight_decay, graph->device,
                               cfg.seed + (int64_t)i));
     if (cfg.gat)  // attention vector W_att [2 F_{l+1}, 1] (GAT_SAMPLE_ALL_GPU.hpp:141-147)
@@ -427,7 +460,9 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
       continue;
     }
     if (bottom && cfg.profile) prof.begin(KernelProfiler::BOTTOM_AGG, (hipStream_t)cs->stream());
-    if (cfg.sample_gpu && bottom && cfg.fused_gather)
+    if (cfg.root_weight)
+      Y = ctx.runGraphOp<op::SingleGPURootGraphOp>(bottom ? F : X, sg, hop, cs.get(), bottom);
+    else if (cfg.sample_gpu && bottom && cfg.fused_gather)
       Y = ctx.runGraphOp<op::SingleGPUSampleGraphOp>(F, sg, graph.get(), hop, cs.get(), true,
                                                      fcache.get());
     else if (cfg.sample_gpu)
@@ -754,7 +789,7 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_eval(const std::vector<Verte
   const int L = (int)cfg.fanout.size();
   std::vector<bool> csr(L, cfg.gat);
   FastSampler s(graph, seeds, L, (int)seeds.size(), cfg.fanout, 1, csr,
-                !cfg.gat && cfg.weight_type != WeightType::None, cfg.gat);
+                !cfg.gat && cfg.weight_type != WeightType::None, cfg.gat || cfg.root_weight);
   s.rng_mode = cfg.rng_mode;
   s.up_degree = cfg.up_degree;
   s.batch_seq = batch_seq;
@@ -834,7 +869,7 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
   const WeightType wt = cfg.gat ? WeightType::None : cfg.weight_type;
   std::vector<bool> csr(L, cfg.gat);
   FastSampler s(graph, nids, L, cfg.batch_size, cfg.fanout, 1, csr, wt != WeightType::None,
-                cfg.gat);
+                cfg.gat || cfg.root_weight);
   s.rng_mode = cfg.rng_mode;
   s.up_degree = cfg.up_degree;
   s.batch_seq = eval_seq;
@@ -906,9 +941,12 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
   const nts_graph_dev g = graph->dev();
   hipStream_t st = (hipStream_t)cs->stream();
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+  // root_weight: the aggregation fills the left half of a [V, 2 F] buffer and
+  // the rows themselves are copied into the right half
   auto aggregate = [&](const NtsVar& x, bool relu) {
     NtsVar xr = row_major(x);
-    NtsVar y = row_padded_empty(V, xr.size(1), graph->device);
+    NtsVar y = row_padded_empty(V, (cfg.root_weight ? 2 : 1) * xr.size(1), graph->device);
+    if (cfg.root_weight) y.narrow(1, xr.size(1), xr.size(1)).copy_(xr);
     if (cfg.profile) {
       hipEvent_t a, b;
       TORCH_CHECK(hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess,
@@ -931,7 +969,7 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
     for (int l = 0; l < L; ++l) {
       const bool last = l == L - 1;
       const NtsVar& W = P[l]->W;
-      if (W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
+      if (!cfg.root_weight && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
         NtsVar H = P[l]->forward(X);
         NtsVar Y = aggregate(H, !last);
         X = last && !cfg.multi_label ? Y.log_softmax(1) : Y;

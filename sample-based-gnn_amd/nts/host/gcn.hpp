@@ -33,6 +33,13 @@ struct GCNConfig {
   // nts_hip_linear_bce_*), and evaluate() / evaluate_full() return the
   // micro-F1 of the prediction z > 0.  GCN / GraphSAGE layers only.
   bool multi_label = false;
+  // GraphSAGE root weight (SAGEConv; no reference counterpart): every layer is
+  // X' = act([A X | X_dst] W) with one stacked W = [W_n; W_s] of
+  // [2 layer_size[l], layer_size[l+1]].  The sampler merges the dsts into each
+  // frontier (with the weights of weight_type); aggregate-first only.  Not with
+  // gat, pd_cache, sample_gpu, transform_first = 1, pair_table, cache_rate >= 0
+  // or fused_gather = false.
+  bool root_weight = false;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its

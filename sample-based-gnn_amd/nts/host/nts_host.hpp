@@ -122,6 +122,9 @@ class sampCSC {
   // is_merge_src_dst (GAT): dst d is local src dst_local_id[d]; CSR slot j is
   // CSC edge csr_edge_id[j] (both undefined unless set_merge_src_dst())
   torch::Tensor dst_local_id, csr_edge_id;
+  // root weight: src_dst[s] = the dst whose dst_local_id is s, else
+  // NTS_NOT_CACHED (nts_hip_root_inverse_map, built next to the sampling)
+  torch::Tensor src_dst;
   // PD cache (sampled with an omit map): per dst its cache row or NTS_NOT_CACHED
   torch::Tensor omit_row;
   // transform-first training: this layer's graph-op backward also applies the
@@ -343,6 +346,24 @@ class SingleGPUSampleGraphOp : public SingleGPUAllSampleGraphOp {
  public:
   using SingleGPUAllSampleGraphOp::SingleGPUAllSampleGraphOp;
   NtsVar backward(NtsVar& f_output_grad) override;
+};
+
+// GraphSAGE root weight (no reference counterpart): forward Ycat = [A X |
+// X[dst rows]] in one launch over a merged src/dst layer (dst_local_id; with
+// gather_from_table the self rows are the table's `destination` rows);
+// backward dX = A^T dYcat[:, :F] + dYcat[src_dst, F:] over the CSR and the
+// layer's inverse map.
+class SingleGPURootGraphOp : public ntsGraphOp {
+ public:
+  SingleGPURootGraphOp(SampledSubgraph* subgraphs, int layer, NtsStream* cs,
+                       bool gather_from_table = false);
+  NtsVar forward(NtsVar& f_input) override;
+  NtsVar backward(NtsVar& f_output_grad) override;
+
+  SampledSubgraph* subgraphs;
+  int layer;
+  NtsStream* cuda_stream;
+  bool gather_from_table;
 };
 
 }  // namespace op

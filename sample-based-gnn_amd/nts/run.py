@@ -105,6 +105,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.multi_label and model == "gat":
         raise SystemExit(f"ALGORITHM {info.algorithm}: MULTI_LABEL is not supported with GAT "
                          "(GCN / GraphSAGE algorithms only)")
+    if info.root_weight and (model == "gat" or place is not None):
+        raise SystemExit(f"ALGORITHM {info.algorithm}: ROOT_WEIGHT is not supported with GAT, "
+                         "PD-cache or GCN_SAMPLE_GPU algorithms")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -119,7 +122,7 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         pipeline=info.pipeline_num > 1, up_degree=info.up_degree, gat=model == "gat",
         cache_rate=cache_rate, shuffle=True, pd_cache=pd, pd_rate=info.cache_rate,
         pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu",
-        multi_label=bool(info.multi_label))
+        multi_label=bool(info.multi_label), root_weight=bool(info.root_weight))
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
