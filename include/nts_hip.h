@@ -666,7 +666,7 @@ int nts_hip_linear_bce_train(nts_hip_ctx *ctx, const float *Y, uint64_t ldy, int
                              const uint32_t *index, float *loss, float *dY, float *dW,
                              uint32_t *counts);
 
-/* ---- GraphSAGE root weight (csrc/root.hip; no counterpart in the reference) --
+/* ---- GraphSAGE root weight (csrc/aggregate.hip; no counterpart in the reference) --
  * The graph op of X' = act([A X | X_dst] W), W = [W_n; W_s] stacked on K.
  *
  * Forward, one launch: for every d < *v

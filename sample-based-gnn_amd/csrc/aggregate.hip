@@ -1,5 +1,5 @@
-// Sampled aggregation (CSC gather SpMM, CSR transpose gather, atomic scatter),
-// row/label gathers and the fused Adam step.
+// Sampled aggregation (CSC gather SpMM, CSR transpose gather, atomic scatter,
+// the GraphSAGE root weight's graph op), row/label gathers and the fused Adam step.
 //
 // The aggregation is HBM-bound (~2 flop/B).  Layout: X/Y row-major
 // fp32 [rows, ld]; one wave-group (LPD lanes) per destination row, each lane
@@ -92,7 +92,8 @@ struct Tier {
 constexpr uint32_t kNotCached = 0xFFFFFFFFu;
 constexpr uint32_t kHostBit = 0x80000000u;
 
-// MODE: what the gather computes around the weighted sum (MAP/TIER only with kAggPlain)
+// MODE: what the gather computes around the weighted sum (MAP/TIER only with
+// kAggPlain, MAP also with kAggRootFwd)
 //   kAggPlain: y = A x
 //   kAggAct:   y = dropout(relu(A x), p) — vertexForward's activation in the
 //              epilogue, keep bits keyed exactly like the GEMM epilogue of
@@ -105,7 +106,19 @@ constexpr uint32_t kHostBit = 0x80000000u;
 //   kAggColmax: kAggPlain, and per block the column maxima of |y| over the
 //     block's output rows into row blockIdx.x of ax.cm_out (the f16
 //     pair-table TN GEMM's per-chunk column scales, nts_hip_spmm_csr_bwd_colmax)
-enum { kAggPlain = 0, kAggAct = 1, kAggMask = 2, kAggPostMask = 3, kAggColmax = 4 };
+//   kAggRootFwd: the GraphSAGE root weight's forward (X' = act([A X | X_dst] W)):
+//     y[d, 0:F] = (A x)[d] as kAggPlain, y[d, F:2F] = x[ax.self[d]] (MAP: a
+//     global row, not looked up in map); F a multiple of VEC
+//   kAggRootBwd (COOP): y[s] = mask_s ⊙ scale ((A x[:, 0:F])[s] + x[ax.self[s], F:2F])
+//     with x = dYcat; the self row is added last and skipped where ax.self[s]
+//     is kNotCached, the mask is ax.mx's row s as kAggPostMask's (ax.mx NULL:
+//     none).  Rows above ax.long_row edges are the long ones: the threshold
+//     nts_hip_spmm_csr_bwd takes for the same operands, whose float4 over pitch
+//     padding this mode cannot follow (the right half starts at column F)
+enum {
+  kAggPlain = 0, kAggAct = 1, kAggMask = 2, kAggPostMask = 3, kAggColmax = 4, kAggRootFwd = 5,
+  kAggRootBwd = 6
+};
 struct AggExtra {
   const float* mx = nullptr;
   uint64_t ldm = 0;
@@ -124,6 +137,10 @@ struct AggExtra {
   uint32_t* bits_out = nullptr;
   const uint32_t* bits_in = nullptr;
   uint64_t ldb = 0;
+  // the root modes (appended: the fields above keep their kernel-argument
+  // offsets): the self row of every output row, and kAggRootBwd's long-row threshold
+  const uint32_t* self = nullptr;
+  uint32_t long_row = 0;
 };
 
 // Mask bits of a float4 row on LPD >= 32 lanes (one chunk of NCH float4 a
@@ -142,9 +159,6 @@ __device__ __forceinline__ float vcomp(const typename VT<VEC>::T& v, int q) {
 
 // acc[c] += sum over the edges [beg, end) in edge order of w[e] * row(e)[col],
 // col = c0 + sl + c * LPD (one LPD-lane group, see k_spmm_gather)
-// pre: the row's first chunk of edge ids / weights was loaded by the caller
-// (lane sl: entry beg + sl, raw id before MAP/TIER) — one row ahead, so that
-// the chain per row is the row loads alone
 template <int VEC, int LPD, int NCH, bool MAP, int U, bool TIER, int MODE>
 __device__ __forceinline__ void gather_edges(typename VT<VEC>::T (&acc)[NCH], uint32_t beg,
                                              uint32_t end, uint32_t c0, int sl,
@@ -152,9 +166,7 @@ __device__ __forceinline__ void gather_edges(typename VT<VEC>::T (&acc)[NCH], ui
                                              const float* __restrict__ w,
                                              const float* __restrict__ x, uint64_t ldx,
                                              const uint32_t* __restrict__ map, uint32_t nv,
-                                             const Tier& tier, const AggExtra& ax,
-                                             bool pre = false, uint32_t pre_r = 0,
-                                             float pre_w = 0.f) {
+                                             const Tier& tier, const AggExtra& ax) {
   using V = VT<VEC>;
   using T = typename V::T;
   for (uint32_t cb = beg; cb < end; cb += LPD) {
@@ -162,13 +174,8 @@ __device__ __forceinline__ void gather_edges(typename VT<VEC>::T (&acc)[NCH], ui
     uint32_t my_r = 0;
     float my_w = 0.f;
     if ((uint32_t)sl < ne) {  // streamed once: do not keep in cache
-      if (pre && cb == beg) {
-        my_r = pre_r;
-        my_w = pre_w;
-      } else {
-        my_r = __builtin_nontemporal_load(idx + cb + sl);
-        my_w = w ? __builtin_nontemporal_load(w + cb + sl) : 1.0f;
-      }
+      my_r = __builtin_nontemporal_load(idx + cb + sl);
+      my_w = w ? __builtin_nontemporal_load(w + cb + sl) : 1.0f;
       const uint32_t loc = my_r;
       if (MAP) my_r = map[my_r];
       if (TIER) {
@@ -224,8 +231,73 @@ __device__ __forceinline__ void gather_edges(typename VT<VEC>::T (&acc)[NCH], ui
   }
 }
 
-// epilogue of one output row: activation (kAggAct) and the store
-template <int VEC, int LPD, int NCH, int MODE>
+// The activation mask of output row d over a lane's NCH vectors (kAggPostMask,
+// kAggRootBwd), dZ = dX ⊙ [X > 0] · scale: the floats of ax.mx's row d, or
+// (BITS: float4 rows on LPD >= 32 lanes, where ax.bits_in is set) its keep bits
+template <int VEC, int LPD, int NCH, bool BITS>
+struct RowMask {
+  static constexpr bool kBits = BITS && VEC == 4 && LPD >= 32;
+  typename VT<VEC>::T m[NCH];
+  uint4 b[kBits ? NCH : 1];
+  bool bits;  // (uniform)
+};
+template <int VEC, int LPD, int NCH, bool BITS>
+__device__ __forceinline__ void load_mask(RowMask<VEC, LPD, NCH, BITS>& rm, uint32_t d,
+                                          uint32_t c0, int sl, uint32_t nv, const AggExtra& ax) {
+  using T = typename VT<VEC>::T;
+  rm.bits = false;
+  if constexpr (RowMask<VEC, LPD, NCH, BITS>::kBits) {
+    if (ax.bits_in) {
+      rm.bits = true;
+      const uint4* brow = reinterpret_cast<const uint4*>(ax.bits_in + (uint64_t)d * ax.ldb) +
+                          (LPD == 64 ? (sl >> 5) : 0) * NCH;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) rm.b[c] = brow[c];
+    }
+  }
+  if (!rm.bits) {
+    const T* mrow = reinterpret_cast<const T*>(ax.mx + (uint64_t)d * ax.ldm);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const uint32_t col = c0 + sl + c * LPD;
+      rm.m[c] = col < nv ? mrow[col] : VT<VEC>::zero();
+    }
+  }
+}
+template <int VEC>
+__device__ __forceinline__ void mask_vec(typename VT<VEC>::T& a, const typename VT<VEC>::T& m,
+                                         float scale) {
+#pragma unroll
+  for (int q = 0; q < VEC; ++q) {
+    float& v = vcomp<VEC>(a, q);
+    v = vcomp<VEC>(m, q) > 0.f ? v * scale : 0.f;
+  }
+}
+template <int VEC, int LPD, int NCH, bool BITS>
+__device__ __forceinline__ void apply_mask(typename VT<VEC>::T (&acc)[NCH],
+                                           const RowMask<VEC, LPD, NCH, BITS>& rm, int sl,
+                                           float scale) {
+  if constexpr (RowMask<VEC, LPD, NCH, BITS>::kBits) {
+    if (rm.bits) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const uint32_t wq[4] = {rm.b[c].x, rm.b[c].y, rm.b[c].z, rm.b[c].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float& v = vcomp<VEC>(acc[c], q);
+          v = ((wq[q] >> (sl & 31)) & 1u) ? v * scale : 0.f;
+        }
+      }
+      return;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) mask_vec<VEC>(acc[c], rm.m[c], scale);
+}
+
+// epilogue of one output row: activation (kAggAct), the mask of a long row
+// (kAggPostMask) and the store, non-temporal or (NT = false) plain
+template <int VEC, int LPD, int NCH, int MODE, bool NT = true>
 __device__ __forceinline__ void store_row(typename VT<VEC>::T (&acc)[NCH], uint32_t d, uint32_t c0,
                                           int sl, uint32_t nv, uint32_t last_valid,
                                           float* __restrict__ y, uint64_t ldy, const AggExtra& ax) {
@@ -265,38 +337,25 @@ __device__ __forceinline__ void store_row(typename VT<VEC>::T (&acc)[NCH], uint3
       }
     }
   }
-  if constexpr (MODE == kAggPostMask) {  // dZ = dX ⊙ [X > 0] · scale, X row d
-    bool bits = false;
-    if constexpr (VEC == 4 && LPD >= 32) {
-      if (ax.bits_in) {  // (uniform) the keep mask as bits
-        bits = true;
-        const uint4* brow = reinterpret_cast<const uint4*>(ax.bits_in + (uint64_t)d * ax.ldb) +
-                            (LPD == 64 ? (sl >> 5) : 0) * NCH;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const uint4 b4 = brow[c];
-          const uint32_t wq[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float& v = vcomp<VEC>(acc[c], q);
-            v = ((wq[q] >> (sl & 31)) & 1u) ? v * ax.scale : 0.f;
-          }
-        }
+  if constexpr (MODE == kAggPostMask) {
+    // a long row, masked after its LDS sum.  The float mask is loaded vector
+    // by vector as it is applied: nothing overlaps the load here, and the
+    // whole row preloaded (load_mask) costs registers (occupancy 3 -> 2 at
+    // four float4 chunks a lane)
+    RowMask<VEC, LPD, NCH, true> rm;
+    rm.bits = false;
+    if constexpr (RowMask<VEC, LPD, NCH, true>::kBits) {
+      if (ax.bits_in) {
+        load_mask(rm, d, c0, sl, nv, ax);
+        apply_mask(acc, rm, sl, ax.scale);
       }
     }
-    if (!bits) {
+    if (!rm.bits) {
       const T* mrow = reinterpret_cast<const T*>(ax.mx + (uint64_t)d * ax.ldm);
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const uint32_t col = c0 + sl + c * LPD;
-        if (col < nv) {
-          const T m = mrow[col];
-#pragma unroll
-          for (int q = 0; q < VEC; ++q) {
-            float& v = vcomp<VEC>(acc[c], q);
-            v = vcomp<VEC>(m, q) > 0.f ? v * ax.scale : 0.f;
-          }
-        }
+        if (col < nv) mask_vec<VEC>(acc[c], mrow[col], ax.scale);
       }
     }
   }
@@ -305,7 +364,8 @@ __device__ __forceinline__ void store_row(typename VT<VEC>::T (&acc)[NCH], uint3
   for (int c = 0; c < NCH; ++c) {  // output rows are not re-read here: keep them
     const uint32_t col = c0 + sl + c * LPD;  // out of the cache that serves x rows
     if (col + 1 < nv || (col + 1 == nv && last_valid == (uint32_t)VEC)) {
-      V::st_nt(yrow + col, acc[c]);
+      if constexpr (NT) V::st_nt(yrow + col, acc[c]);
+      else yrow[col] = acc[c];
     } else if (col + 1 == nv) {  // partial last vector: only the valid floats
       V::st_part(yrow + col, acc[c], last_valid);
     }
@@ -322,33 +382,37 @@ __device__ __forceinline__ void store_row(typename VT<VEC>::T (&acc)[NCH], uint3
 // (bit-identical to MiniBatchFuseOp::backward's), longer rows are summed as
 // GPB in-order pieces.  A group takes at most kCoopRows rows (grid >=
 // ceil(n_cap / (GPB kCoopRows))): the block's long rows fit its list.
-template <int U>
-constexpr uint32_t kLongRow() { return 4 * U; }
+constexpr uint32_t kLongRow(int u) { return 4 * u; }
 constexpr uint32_t kCoopRows = 16;
 
-// Row software pipeline of k_spmm_gather: 0 none, 1 the next row's offsets, 2 the offsets two rows ahead
-// and the first id/weight chunk one row ahead; and the waves-per-SIMD floor of
-// its single-chunk instances (0: the compiler's choice).  Measured at C2 size
-// (scripts/micro_agg.py, r04): bottom fwd / CSR bwd 103.7 / 121.7 us with 0,
-// 105.9 / 130.5 with 1, 102.3 / 130.6 with 2, 114.4 / 152.1 with 2 and a
-// floor of 6 waves (spills) — the prefetch registers cost a wave per SIMD
-// (occupancy 6 -> 5) and the gather needs the waves more than the shorter
-// chain, so 0 stays
-constexpr int kAggPf = 0;
-constexpr int kAggWpe = 1;  // (amdgpu_waves_per_eu minimum: 1 = no floor)
-
+// Each row's loads run off -> ids -> rows with nothing loaded ahead.  A row
+// software pipeline (1: the next row's offsets; 2: the offsets two rows ahead
+// and the first id / weight chunk one row ahead) measured, at C2 size with
+// scripts/micro_agg.py, bottom fwd / CSR bwd 105.9 / 130.5 us (1) and
+// 102.3 / 130.6 (2) against 103.7 / 121.7 without, and 114.4 / 152.1 with 2
+// under a floor of 6 waves per SIMD (spills): the prefetch registers cost a
+// wave per SIMD (occupancy 6 -> 5) and the gather needs the waves more than
+// the shorter chain.
 template <int VEC, int LPD, int NCH, bool MAP, int U, bool TIER, int MODE = kAggPlain,
           bool COOP = false>
-__global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(NCH == 1 ? kAggWpe : 1))) void k_spmm_gather(
+__global__ __launch_bounds__(kAggThreads) void k_spmm_gather(
     const uint32_t* __restrict__ off, const uint32_t* __restrict__ idx,
     const float* __restrict__ w, const uint32_t* n_dev, uint32_t n_cap,
     const float* __restrict__ x, uint64_t ldx, const uint32_t* __restrict__ map, uint32_t nv,
     float* __restrict__ y, uint64_t ldy, uint32_t last_valid, Tier tier, AggExtra ax) {
   using V = VT<VEC>;
   using T = typename V::T;
-  static_assert(MODE == kAggPlain || (!MAP && !TIER), "activation modes gather local rows only");
   constexpr bool CM = MODE == kAggColmax;
-  constexpr int EM = CM ? kAggPlain : MODE;  // the gather and store proper
+  constexpr bool ROOT = MODE == kAggRootFwd || MODE == kAggRootBwd;
+  constexpr bool MASK = MODE == kAggPostMask || MODE == kAggRootBwd;  // of the output row
+  static_assert(MODE == kAggPlain || (!TIER && (!MAP || MODE == kAggRootFwd)),
+                "activation and backward modes gather local rows only");
+  static_assert(MODE != kAggRootBwd || COOP, "the root backward follows the CSR backward's split");
+  constexpr int EM = CM || ROOT ? kAggPlain : MODE;  // the gather and store proper
+  // (the root modes keep the plain stores their timings in DESIGN §8g were
+  // taken with; non-temporal ones have not been measured for them)
+  constexpr bool NT = !ROOT;
+  const uint32_t long_row = MODE == kAggRootBwd ? ax.long_row : kLongRow(U);
   const uint32_t n = n_dev ? min(*n_dev, n_cap) : n_cap;
   constexpr int GPB = kAggThreads / LPD;
   const int grp = threadIdx.x / LPD, sl = threadIdx.x % LPD;
@@ -379,63 +443,58 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(NCH
           atomicMax(&smax[col], __float_as_uint(fabsf(vcomp<VEC>(acc[c], q) * rsd)));
       }
   };
-  // software pipeline over the group's rows: the offsets two rows ahead and
-  // the first chunk of edge ids / weights one row ahead are loaded while this
-  // row is gathered (the chain per row off -> ids -> rows becomes the rows)
-  const uint32_t stride = gridDim.x * GPB;
-  auto first_chunk = [&](uint32_t b, uint32_t e, uint32_t& r, float& wt) {
-    r = 0;
-    wt = 0.f;
-    if ((uint32_t)sl < e - b) {
-      r = __builtin_nontemporal_load(idx + b + sl);
-      wt = w ? __builtin_nontemporal_load(w + b + sl) : 1.0f;
+  // The rows known before the edges are — the output row's mask (MASK) and
+  // the root modes' self row — are loaded ahead of the gather, so that their
+  // latency overlaps it instead of following it
+  struct Side {
+    T self[ROOT ? NCH : 1];
+    RowMask<VEC, LPD, NCH, MODE == kAggPostMask> rm;
+  };
+  auto load_side = [&](Side& sd, uint32_t d, uint32_t c0) {
+    if constexpr (ROOT) {
+      // forward: x[self] (a global row under MAP); backward: x[self, F:2F],
+      // F = nv VEC, zeros where the row has no self term
+      uint32_t sr = ax.self[d];
+      const bool has = MODE == kAggRootFwd || sr != kNotCached;
+      if (!has) sr = 0;
+      const T* srow =
+          reinterpret_cast<const T*>(x + (uint64_t)sr * ldx) + (MODE == kAggRootBwd ? nv : 0);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const uint32_t col = c0 + sl + c * LPD;
+        sd.self[c] = (has && col < nv) ? srow[col] : V::zero();
+      }
+    }
+    if constexpr (MASK) {
+      if (MODE == kAggPostMask || ax.mx) load_mask(sd.rm, d, c0, sl, nv, ax);
     }
   };
-  uint32_t d = blockIdx.x * GPB + grp;
-  uint32_t beg = 0, end = 0, beg1 = 0, end1 = 0, pr = 0;
-  float pw = 0.f;
-  if (kAggPf >= 1 && d < n) {
-    beg = off[d];
-    end = off[d + 1];
-  }
-  if (kAggPf >= 2 && d + stride < n) {
-    beg1 = off[d + stride];
-    end1 = off[d + stride + 1];
-  }
-  if (kAggPf >= 2) first_chunk(beg, end, pr, pw);
-  for (; d < n; d += stride) {
-    uint32_t cbeg, cend, cpr = 0;
-    float cpw = 0.f;
-    if constexpr (kAggPf == 0) {
-      cbeg = off[d];
-      cend = off[d + 1];
-    } else if constexpr (kAggPf == 1) {
-      cbeg = beg;
-      cend = end;
-      if (d + stride < n) {
-        beg = off[d + stride];
-        end = off[d + stride + 1];
-      }
-    } else {
-      uint32_t beg2 = 0, end2 = 0, pr1, dn2 = d + 2 * stride;
-      float pw1;
-      if (dn2 < n) {
-        beg2 = off[dn2];
-        end2 = off[dn2 + 1];
-      }
-      first_chunk(beg1, end1, pr1, pw1);
-      cbeg = beg;
-      cend = end;
-      cpr = pr;
-      cpw = pw;
-      beg = beg1;
-      end = end1;
-      beg1 = beg2;
-      end1 = end2;
-      pr = pr1;
-      pw = pw1;
+  // one output row after its sum: the self term (one more add, last), the
+  // mask, the store, the forward's self copy into columns [F, 2F), the maxima
+  // (long: a long row's kAggPostMask is store_row's, loaded after the sum)
+  auto finish = [&](T (&acc)[NCH], Side& sd, uint32_t d, uint32_t c0, auto long_row_tag) {
+    constexpr bool LATE = MODE == kAggPostMask && decltype(long_row_tag)::value;
+    if constexpr (MODE == kAggRootBwd) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int q = 0; q < VEC; ++q)
+          vcomp<VEC>(acc[c], q) = vcomp<VEC>(acc[c], q) + vcomp<VEC>(sd.self[c], q);
     }
-    if (COOP && cend - cbeg > kLongRow<U>()) {  // summed by the whole block below
+    if constexpr (MASK && !LATE) {
+      if (MODE == kAggPostMask || ax.mx) apply_mask(acc, sd.rm, sl, ax.scale);
+    }
+    store_row<VEC, LPD, NCH, LATE ? kAggPostMask : EM == kAggPostMask ? kAggPlain : EM, NT>(
+        acc, d, c0, sl, nv, last_valid, y, ldy, ax);
+    if constexpr (MODE == kAggRootFwd)
+      store_row<VEC, LPD, NCH, kAggPlain, NT>(sd.self, d, c0, sl, nv, last_valid,
+                                              y + (uint64_t)nv * VEC, ldy, ax);
+    if constexpr (CM) colmax_row(acc, c0, d);
+  };
+  const uint32_t stride = gridDim.x * GPB;
+  for (uint32_t d = blockIdx.x * GPB + grp; d < n; d += stride) {
+    const uint32_t beg = off[d], end = off[d + 1];
+    if (COOP && end - beg > long_row) {  // summed by the whole block below
       if (sl == 0) long_rows[atomicAdd(&n_long, 1u)] = d;
       continue;
     }
@@ -443,61 +502,11 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(NCH
       T acc[NCH];
 #pragma unroll
       for (int c = 0; c < NCH; ++c) acc[c] = V::zero();
-      // kAggPostMask: the output row's mask is known before the edges are —
-      // load it first, so its latency overlaps the gather instead of following it
-      T pm[MODE == kAggPostMask ? NCH : 1];
-      uint4 pb[MODE == kAggPostMask && VEC == 4 && LPD >= 32 ? NCH : 1];
-      if constexpr (MODE == kAggPostMask) {
-        bool bits = false;
-        if constexpr (VEC == 4 && LPD >= 32) {
-          if (ax.bits_in) {  // (uniform) the keep mask as bits
-            bits = true;
-            const uint4* brow = reinterpret_cast<const uint4*>(ax.bits_in + (uint64_t)d * ax.ldb) +
-                                (LPD == 64 ? (sl >> 5) : 0) * NCH;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) pb[c] = brow[c];
-          }
-        }
-        if (!bits) {
-          const T* mrow = reinterpret_cast<const T*>(ax.mx + (uint64_t)d * ax.ldm);
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) {
-            const uint32_t col = c0 + sl + c * LPD;
-            pm[c] = col < nv ? mrow[col] : V::zero();
-          }
-        }
-      }
-      gather_edges<VEC, LPD, NCH, MAP, U, TIER, EM>(acc, cbeg, cend, c0, sl, idx, w, x, ldx, map,
-                                                      nv, tier, ax, kAggPf >= 2, cpr, cpw);
-      if constexpr (MODE == kAggPostMask) {  // same arithmetic as store_row's
-        bool bits = false;
-        if constexpr (VEC == 4 && LPD >= 32) {
-          if (ax.bits_in) {
-            bits = true;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) {
-              const uint32_t wq[4] = {pb[c].x, pb[c].y, pb[c].z, pb[c].w};
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                float& v = vcomp<VEC>(acc[c], q);
-                v = ((wq[q] >> (sl & 31)) & 1u) ? v * ax.scale : 0.f;
-              }
-            }
-          }
-        }
-        if (!bits) {
-#pragma unroll
-          for (int c = 0; c < NCH; ++c)
-#pragma unroll
-            for (int q = 0; q < VEC; ++q) {
-              float& v = vcomp<VEC>(acc[c], q);
-              v = vcomp<VEC>(pm[c], q) > 0.f ? v * ax.scale : 0.f;
-            }
-        }
-      }
-      store_row<VEC, LPD, NCH, MODE == kAggPostMask ? kAggPlain : EM>(acc, d, c0, sl, nv,
-                                                                      last_valid, y, ldy, ax);
-      if constexpr (CM) colmax_row(acc, c0, d);
+      Side sd;
+      load_side(sd, d, c0);
+      gather_edges<VEC, LPD, NCH, MAP, U, TIER, EM>(acc, beg, end, c0, sl, idx, w, x, ldx, map, nv,
+                                                    tier, ax);
+      finish(acc, sd, d, c0, std::false_type{});
     }
   }
   if constexpr (COOP) {
@@ -513,6 +522,10 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(NCH
         T acc[NCH];
 #pragma unroll
         for (int c = 0; c < NCH; ++c) acc[c] = V::zero();
+        Side sd;
+        if constexpr (ROOT) {
+          if (grp == 0) load_side(sd, d, c0);
+        }
         gather_edges<VEC, LPD, NCH, MAP, U, TIER, EM>(acc, pb, pe, c0, sl, idx, w, x, ldx, map,
                                                         nv, tier, ax);
 #pragma unroll
@@ -529,8 +542,8 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(NCH
             }
             acc[c] = s;
           }
-          store_row<VEC, LPD, NCH, EM>(acc, d, c0, sl, nv, last_valid, y, ldy, ax);
-          if constexpr (CM) colmax_row(acc, c0, d);
+          // (kAggPostMask: a long row's mask is loaded after its sum)
+          finish(acc, sd, d, c0, std::true_type{});
         }
         __syncthreads();
       }
@@ -631,6 +644,25 @@ __global__ void k_gather_labels(const int64_t* __restrict__ labels,
     out[i] = labels[index[i]];
 }
 
+// src_dst[s] = the d with dst_local_id[d] == s, or kNotCached (the root
+// backward's self index): fill, then scatter
+__global__ void k_root_fill(uint32_t* __restrict__ out, const uint32_t* __restrict__ n_dev,
+                            uint32_t n_cap) {
+  const uint32_t n = min(*n_dev, n_cap);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = kNotCached;
+}
+// dst_local_id is one-to-one: every slot has at most one writer
+__global__ void k_root_scatter(uint32_t* __restrict__ out, const uint32_t* __restrict__ dst_local,
+                               const uint32_t* __restrict__ v_dev, uint32_t v_cap,
+                               const uint32_t* __restrict__ s_dev, uint32_t s_cap) {
+  const uint32_t v = min(*v_dev, v_cap), s = min(*s_dev, s_cap);
+  for (uint32_t d = blockIdx.x * blockDim.x + threadIdx.x; d < v; d += gridDim.x * blockDim.x) {
+    const uint32_t loc = dst_local[d];
+    if (loc < s) out[loc] = d;
+  }
+}
+
 // Adam, element-wise in the exact operation order of the reference's torch
 // expressions (core/NtsScheduler.hpp:863-880 and :937-945).
 __global__ void k_adam(float* __restrict__ W, const float* __restrict__ G, float* __restrict__ M,
@@ -666,11 +698,24 @@ __global__ void k_adam(float* __restrict__ W, const float* __restrict__ G, float
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
-static int pick_vec(uint32_t F, uint64_t ld1, uint64_t ld2, const void* p1, const void* p2) {
-  auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p % a) == 0; };
-  if (F % 4 == 0 && ld1 % 4 == 0 && ld2 % 4 == 0 && al(p1, 16) && al(p2, 16)) return 4;
-  if (F % 2 == 0 && ld1 % 2 == 0 && ld2 % 2 == 0 && al(p1, 8) && al(p2, 8)) return 2;
-  return 1;
+// The widest vector (4, 2 or 1 floats) the rows of these operands allow: F a
+// multiple of it and every row start aligned to it (a NULL operand is absent).
+// pad: rows padded to a 16-byte multiple (the 128-byte feature / output pitch)
+// take float4 whatever F is, the partial last vector reading pitch padding
+// and storing only its valid floats.
+struct Rows {
+  const void* p;
+  uint64_t ld;  // pitch in floats
+};
+static int row_vec(uint32_t F, std::initializer_list<Rows> ops, bool pad = false) {
+  auto fits = [&](uint32_t cols, int vec) {
+    bool ok = cols % vec == 0;
+    for (const Rows& r : ops)
+      ok = ok && (!r.p || (cols <= r.ld && r.ld % vec == 0 && (uintptr_t)r.p % (4 * vec) == 0));
+    return ok;
+  };
+  if (pad && fits((F + 3) / 4 * 4, 4)) return 4;
+  return fits(F, 4) ? 4 : fits(F, 2) ? 2 : 1;
 }
 
 struct Shape {
@@ -688,21 +733,10 @@ static Shape pick_shape(uint32_t nv) {
   return {64, (int)std::min<uint32_t>(nch, 8)};
 }
 
-// the vector width launch_gather picks for a local-row gather (no tier, no
-// mask operand): rows padded to a 16-byte multiple take float4 loads, the
-// partial last vector reading pitch padding and storing only its valid floats
-static int plain_vec(uint32_t F, uint64_t ldx, uint64_t ldy, const void* x, const void* y) {
-  int vec = pick_vec(F, ldx, ldy, x, y);
-  const uint32_t F4 = (F + 3) / 4 * 4;
-  if (vec < 4 && F4 <= ldx && F4 <= ldy && ldx % 4 == 0 && ldy % 4 == 0 &&
-      (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0)
-    vec = 4;
-  return vec;
-}
-
 constexpr int gather_u(int floats_per_lane) {
   return floats_per_lane <= 4 ? 8 : floats_per_lane <= 12 ? 5 : 4;
 }
+constexpr uint32_t kGatherGridCap = 1u << 24;
 
 template <int VEC, bool MAP, bool TIER, int MODE, bool COOP>
 static int launch_gather_vec(hipStream_t st, uint32_t grid, uint32_t last_valid, Shape s,
@@ -744,36 +778,31 @@ static int launch_gather(hipStream_t st, const uint32_t* off, const uint32_t* id
                          uint64_t ldx, const uint32_t* map, uint32_t F, float* y, uint64_t ldy,
                          Tier tier = Tier{nullptr, nullptr, 0, 0}, AggExtra ax = AggExtra(),
                          uint32_t expect_grid = 0) {
-  int vec = pick_vec(F, ldx, ldy, x, y);
-  if (TIER) vec = std::min(vec, pick_vec(F, tier.ldh, ldx, tier.host, x));
-  if (MODE == kAggMask || (MODE == kAggPostMask && !ax.bits_in))
-    vec = std::min(vec, pick_vec(F, ax.ldm, ldx, ax.mx, x));
-  // rows padded to a 16-byte multiple (the 128-byte feature / output pitch):
-  // float4 loads, the partial last vector reads pitch padding and stores only
-  // its valid floats
-  const uint32_t F4 = (F + 3) / 4 * 4;
-  if ((MODE == kAggPlain || MODE == kAggColmax) && vec < 4 && F4 <= ldx && F4 <= ldy && ldx % 4 == 0 && ldy % 4 == 0 &&
-      (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 &&
-      (!TIER || (F4 <= tier.ldh && tier.ldh % 4 == 0 && (uintptr_t)tier.host % 16 == 0)))
-    vec = 4;
+  // (the modes that mask, activate or place a second half at column F keep
+  // to whole vectors)
+  const bool pad = MODE == kAggPlain || MODE == kAggColmax;
+  const int vec = row_vec(F, {{x, ldx}, {y, ldy}, {TIER ? tier.host : nullptr, tier.ldh},
+                              {ax.bits_in ? nullptr : ax.mx, ax.ldm}}, pad);
   const uint32_t nv = (F + vec - 1) / vec;
   const uint32_t last_valid = F - (nv - 1) * vec;
-  const Shape s = pick_shape(nv);
+  Shape s = pick_shape(nv);
+  if (MODE == kAggRootBwd) {
+    // the lane-group shape and the long-row threshold nts_hip_spmm_csr_bwd
+    // takes for the same operands, so that every row is summed in its pieces;
+    // where that call's vector is wider than this one the row takes more c0 rounds
+    const int plain = row_vec(F, {{x, ldx}, {y, ldy}}, true);
+    s = pick_shape((F + plain - 1) / plain);
+    ax.long_row = kLongRow(gather_u(plain * s.nch));
+  }
   const uint32_t gpb = kAggThreads / s.lpd;
-  // one destination per lane group: every row's dependent loads (offsets ->
-  // ids -> rows) are in flight at once; a grid-stride cap
-  // serialises rows per group and measured slower (C2: 1.069 vs 1.097 ms per
-  // step at a 4096-block cap; the narrow CSR backward 50 -> ~25 us)
-  constexpr uint32_t cap = 1u << 24;
-  // the post-mask CSR gather (the hop above a transform-first bottom layer,
-  // ~2 edges per row at C2) with a few rows per group instead of one
-  // measured 44.7 / 44.6 / 51.7 us at 4096 / 8192 / 2048 blocks against 44.9
-  // at one row per group — bound by its bytes, not by block lifetimes: no cap
-  constexpr uint32_t pm_cap = 1u << 24;
-  // COOP: at most kCoopRows rows per lane group (the colmax parts: one)
-  const uint32_t grid =
-      std::max(1u, COOP ? std::max(ceil_div(n_cap, gpb * kCoopRows), std::min(ceil_div(n_cap, gpb), pm_cap))
-                        : std::min(ceil_div(n_cap, gpb), cap));
+  // One destination per lane group, every row's dependent loads (offsets ->
+  // ids -> rows) in flight at once.  Fewer blocks with several rows per group
+  // measured slower or no faster (C2: 1.069 vs 1.097 ms per step at 4096
+  // blocks, the narrow CSR backward 50 -> ~25 us; the post-mask CSR gather
+  // 44.7 / 44.6 / 51.7 us at 4096 / 8192 / 2048 blocks against 44.9), so the
+  // cap only bounds the grid.  COOP: at most kCoopRows rows per lane group.
+  const uint32_t grid = std::max({1u, std::min(ceil_div(n_cap, gpb), kGatherGridCap),
+                                  COOP ? ceil_div(n_cap, gpb * kCoopRows) : 0u});
   // kAggColmax: the per-block buffer was sized for this grid
   NTS_CHECK_ARG(expect_grid == 0 || expect_grid == grid, "aggregation grid != the sized one");
   if (vec == 4)
@@ -843,7 +872,7 @@ int nts_hip_spmm_csr_bwd_colmax(nts_hip_ctx* ctx, const uint32_t* row_offset,
   if (s_cap == 0 || feature_size == 0) return NTS_OK;
   // the parts follow the COOP grid (one output row per lane group): the
   // float4 row shape nts_hip_csr_bwd_colmax_rows_per_part assumes
-  NTS_CHECK_ARG(plain_vec(feature_size, ld_gout, ld_gin, g_out, g_in) == 4,
+  NTS_CHECK_ARG(row_vec(feature_size, {{g_out, ld_gout}, {g_in, ld_gin}}, true) == 4,
                 "column maxima: 16-byte aligned rows with ld % 4 == 0");
   const uint32_t rpp = nts_hip_csr_bwd_colmax_rows_per_part(feature_size);
   NTS_HIP_TRY(hipSetDevice(ctx->device));
@@ -935,7 +964,7 @@ int nts_hip_spmm_csc_fwd_act_bits(nts_hip_ctx* ctx, const uint32_t* column_offse
   NTS_CHECK_ARG(p >= 0.f && p <= 1.f, "dropout probability must be in [0, 1]");
   const uint32_t words = nts_hip_act_bits_words(feature_size);
   if (words == 0) return NTS_ERR_UNSUPPORTED;
-  NTS_CHECK_ARG(pick_vec(feature_size, ldx, ldy, x, y) == 4 && (uintptr_t)mask_bits % 16 == 0,
+  NTS_CHECK_ARG(row_vec(feature_size, {{x, ldx}, {y, ldy}}) == 4 && (uintptr_t)mask_bits % 16 == 0,
                 "mask bits: 16-byte aligned rows with ld % 4 == 0");
   if (v_cap == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
@@ -962,7 +991,7 @@ int nts_hip_spmm_csr_bwd_postmask_bits(nts_hip_ctx* ctx, const uint32_t* row_off
                 "leading dimension < feature_size");
   const uint32_t words = nts_hip_act_bits_words(feature_size);
   if (words == 0) return NTS_ERR_UNSUPPORTED;
-  NTS_CHECK_ARG(pick_vec(feature_size, ld_gout, ld_gin, g_out, g_in) == 4 &&
+  NTS_CHECK_ARG(row_vec(feature_size, {{g_out, ld_gout}, {g_in, ld_gin}}) == 4 &&
                     (uintptr_t)mask_bits % 16 == 0,
                 "mask bits: 16-byte aligned rows with ld % 4 == 0");
   if (s_cap == 0) return NTS_OK;
@@ -977,6 +1006,70 @@ int nts_hip_spmm_csr_bwd_postmask_bits(nts_hip_ctx* ctx, const uint32_t* row_off
                                                          Tier{nullptr, nullptr, 0, 0}, ax);
 }
 
+int nts_hip_spmm_csc_fwd_root(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                              const uint32_t* row_indices, const float* weight, const uint32_t* v,
+                              uint32_t v_cap, const float* x, uint64_t ldx,
+                              const uint32_t* x_row_map, const uint32_t* self_index,
+                              uint32_t feature_size, float* ycat, uint64_t ld_ycat) {
+  NTS_CHECK_ARG(ctx && column_offset && row_indices && v && x && self_index && ycat,
+                "NULL argument");
+  NTS_CHECK_ARG(feature_size > 0, "feature_size is 0");
+  NTS_CHECK_ARG(ldx >= feature_size, "leading dimension < feature_size");
+  NTS_CHECK_ARG(ld_ycat >= 2 * (uint64_t)feature_size, "ld_ycat < 2 feature_size");
+  if (v_cap == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  AggExtra ax;
+  ax.self = self_index;
+  if (x_row_map)
+    return launch_gather<true, false, kAggRootFwd>(ctx->stream, column_offset, row_indices, weight,
+                                                   v, v_cap, x, ldx, x_row_map, feature_size, ycat,
+                                                   ld_ycat, Tier{nullptr, nullptr, 0, 0}, ax);
+  return launch_gather<false, false, kAggRootFwd>(ctx->stream, column_offset, row_indices, weight,
+                                                  v, v_cap, x, ldx, nullptr, feature_size, ycat,
+                                                  ld_ycat, Tier{nullptr, nullptr, 0, 0}, ax);
+}
+
+int nts_hip_root_inverse_map(nts_hip_ctx* ctx, const uint32_t* dst_local_id, const uint32_t* v,
+                             uint32_t v_cap, const uint32_t* s, uint32_t s_cap,
+                             uint32_t* src_dst) {
+  NTS_CHECK_ARG(ctx && dst_local_id && v && s && src_dst, "NULL argument");
+  if (s_cap == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_root_fill, dim3(std::min(ceil_div(s_cap, 256), kMaxGrid)), dim3(256), 0,
+                     ctx->stream, src_dst, s, s_cap);
+  NTS_LAUNCH_CHECK();
+  if (v_cap == 0) return NTS_OK;
+  hipLaunchKernelGGL(k_root_scatter, dim3(std::min(ceil_div(v_cap, 256), kMaxGrid)), dim3(256), 0,
+                     ctx->stream, src_dst, dst_local_id, v, v_cap, s, s_cap);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
+int nts_hip_spmm_csr_bwd_root(nts_hip_ctx* ctx, const uint32_t* row_offset,
+                              const uint32_t* column_indices, const float* weight_backward,
+                              const uint32_t* s, uint32_t s_cap, const float* g_ycat,
+                              uint64_t ld_g, const uint32_t* src_dst, const float* x_act,
+                              uint64_t ld_act, float scale, uint32_t feature_size, float* g_in,
+                              uint64_t ld_gin) {
+  NTS_CHECK_ARG(ctx && row_offset && column_indices && s && g_ycat && src_dst && g_in,
+                "NULL argument");
+  NTS_CHECK_ARG(feature_size > 0, "feature_size is 0");
+  NTS_CHECK_ARG(ld_g >= 2 * (uint64_t)feature_size, "ld_ycat < 2 feature_size");
+  NTS_CHECK_ARG(ld_gin >= feature_size && (!x_act || ld_act >= feature_size),
+                "leading dimension < feature_size");
+  if (s_cap == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  AggExtra ax;
+  ax.self = src_dst;
+  ax.mx = x_act;
+  ax.ldm = ld_act;
+  ax.scale = x_act ? scale : 1.f;
+  return launch_gather<false, false, kAggRootBwd, true>(ctx->stream, row_offset, column_indices,
+                                                        weight_backward, s, s_cap, g_ycat, ld_g,
+                                                        nullptr, feature_size, g_in, ld_gin,
+                                                        Tier{nullptr, nullptr, 0, 0}, ax);
+}
+
 int nts_hip_spmm_csc_bwd_atomic(nts_hip_ctx* ctx, const uint32_t* column_offset,
                                 const uint32_t* row_indices, const float* weight,
                                 const uint32_t* v, uint32_t v_cap, const float* g_out,
@@ -987,7 +1080,7 @@ int nts_hip_spmm_csc_bwd_atomic(nts_hip_ctx* ctx, const uint32_t* column_offset,
                 "leading dimension < feature_size");
   if (v_cap == 0 || feature_size == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const int vec = pick_vec(feature_size, ld_gout, ld_gin, g_out, g_in);
+  const int vec = row_vec(feature_size, {{g_out, ld_gout}, {g_in, ld_gin}});
   const uint32_t nv = feature_size / vec;
   const int lpd = nv <= 16 ? 16 : (nv <= 32 ? 32 : 64);
   const uint32_t grid = std::max(1u, std::min(ceil_div(v_cap, kAggThreads / lpd), 4096u));
@@ -1013,8 +1106,8 @@ template <bool TIER, bool STAGE = false>
 static int gather_rows(nts_hip_ctx* ctx, const float* table, uint64_t ld_table,
                        const uint32_t* index, const uint32_t* n, uint32_t n_cap,
                        uint32_t feature_size, float* out, uint64_t ld_out, Tier tier) {
-  int vec = pick_vec(feature_size, ld_table, ld_out, table, out);
-  if (TIER) vec = std::min(vec, pick_vec(feature_size, tier.ldh, ld_out, tier.host, out));
+  const int vec = row_vec(feature_size, {{table, ld_table}, {out, ld_out},
+                                         {TIER ? tier.host : nullptr, tier.ldh}});
   const uint32_t nv = feature_size / vec;
   const int lpd = nv <= 16 ? 16 : (nv <= 32 ? 32 : 64);
   const uint32_t grid = std::max(1u, std::min(ceil_div(n_cap, kAggThreads / lpd), 4096u));

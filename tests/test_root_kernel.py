@@ -1,4 +1,4 @@
-"""GraphSAGE root-weight graph op (csrc/root.hip) through the C-ABI.
+"""GraphSAGE root-weight graph op (the root modes of csrc/aggregate.hip) through the C-ABI.
 
 The arithmetic is defined to the bit (the aggregation's serial edge order,
 (x*w)+acc without contraction, the self term one more fp32 add), so every
@@ -290,5 +290,53 @@ def test_backward_long_rows_follow_the_existing_split(hip, F):
     comp = torch.where(x_act > 0, comp * 0.5, torch.zeros_like(comp))
     gin = _buf(s, F, True)
     hip.spmm_csr_bwd_root(ro_t, ci_t, wb_t, s_dev, s, g, inv, gin, x_act=x_act, scale=0.5)
+    torch.cuda.synchronize()
+    assert torch.equal(gin, comp)
+
+
+def _pitched(rows, cols, fill=float("nan")):
+    """[rows, cols] view of a buffer whose row pitch is cols rounded up to 32
+    floats (the 128-byte pitch the driver's buffers have)"""
+    ld = (cols + 31) // 32 * 32
+    return torch.full((rows, ld), fill, dtype=torch.float32, device=DEV)[:, :cols]
+
+
+@pytest.mark.parametrize("masked", [True, False], ids=["x_act", "no_mask"])
+@pytest.mark.parametrize("F", [18, 41, 602])
+def test_backward_long_rows_on_padded_pitches(hip, F, masked):
+    """The same hand-made block on 128-byte row pitches with F no multiple of
+    4: nts_hip_spmm_csr_bwd takes float4 over the pitch padding there and the
+    root backward, whose right half starts at column F, a narrower vector.
+    The lane-group shape and the long-row threshold must still be the plain
+    call's (at F = 18 and 41 the other reading gives 32 against 16 and 16
+    against 4 pieces per long row), so the 33- and 200-edge rows agree to the
+    bit only if they are."""
+    rng = np.random.default_rng(F)
+    s, v = 70, 260
+    lens = rng.integers(0, 6, s)
+    lens[[3, 40, 69]] = (17, 33, 200)
+    ro = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)
+    e = int(ro[-1])
+    ci = rng.integers(0, v, e).astype(np.uint32)
+    wb = rng.random(e).astype(np.float32)
+    inv_np = np.full(s, NONE, np.uint32)
+    pick = rng.choice(s, 40, replace=False)
+    inv_np[pick] = rng.choice(v, 40, replace=False).astype(np.uint32)
+    inv_np[[3, 69]] = (5, 6)
+    inv_np[40] = NONE
+    ro_t, ci_t, wb_t, inv = _t(ro), _t(ci), torch.from_numpy(wb).to(DEV), _t(inv_np)
+    s_dev = torch.tensor([s], dtype=torch.int32, device=DEV)
+    g = _rand_into(_pitched(v, 2 * F), F)
+    x_act = _rand_into(_pitched(s, F), F + 1)
+    ref = _pitched(s, F)
+    hip.spmm_csr_bwd(ro_t, ci_t, wb_t, s_dev, s, g[:, :F], ref)
+    has = torch.from_numpy(np.flatnonzero(inv_np != NONE)).to(DEV)
+    comp = ref.clone()
+    comp.index_add_(0, has, g[:, F:][inv[has].long()])
+    if masked:
+        comp = torch.where(x_act > 0, comp * 0.5, torch.zeros_like(comp))
+    gin = _pitched(s, F)
+    hip.spmm_csr_bwd_root(ro_t, ci_t, wb_t, s_dev, s, g, inv, gin,
+                          x_act=x_act if masked else None, scale=0.5)
     torch.cuda.synchronize()
     assert torch.equal(gin, comp)
