@@ -702,6 +702,49 @@ int nts_hip_spmm_csr_bwd_root(nts_hip_ctx *ctx, const uint32_t *row_offset,
                               uint64_t ld_act, float scale, uint32_t feature_size, float *g_in,
                               uint64_t ld_gin);
 
+/* ---- GraphSAGE max aggregator (csrc/aggmax.hip, csrc/infer.hip; no
+ * counterpart in the reference, whose graph ops are weighted sums) ----------
+ * Forward: for every d < *v and column c < F
+ *   y[d, c] = max over e in [co[d], co[d+1]) of x[row(e), c]
+ * with row(e) as in nts_hip_spmm_csc_fwd (through x_row_map when non-NULL).
+ * The column is scanned serially in CSC edge order: the first edge's value
+ * starts the maximum (not 0, not -FLT_MAX) and a later one replaces it on a
+ * strict >, so ties (+0 / -0 included) go to the earliest edge.  An empty
+ * column gives 0.0f.  No weights.  NaN inputs are unspecified.
+ * arg (nullable, uint32 [v_cap, F], row pitch F): arg[d, c] = the winning CSC
+ * edge index, 0xFFFFFFFF for an empty column.  self_index (nullable): also
+ * y[d, F:2F] = x[self_index[d], :] as nts_hip_spmm_csc_fwd_root's right half
+ * (ldy >= 2 F).  Rows >= *v are left untouched; any F >= 1 (float4 / float2 /
+ * scalar by alignment). */
+int nts_hip_spmm_csc_fwd_max(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                             const uint32_t *row_indices, const uint32_t *v, uint32_t v_cap,
+                             const float *x, uint64_t ldx, const uint32_t *x_row_map,
+                             const uint32_t *self_index, uint32_t feature_size, float *y,
+                             uint64_t ldy, uint32_t *arg);
+/* Backward over the CSR transpose of a layer sampled with csr_edge_id: for s < *s
+ *   g_in[s, c] = m_s[c] ( sum_{j in [ro[s], ro[s+1]), arg[ci[j], c] == csr_edge_id[j]} g_y[ci[j], c]
+ *                         + (src_dst && src_dst[s] != NTS_NOT_CACHED ? g_y[src_dst[s], F + c] : 0) )
+ * m_s = [x_act[s, :] > 0] scale when x_act != NULL (nts_hip_spmm_csr_bwd_postmask's
+ * rule), else 1.  The sum runs in nts_hip_spmm_csr_bwd's order for the same
+ * row_offset and F, its long-row rule included; a slot that did not win adds
+ * nothing or an exact +0, so where every slot of a row won the result is
+ * nts_hip_spmm_csr_bwd's with unit weights bit for bit.  Deterministic: no
+ * float atomics, no grid barrier.  ld_g >= 2 F with src_dst. */
+int nts_hip_spmm_csr_bwd_max(nts_hip_ctx *ctx, const uint32_t *row_offset,
+                             const uint32_t *column_indices, const uint32_t *csr_edge_id,
+                             const uint32_t *s, uint32_t s_cap, const float *g_y, uint64_t ld_g,
+                             const uint32_t *arg, const uint32_t *src_dst, const float *x_act,
+                             uint64_t ld_act, float scale, uint32_t feature_size, float *g_in,
+                             uint64_t ld_gin);
+/* The same maximum over the GLOBAL CSC of `graph` for v_begin <= d < v_end
+ * (layer-wise inference, see nts_hip_spmm_graph_fwd): no arg, an empty column
+ * writes a zero row, relu optional.  Hub columns are walked in a fixed order,
+ * and a maximum does not depend on it: the result equals the serial one (only
+ * the sign of a zero maximum is left open). */
+int nts_hip_spmm_graph_fwd_max(nts_hip_ctx *ctx, const nts_graph_dev *graph, uint64_t v_begin,
+                               uint64_t v_end, int relu, const float *x, uint64_t ldx,
+                               uint32_t feature_size, float *y, uint64_t ldy);
+
 /* ---- optimiser ---------------------------------------------------------- */
 /* Fused Adam step on one parameter (n elements), element-wise identical to
  *  bias_correction != 0: Parameter::learnC2C_with_decay_Adam (core/NtsScheduler.hpp:863-880)

@@ -8,7 +8,7 @@
 // runs in CSC edge order as acc + x*w with contraction disabled: bit-identical
 // to the reference's MiniBatchFuseOp/nts_comp (core/ntsBaseOp.hpp:546-562,
 // `_mm256_add_ps(_mm256_mul_ps(source,w),destination)`) for the same sampCSC.
-#include "common.hpp"
+#include "agg_shape.hpp"
 
 #pragma clang fp contract(off)
 
@@ -64,8 +64,6 @@ struct VT<4> {
     if (nvalid > 2) __builtin_nontemporal_store(v.z, q + 2);
   }
 };
-
-constexpr int kAggThreads = 256;
 
 // y[d, :] = sum_{e in [off[d], off[d+1])} w[e] * x[row(e), :]
 // row(e) = MAP ? map[idx[e]] : idx[e];  w == nullptr -> weight 1.
@@ -382,8 +380,7 @@ __device__ __forceinline__ void store_row(typename VT<VEC>::T (&acc)[NCH], uint3
 // (bit-identical to MiniBatchFuseOp::backward's), longer rows are summed as
 // GPB in-order pieces.  A group takes at most kCoopRows rows (grid >=
 // ceil(n_cap / (GPB kCoopRows))): the block's long rows fit its list.
-constexpr uint32_t kLongRow(int u) { return 4 * u; }
-constexpr uint32_t kCoopRows = 16;
+// (kLongRow, kCoopRows: agg_shape.hpp)
 
 // Each row's loads run off -> ids -> rows with nothing loaded ahead.  A row
 // software pipeline (1: the next row's offsets; 2: the offsets two rows ahead
@@ -698,45 +695,7 @@ __global__ void k_adam(float* __restrict__ W, const float* __restrict__ G, float
 // ---------------------------------------------------------------------------
 // dispatch
 // ---------------------------------------------------------------------------
-// The widest vector (4, 2 or 1 floats) the rows of these operands allow: F a
-// multiple of it and every row start aligned to it (a NULL operand is absent).
-// pad: rows padded to a 16-byte multiple (the 128-byte feature / output pitch)
-// take float4 whatever F is, the partial last vector reading pitch padding
-// and storing only its valid floats.
-struct Rows {
-  const void* p;
-  uint64_t ld;  // pitch in floats
-};
-static int row_vec(uint32_t F, std::initializer_list<Rows> ops, bool pad = false) {
-  auto fits = [&](uint32_t cols, int vec) {
-    bool ok = cols % vec == 0;
-    for (const Rows& r : ops)
-      ok = ok && (!r.p || (cols <= r.ld && r.ld % vec == 0 && (uintptr_t)r.p % (4 * vec) == 0));
-    return ok;
-  };
-  if (pad && fits((F + 3) / 4 * 4, 4)) return 4;
-  return fits(F, 4) ? 4 : fits(F, 2) ? 2 : 1;
-}
-
-struct Shape {
-  int lpd, nch;
-};
-// (128-float rows on 16-lane groups of two float4 per lane — four rows per
-// wave instead of two — measured: hop-0 backward 42.5 vs 44.8 us, the bottom
-// CSR backward 125-127 vs 122, C2 0.824 vs 0.807 ms/step; not kept)
-static Shape pick_shape(uint32_t nv) {
-  if (nv <= 8) return {8, 1};
-  if (nv <= 16) return {16, 1};
-  if (nv <= 32) return {32, 1};
-  if (nv <= 64) return {64, 1};
-  uint32_t nch = (nv + 63) / 64;
-  return {64, (int)std::min<uint32_t>(nch, 8)};
-}
-
-constexpr int gather_u(int floats_per_lane) {
-  return floats_per_lane <= 4 ? 8 : floats_per_lane <= 12 ? 5 : 4;
-}
-constexpr uint32_t kGatherGridCap = 1u << 24;
+// (row_vec, pick_shape, gather_u, kGatherGridCap: agg_shape.hpp)
 
 template <int VEC, bool MAP, bool TIER, int MODE, bool COOP>
 static int launch_gather_vec(hipStream_t st, uint32_t grid, uint32_t last_valid, Shape s,

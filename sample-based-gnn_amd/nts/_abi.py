@@ -58,6 +58,7 @@ EXPORTED = (
     "nts_hip_spmm_graph_fwd",
     "nts_hip_linear_bce_fwd", "nts_hip_linear_bce_train",
     "nts_hip_spmm_csc_fwd_root", "nts_hip_root_inverse_map", "nts_hip_spmm_csr_bwd_root",
+    "nts_hip_spmm_csc_fwd_max", "nts_hip_spmm_csr_bwd_max", "nts_hip_spmm_graph_fwd_max",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -160,6 +161,9 @@ def lib() -> C.CDLL:
         "nts_hip_spmm_csc_fwd_root": ([P, P, P, P, P, U32, P, U64, P, P, U32, P, U64], I),
         "nts_hip_root_inverse_map": ([P, P, P, U32, P, U32, P], I),
         "nts_hip_spmm_csr_bwd_root": ([P, P, P, P, P, U32, P, U64, P, P, U64, F, U32, P, U64], I),
+        "nts_hip_spmm_csc_fwd_max": ([P, P, P, P, U32, P, U64, P, P, U32, P, U64, P], I),
+        "nts_hip_spmm_csr_bwd_max": ([P, P, P, P, P, U32, P, U64, P, P, P, U64, F, U32, P, U64], I),
+        "nts_hip_spmm_graph_fwd_max": ([P, P, U64, U64, I, P, U64, U32, P, U64], I),
         "nts_hip_adam": ([P, P, P, P, P, U64, F, F, F, F, F, F, F, I], I),
         "nts_hip_comm_unique_id": ([P], I),
         "nts_hip_comm_init": ([C.POINTER(P), I, I, P, I], I),

@@ -262,6 +262,13 @@ def random_generate(n_vertices: int, n_features: int, n_classes: int, seed: int 
     return feats, labels, masks
 
 
+def _aggregator(value: str) -> str:
+    v = value.strip().lower()
+    if v not in ("sum", "max"):
+        raise ValueError(f"AGGREGATOR:{value}: sum or max")
+    return v
+
+
 @dataclass
 class InputInfo:
     """InputInfo (core/GraphSegment.h:156-244) — the cfg keys of Appendix C."""
@@ -294,6 +301,10 @@ class InputInfo:
     # ROOT_WEIGHT (this build's key): GraphSAGE layers with a root weight,
     # X' = act([A X | X_dst] W) (GCN / GraphSAGE algorithms without PD cache)
     root_weight: int = 0
+    # AGGREGATOR (this build's key): sum (the weighted sum of the algorithm's
+    # weight type, the default) or max (GraphSAGE's max aggregator; the weight
+    # type is then ignored; GCN / GraphSAGE algorithms without PD cache)
+    aggregator: str = "sum"
     extra: dict = field(default_factory=dict)
 
     @property
@@ -321,6 +332,7 @@ class InputInfo:
             "FULL_INFERENCE": ("full_inference", int),
             "MULTI_LABEL": ("multi_label", int),
             "ROOT_WEIGHT": ("root_weight", int),
+            "AGGREGATOR": ("aggregator", _aggregator),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

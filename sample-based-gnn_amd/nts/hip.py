@@ -208,6 +208,36 @@ class HipContext:
             ptr(src_dst), ptr(x_act), x_act.stride(0) if x_act is not None else 0, float(scale),
             F, ptr(g_in), g_in.stride(0)))
 
+    def spmm_csc_fwd_max(self, co, ri, v_dev, v_cap, x, y, row_map=None, self_index=None, arg=None):
+        """y[d, :F] = max over d's edges of x[row(e)] in CSC edge order (ties to the
+        earliest edge, an empty column 0); arg (int32 [v_cap, F]): the winning edge or
+        -1; self_index: also y[d, F:2F] = x[self_index[d]]."""
+        F = x.shape[1]
+        check(self.lib.nts_hip_spmm_csc_fwd_max(self.h, ptr(co), ptr(ri), ptr(v_dev), v_cap, ptr(x),
+                                                x.stride(0), ptr(row_map), ptr(self_index), F,
+                                                ptr(y), y.stride(0), ptr(arg)))
+
+    def spmm_csr_bwd_max(self, ro, ci, ceid, s_dev, s_cap, g_y, arg, g_in, src_dst=None,
+                         x_act=None, scale=1.0):
+        """g_in[s] = m ⊙ (sum of g_y[ci[j], :F] over the CSR slots j of s whose edge
+        ceid[j] is arg[ci[j]] + g_y[src_dst[s], F:]), m = (x_act > 0) * scale (1 without
+        x_act); F = g_in.shape[1]."""
+        F = g_in.shape[1]
+        check(self.lib.nts_hip_spmm_csr_bwd_max(
+            self.h, ptr(ro), ptr(ci), ptr(ceid), ptr(s_dev), s_cap, ptr(g_y), g_y.stride(0),
+            ptr(arg), ptr(src_dst), ptr(x_act), x_act.stride(0) if x_act is not None else 0,
+            float(scale), F, ptr(g_in), g_in.stride(0)))
+
+    def spmm_graph_fwd_max(self, graph, x, y, relu=False, v_begin=0, v_end=None):
+        """y[d] = (relu?)(max over ALL in-edges of d of x[src(e)]) for v_begin <= d <
+        v_end over the global CSC of `graph`; a vertex without in-edges gets zeros."""
+        g = graph.as_struct()
+        if v_end is None:
+            v_end = graph.n_vertices
+        check(self.lib.nts_hip_spmm_graph_fwd_max(self.h, C.byref(g), int(v_begin), int(v_end),
+                                                  int(bool(relu)), ptr(x), x.stride(0), x.shape[1],
+                                                  ptr(y), y.stride(0)))
+
     def spmm_csr_bwd_masked(self, ro, ci, wb, s_dev, s_cap, g_out, x_act, g_in, scale=1.0):
         """g_in = A^T (g_out * (x_act > 0) * scale) over the CSR."""
         F = g_out.shape[1]
@@ -494,6 +524,7 @@ class LayerBuffers:
     omit_key: int = 0
     omit_loc: torch.Tensor | None = None  # ... their cache rows, recorded per dst in t["omit_row"]
     t: dict = field(default_factory=dict)
+    edge_ids: bool = False  # csr_edge_id for a layer with a CSR, without merging (max aggregator)
 
     def __post_init__(self):
         d = self.device
@@ -513,7 +544,7 @@ class LayerBuffers:
         else:
             self.t["row_offset"] = self.t["column_indices"] = self.t["edge_weight_backward"] = None
         self.t["dst_local_id"] = _u32(max(self.v_cap, 1), d) if self.merge else None
-        self.t["csr_edge_id"] = _u32(max(self.e_cap, 1), d) if (self.merge and self.csr) else None
+        self.t["csr_edge_id"] = _u32(max(self.e_cap, 1), d) if ((self.merge or self.edge_ids) and self.csr) else None
         self.t["omit_row"] = _u32(max(self.v_cap, 1), d) if self.omit_map is not None else None
 
     def __getattr__(self, k):

@@ -40,7 +40,9 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                fuse_loss=True, sampler_cus=0, sampler_gate=0, pad_features=True, cache_rate=-1.0,
                up_degree=False, gat=False, pd_cache=False, pd_rate=0.2, pd_super_batch=4,
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
-               multi_label=False, root_weight=False):
+               multi_label=False, root_weight=False, aggregator="sum"):
+    if aggregator not in ("sum", "max"):
+        raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
     E = ext()
     c = E.GCNConfig()
     c.layer_size = list(layers)
@@ -69,6 +71,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.fuse_loss = bool(fuse_loss)
     c.multi_label = bool(multi_label)
     c.root_weight = bool(root_weight)
+    c.aggregator = {"sum": 0, "max": 1}[aggregator]
     c.sampler_cus = int(sampler_cus)
     c.sampler_gate = int(sampler_gate)
     c.pad_features = bool(pad_features)

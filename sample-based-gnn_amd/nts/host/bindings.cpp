@@ -36,6 +36,7 @@ static py::list layers_of(SampledSubgraph* sg) {
       d["edge_weight_backward"] = n(s->edge_weight_backward, s->e_size);
     }
     if (s->dst_local_id.defined()) d["dst_local_id"] = n(s->dst_local_id, s->v_size);
+    if (s->csr_edge_id.defined()) d["csr_edge_id"] = n(s->csr_edge_id, s->e_size);
     out.append(d);
   }
   return out;
@@ -231,6 +232,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("fuse_loss", &GCNConfig::fuse_loss)
       .def_readwrite("multi_label", &GCNConfig::multi_label)
       .def_readwrite("root_weight", &GCNConfig::root_weight)
+      .def_readwrite("aggregator", &GCNConfig::aggregator)
       .def_readwrite("sampler_cus", &GCNConfig::sampler_cus)
       .def_readwrite("sampler_gate", &GCNConfig::sampler_gate)
       .def_readwrite("pad_features", &GCNConfig::pad_features)

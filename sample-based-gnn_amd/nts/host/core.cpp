@@ -163,6 +163,11 @@ void sampCSC::set_merge_src_dst() {
     csr_edge_id = torch::empty({std::max<int64_t>(e_cap, 1)}, u32_opts(column_offset.device().index()));
 }
 
+void sampCSC::set_edge_ids() {
+  if (has_csr && !csr_edge_id.defined())
+    csr_edge_id = torch::empty({std::max<int64_t>(e_cap, 1)}, u32_opts(column_offset.device().index()));
+}
+
 sampCSC::sampCSC(int device, VertexId vc, VertexId ec, VertexId sc, bool csr, bool weights)
     : v_cap(vc), e_cap(ec), s_cap(sc), has_csr(csr) {
   auto U = u32_opts(device);
@@ -206,7 +211,8 @@ static std::vector<std::array<uint64_t, 3>> layer_caps(VertexId batch,
 
 SampledSubgraph::SampledSubgraph(int device, int layers_, const std::vector<int>& fanout_,
                                  VertexId batch, VertexId vertices, uint64_t edges,
-                                 const std::vector<bool>& csr, bool weights, bool merge)
+                                 const std::vector<bool>& csr, bool weights, bool merge,
+                                 bool edge_ids)
     : layers(layers_), fanout(fanout_) {
   auto caps = layer_caps(batch, fanout, vertices, edges, merge);
   for (int l = 0; l < layers; ++l) {
@@ -214,6 +220,7 @@ SampledSubgraph::SampledSubgraph(int device, int layers_, const std::vector<int>
     sampled_sgs.push_back(new sampCSC(device, (VertexId)caps[l][0], (VertexId)caps[l][1],
                                       (VertexId)caps[l][2], c, weights));
     if (merge) sampled_sgs.back()->set_merge_src_dst();
+    if (edge_ids) sampled_sgs.back()->set_edge_ids();
   }
   // every layer's sizes[4] as a view of one device array: one D2H per batch
   dev_sizes = torch::zeros({std::max(layers, 1) * 4}, u32_opts(device));
@@ -241,13 +248,14 @@ SampledSubgraph::~SampledSubgraph() {
 FastSampler::FastSampler(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& index,
                          int layers, int batch_size, const std::vector<int>& fanout_,
                          int pipeline_num, std::vector<bool> csr_layers, bool weights,
-                         bool merge_src_dst)
+                         bool merge_src_dst, bool edge_ids)
     : whole_graph(g), layer(layers), fanout(fanout_), batch_cap_((VertexId)batch_size) {
   TORCH_CHECK((int)fanout.size() == layers, "fanout size != layers");
   if (pipeline_num < 1) pipeline_num = 1;
   for (int i = 0; i < pipeline_num; ++i)
     ssgs.push_back(new SampledSubgraph(g->device, layers, fanout, batch_cap_, g->global_vertices,
-                                       g->global_edges, csr_layers, weights, merge_src_dst));
+                                       g->global_edges, csr_layers, weights, merge_src_dst,
+                                       edge_ids));
   ssg = ssgs[0];
   recs_.resize(ssgs.size());
   set_sample_nids(index);
@@ -661,6 +669,63 @@ NtsVar SingleGPURootGraphOp::backward(NtsVar& g) {
                                       sg->post_mask_scale, (uint32_t)F, gi.data_ptr<float>(),
                                       (uint64_t)F),
             "nts_hip_spmm_csr_bwd_root");
+  return gi;
+}
+
+SingleGPUMaxGraphOp::SingleGPUMaxGraphOp(SampledSubgraph* sgs, int layer_, NtsStream* cs,
+                                         bool gather, bool root)
+    : subgraphs(sgs), layer(layer_), cuda_stream(cs), gather_from_table(gather), root_weight(root) {}
+
+NtsVar SingleGPUMaxGraphOp::forward(NtsVar& f_input) {
+  sampCSC* sg = subgraphs->sampled_sgs[layer];
+  TORCH_CHECK(!root_weight || sg->dst_local_id.defined(),
+              "root weight needs a merged src/dst layer");
+  TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
+                  f_input.stride(1) == 1,
+              "graph op input must be a row-major fp32 CUDA matrix");
+  TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
+              "graph op input has fewer rows than src_size");
+  const int64_t F = f_input.size(1);
+  NtsVar f_output =
+      row_padded_empty((int64_t)sg->v_size, (root_weight ? 2 : 1) * F, cuda_stream->device());
+  // the winners only where a backward will read them (never the bottom hop)
+  const bool keep = output_requires_grad && sg->has_csr;
+  if (keep) {
+    TORCH_CHECK(sg->csr_edge_id.defined(), "max aggregator backward needs csr_edge_id");
+    arg = torch::empty({std::max<int64_t>(sg->v_size, 1), F}, u32_opts(cuda_stream->device()));
+  }
+  const VertexId* self = !root_weight        ? nullptr
+                         : gather_from_table ? sg->dev_dst()
+                                             : sg->dev_dst_local_id();
+  hip_check(nts_hip_spmm_csc_fwd_max(
+                cuda_stream->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_v_size(), sg->v_size,
+                f_input.data_ptr<float>(), (uint64_t)f_input.stride(0),
+                gather_from_table ? sg->dev_src() : nullptr, self, (uint32_t)F,
+                f_output.data_ptr<float>(), (uint64_t)f_output.stride(0),
+                keep ? dptr<uint32_t>(arg) : nullptr),
+            "nts_hip_spmm_csc_fwd_max");
+  if (output_requires_grad) f_output.set_requires_grad(true);
+  return f_output;
+}
+
+NtsVar SingleGPUMaxGraphOp::backward(NtsVar& g) {
+  sampCSC* sg = subgraphs->sampled_sgs[layer];
+  TORCH_CHECK(sg->has_csr && sg->csr_edge_id.defined() && arg.defined(),
+              "max aggregator backward needs the CSR transpose, its edge ids and the forward's arg");
+  TORCH_CHECK(!root_weight || sg->src_dst.defined(), "root weight backward needs the inverse map");
+  NtsVar go = g.contiguous();
+  const int64_t F = arg.size(1);
+  TORCH_CHECK(go.size(0) == (int64_t)sg->v_size && go.size(1) == (root_weight ? 2 : 1) * F,
+              "output grad must be [v_size, F] ([v_size, 2 F] under root weight)");
+  NtsVar gi = torch::empty({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
+  hip_check(nts_hip_spmm_csr_bwd_max(cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(),
+                                     dptr<uint32_t>(sg->csr_edge_id), sg->dev_src_size(),
+                                     sg->src_size, go.data_ptr<float>(), (uint64_t)go.size(1),
+                                     dptr<uint32_t>(arg),
+                                     root_weight ? dptr<uint32_t>(sg->src_dst) : nullptr,
+                                     sg->post_mask, sg->post_mask_ld, sg->post_mask_scale,
+                                     (uint32_t)F, gi.data_ptr<float>(), (uint64_t)F),
+            "nts_hip_spmm_csr_bwd_max");
   return gi;
 }
 

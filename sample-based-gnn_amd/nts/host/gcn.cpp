@@ -54,6 +54,22 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     TORCH_CHECK(cfg.deterministic_backward,
                 "root_weight needs deterministic_backward (its backward runs over the CSR)");
   }
+  TORCH_CHECK(cfg.aggregator == 0 || cfg.aggregator == 1, "aggregator must be 0 (sum) or 1 (max)");
+  if (max_aggr()) {
+    TORCH_CHECK(!cfg.gat, "aggregator = max is not supported with gat (GCN / GraphSAGE layers only)");
+    TORCH_CHECK(!cfg.pd_cache, "aggregator = max is not supported with pd_cache");
+    TORCH_CHECK(!cfg.sample_gpu, "aggregator = max is not supported with sample_gpu");
+    TORCH_CHECK(cfg.transform_first != 1,
+                "aggregator = max is not supported with transform_first = 1 (a maximum does not "
+                "commute with W: aggregate-first only)");
+    TORCH_CHECK(cfg.pair_table <= 0, "aggregator = max is not supported with pair_table > 0");
+    TORCH_CHECK(cfg.cache_rate < 0.0, "aggregator = max is not supported with cache_rate >= 0");
+    TORCH_CHECK(cfg.fused_gather, "aggregator = max is not supported with fused_gather = false");
+    TORCH_CHECK(cfg.deterministic_backward,
+                "aggregator = max needs deterministic_backward (its backward runs over the CSR)");
+    TORCH_CHECK(!cfg.up_degree, "aggregator = max is not supported with up_degree (it takes no "
+                                "edge weights)");
+  }
   if (cfg.sample_gpu) {
     TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
     TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
@@ -99,7 +115,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // (a table that stays in the Infinity Cache) instead of F_in-wide feature
   // rows, at the price of a GEMM over the src rows instead of the dst rows.
   const bool tf_ok = L >= 2 && !cfg.gat && !fcache && cfg.hip_gemm && cfg.fuse_activation &&
-                     !cfg.pd_cache && !cfg.root_weight;
+                     !cfg.pd_cache && !cfg.root_weight && !max_aggr();
   if (cfg.transform_first == 1)
     TORCH_CHECK(tf_ok, "transform_first needs >= 2 layers, the MFMA GEMMs with the fused "
                        "activation, no GAT and no feature cache");
@@ -155,9 +171,8 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // blocks every launch on that stream in the host for ~60 us).
   nslots_ = cfg.pipeline ? kSlots : 1;
   sampler = std::make_unique<FastSampler>(graph, train_nids, L, cfg.batch_size, cfg.fanout,
-                                          nslots_, csr,
-                                          !cfg.gat && cfg.weight_type != WeightType::None,
-                                          cfg.gat || cfg.root_weight);
+                                          nslots_, csr, sample_weight() != WeightType::None,
+                                          cfg.gat || cfg.root_weight, max_aggr());
   sampler->rng_mode = cfg.rng_mode;
   sampler->up_degree = cfg.up_degree;
   if (cfg.root_weight)  // the inverse of dst_local_id, for every hop with a graph-op backward
@@ -270,8 +285,7 @@ void GCN_SAMPLE_ALLGPU_impl::mark(const char* what, NtsStream& st) {
 void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
   mark("S<", st);
   if (cfg.pd_cache) pd_issue(slot, st);
-  sampler->issue_gpu_sample(cfg.batch_size, slot, st,
-                            cfg.gat ? WeightType::None : cfg.weight_type);
+  sampler->issue_gpu_sample(cfg.batch_size, slot, st, sample_weight());
   sampler->omit_map = nullptr;
   if (cfg.root_weight)  // the backward's inverse maps, next to the sampling
     for (auto* s : sampler->ssgs[slot]->sampled_sgs)
@@ -305,6 +319,14 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
       fcache->aggregate(st.ctx(), s, dptr<uint32_t>(s->sizes), s->v_cap,
                         dptr<uint32_t>(s->sizes) + 2, s->s_cap, stage_[slot].data_ptr<float>(),
                         y.data_ptr<float>(), (uint64_t)y.stride(0));
+    else if (max_aggr())  // the bottom hop has no backward: no arg
+      hip_check(nts_hip_spmm_csc_fwd_max(st.ctx(), s->dev_c_o(), s->dev_r_i(),
+                                         dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
+                                         (uint64_t)F.stride(0), s->dev_src(),
+                                         cfg.root_weight ? s->dev_dst() : nullptr,
+                                         (uint32_t)F.size(1), y.data_ptr<float>(),
+                                         (uint64_t)y.stride(0), nullptr),
+                "nts_hip_spmm_csc_fwd_max(early)");
     else if (cfg.root_weight)  // [A X | X[destination]] from the table, one launch
       hip_check(nts_hip_spmm_csc_fwd_root(st.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(),
                                           dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
@@ -460,7 +482,10 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
       continue;
     }
     if (bottom && cfg.profile) prof.begin(KernelProfiler::BOTTOM_AGG, (hipStream_t)cs->stream());
-    if (cfg.root_weight)
+    if (max_aggr())
+      Y = ctx.runGraphOp<op::SingleGPUMaxGraphOp>(bottom ? F : X, sg, hop, cs.get(), bottom,
+                                                  cfg.root_weight);
+    else if (cfg.root_weight)
       Y = ctx.runGraphOp<op::SingleGPURootGraphOp>(bottom ? F : X, sg, hop, cs.get(), bottom);
     else if (cfg.sample_gpu && bottom && cfg.fused_gather)
       Y = ctx.runGraphOp<op::SingleGPUSampleGraphOp>(F, sg, graph.get(), hop, cs.get(), true,
@@ -789,12 +814,11 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_eval(const std::vector<Verte
   const int L = (int)cfg.fanout.size();
   std::vector<bool> csr(L, cfg.gat);
   FastSampler s(graph, seeds, L, (int)seeds.size(), cfg.fanout, 1, csr,
-                !cfg.gat && cfg.weight_type != WeightType::None, cfg.gat || cfg.root_weight);
+                sample_weight() != WeightType::None, cfg.gat || cfg.root_weight);
   s.rng_mode = cfg.rng_mode;
   s.up_degree = cfg.up_degree;
   s.batch_seq = batch_seq;
-  SampledSubgraph* sg = s.sample_gpu_fast((int)seeds.size(), 0, *cs,
-                                          cfg.gat ? WeightType::None : cfg.weight_type);
+  SampledSubgraph* sg = s.sample_gpu_fast((int)seeds.size(), 0, *cs, sample_weight());
   ctx.eval();
   torch::NoGradGuard ng;
   std::vector<NtsVar> acts;
@@ -866,7 +890,7 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
   if (nids.empty()) return 0.0;
   auto guard = cs->guard();
   const int L = (int)cfg.fanout.size();
-  const WeightType wt = cfg.gat ? WeightType::None : cfg.weight_type;
+  const WeightType wt = sample_weight();
   std::vector<bool> csr(L, cfg.gat);
   FastSampler s(graph, nids, L, cfg.batch_size, cfg.fanout, 1, csr, wt != WeightType::None,
                 cfg.gat || cfg.root_weight);
@@ -928,7 +952,7 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
   TORCH_CHECK(!cfg.gat, "infer_full: GAT layers are not supported (GCN / GraphSAGE only)");
   TORCH_CHECK(!cfg.up_degree,
               "infer_full: UP_DEGREE weights are a property of a sample, not of the whole graph");
-  TORCH_CHECK(cfg.weight_type != WeightType::MeanSampled,
+  TORCH_CHECK(max_aggr() || cfg.weight_type != WeightType::MeanSampled,
               "infer_full: MeanSampled weights are a property of a sample, not of the whole graph");
   TORCH_CHECK(!fcache, "infer_full: needs the whole feature table in HBM (cache_rate < 0)");
   flush_update();
@@ -954,11 +978,18 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
       evs.push_back({a, b});
       (void)hipEventRecord(a, st);
     }
-    hip_check(nts_hip_spmm_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
-                                     xr.data_ptr<float>(), (uint64_t)xr.stride(0),
-                                     (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                     (uint64_t)y.stride(0)),
-              "nts_hip_spmm_graph_fwd");
+    if (max_aggr())
+      hip_check(nts_hip_spmm_graph_fwd_max(cs->ctx(), &g, 0, (uint64_t)V, relu ? 1 : 0,
+                                           xr.data_ptr<float>(), (uint64_t)xr.stride(0),
+                                           (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                           (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd_max");
+    else
+      hip_check(nts_hip_spmm_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+                                       xr.data_ptr<float>(), (uint64_t)xr.stride(0),
+                                       (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                       (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd");
     if (cfg.profile) (void)hipEventRecord(evs.back().second, st);
     return y;
   };
@@ -969,7 +1000,7 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
     for (int l = 0; l < L; ++l) {
       const bool last = l == L - 1;
       const NtsVar& W = P[l]->W;
-      if (!cfg.root_weight && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
+      if (!cfg.root_weight && !max_aggr() && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
         NtsVar H = P[l]->forward(X);
         NtsVar Y = aggregate(H, !last);
         X = last && !cfg.multi_label ? Y.log_softmax(1) : Y;

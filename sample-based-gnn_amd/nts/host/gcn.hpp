@@ -40,6 +40,17 @@ struct GCNConfig {
   // gat, pd_cache, sample_gpu, transform_first = 1, pair_table, cache_rate >= 0
   // or fused_gather = false.
   bool root_weight = false;
+  // Aggregator of every layer's graph op: 0 = the weighted sum of weight_type
+  // (the default), 1 = max (GraphSAGE's max aggregator, SAGEConv(aggr="max");
+  // no reference counterpart): Y[d] = max over d's sampled edges of X[src] per
+  // column, ties to the earliest CSC edge, an empty column 0.  weight_type is
+  // ignored (the sampler builds no edge weights, the CSRs carry their edge
+  // ids), every layer is aggregate-first (a maximum does not commute with W:
+  // transform_first = -1 resolves to 0) and infer_full() takes the maximum
+  // over all in-edges.  Not with gat, pd_cache, sample_gpu, transform_first =
+  // 1, pair_table > 0, cache_rate >= 0, fused_gather = false,
+  // deterministic_backward = false or up_degree.
+  int aggregator = 0;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its
@@ -246,6 +257,11 @@ class GCN_SAMPLE_ALLGPU_impl {
   bool pd_active_ = false;
   std::vector<std::pair<const char*, hipEvent_t>> tl_;  // NTS_TIMELINE events
   bool tf_ = false;  // transform-first bottom layer (cfg.transform_first)
+  // cfg.aggregator: the max graph op, and the weights the samplers then build (none)
+  bool max_aggr() const { return cfg.aggregator == 1; }
+  WeightType sample_weight() const {
+    return cfg.gat || max_aggr() ? WeightType::None : cfg.weight_type;
+  }
   std::unique_ptr<PairTable> pairs_;  // the feature table's f16 pair table (cfg.pair_table)
   // early aggregation: per sampler slot, the bottom graph op's output and the
   // event after which it (and the slot's sampled graph) is ready

@@ -120,7 +120,8 @@ class sampCSC {
   torch::Tensor destination, column_offset, row_indices, sample_ans, edge_dst, source,
       edge_weight_forward, row_offset, column_indices, edge_weight_backward, sizes;
   // is_merge_src_dst (GAT): dst d is local src dst_local_id[d]; CSR slot j is
-  // CSC edge csr_edge_id[j] (both undefined unless set_merge_src_dst())
+  // CSC edge csr_edge_id[j] (both undefined unless set_merge_src_dst();
+  // set_edge_ids() asks for csr_edge_id alone: the max aggregator's backward)
   torch::Tensor dst_local_id, csr_edge_id;
   // root weight: src_dst[s] = the dst whose dst_local_id is s, else
   // NTS_NOT_CACHED (nts_hip_root_inverse_map, built next to the sampling)
@@ -140,6 +141,7 @@ class sampCSC {
 
   sampCSC(int device, VertexId v_cap, VertexId e_cap, VertexId s_cap, bool csr, bool weights);
   void set_merge_src_dst();  // core/coocsc.hpp:405-411
+  void set_edge_ids();       // csr_edge_id where the layer has a CSR, without merging
   VertexId* dev_dst_local_id() const { return dptr<VertexId>(dst_local_id); }
   // the reference accessor names
   VertexId* dev_dst() const { return dptr<VertexId>(destination); }
@@ -174,7 +176,7 @@ class SampledSubgraph {
   SampledSubgraph(int device, int layers, const std::vector<int>& fanout, VertexId batch,
                   VertexId vertices, uint64_t edges, const std::vector<bool>& csr,
                   bool weights,
-                  bool merge = false);
+                  bool merge = false, bool edge_ids = false);
   ~SampledSubgraph();
   SampledSubgraph(const SampledSubgraph&) = delete;
   SampledSubgraph& operator=(const SampledSubgraph&) = delete;
@@ -242,7 +244,7 @@ class FastSampler {
   FastSampler(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& index, int layers,
               int batch_size, const std::vector<int>& fanout, int pipeline_num = 1,
               std::vector<bool> csr_layers = {}, bool weights = true,
-              bool merge_src_dst = false);
+              bool merge_src_dst = false, bool edge_ids = false);
   ~FastSampler();
 
   SampledSubgraph* sample_gpu_fast(int batch_size, int ssg_id, NtsStream& cs,
@@ -364,6 +366,26 @@ class SingleGPURootGraphOp : public ntsGraphOp {
   int layer;
   NtsStream* cuda_stream;
   bool gather_from_table;
+};
+
+// GraphSAGE max aggregator (no reference counterpart): forward Y[d] = max over
+// d's sampled edges of X[src] per column, in CSC edge order (ties to the
+// earliest edge), the winning edge kept in `arg` where a backward follows;
+// backward routes each dY[d, c] to the source of that edge over the CSR and
+// its csr_edge_id.  root_weight: Ycat = [max | X[dst rows]] on a merged layer
+// and the self term in the backward, as SingleGPURootGraphOp.
+class SingleGPUMaxGraphOp : public ntsGraphOp {
+ public:
+  SingleGPUMaxGraphOp(SampledSubgraph* subgraphs, int layer, NtsStream* cs,
+                      bool gather_from_table = false, bool root_weight = false);
+  NtsVar forward(NtsVar& f_input) override;
+  NtsVar backward(NtsVar& f_output_grad) override;
+
+  SampledSubgraph* subgraphs;
+  int layer;
+  NtsStream* cuda_stream;
+  bool gather_from_table, root_weight;
+  torch::Tensor arg;  // u32 [v_size, F], forward to backward
 };
 
 }  // namespace op

@@ -108,6 +108,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.root_weight and (model == "gat" or place is not None):
         raise SystemExit(f"ALGORITHM {info.algorithm}: ROOT_WEIGHT is not supported with GAT, "
                          "PD-cache or GCN_SAMPLE_GPU algorithms")
+    if info.aggregator == "max" and (model == "gat" or place is not None):
+        raise SystemExit(f"ALGORITHM {info.algorithm}: AGGREGATOR:max is not supported with GAT, "
+                         "PD-cache or GCN_SAMPLE_GPU algorithms")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -122,7 +125,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         pipeline=info.pipeline_num > 1, up_degree=info.up_degree, gat=model == "gat",
         cache_rate=cache_rate, shuffle=True, pd_cache=pd, pd_rate=info.cache_rate,
         pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu",
-        multi_label=bool(info.multi_label), root_weight=bool(info.root_weight))
+        multi_label=bool(info.multi_label), root_weight=bool(info.root_weight),
+        aggregator=info.aggregator)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
