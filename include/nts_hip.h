@@ -470,7 +470,13 @@ int nts_hip_relu_dropout_f32(nts_hip_ctx *ctx, uint32_t rows, uint32_t feature_s
  * for the source half, a2 = att[F:2F] for the destination half).  Forward:
  *   m[e] = leaky_relu(H[src_e].a1 + H[dst_local(d)].a2, 0.2),
  *   a[e] = softmax over the edges of d of m,  Y[d] = relu(sum_e a[e] H[src_e]).
- * One wave per destination, online softmax (running max/sum), edge order. */
+ * One wave per destination, online softmax (running max/sum), edge order.
+ * Width limit (a lane holds at most 4 vectors of a row): F <= 1024 when F is a
+ * multiple of 4, every row pointer and att are 16-byte aligned and every
+ * pitch is a multiple of 4 (float4 path); F <= 256 otherwise (scalar path).
+ * The backward applies the same rule to all of its row operands, so it may
+ * take the scalar path where the forward took float4.  A wider F returns
+ * NTS_ERR_INVALID and writes nothing. */
 int nts_hip_gat_forward(nts_hip_ctx *ctx, const uint32_t *column_offset,
                         const uint32_t *row_indices, const uint32_t *dst_local_id,
                         uint32_t v_size, const float *H, uint64_t ldh, uint32_t F,

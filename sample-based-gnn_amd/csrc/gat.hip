@@ -301,11 +301,16 @@ static bool gat_vec4(uint32_t F, uint64_t l1, uint64_t l2, const void* p1, const
 
 using namespace nts_hip;
 
+// at most 4 vectors per lane: 4 * 64 float4 or 4 * 64 floats a row
+static const char kGatWidthMsg[] =
+    "feature width too large (F <= 1024 on 16-byte aligned rows with pitches that are "
+    "multiples of 4, F <= 256 otherwise)";
+
 #define NTS_GAT_DISPATCH(KERNEL, ARGS)                                                   \
   do {                                                                                   \
     const uint32_t nvec = v4 ? F / 4 : F;                                                \
     const int nch = (int)((nvec + 63) / 64);                                             \
-    NTS_CHECK_ARG(nch <= 4, "feature width too large (<= 1024 with float4, 256 else)"); \
+    NTS_CHECK_ARG(nch <= 4, kGatWidthMsg);                                               \
     const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));                        \
     if (v4) {                                                                            \
       switch (nch) {                                                                     \
@@ -363,10 +368,12 @@ int nts_hip_gat_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
   if (F == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
   const hipStream_t st = ctx->stream;
-  if (src_size) NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * sizeof(float), st));
   const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 && lddh % 4 == 0 &&
                   ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 && ((uintptr_t)dH % 16) == 0 &&
                   ((uintptr_t)GM % 16) == 0;
+  // a refused width leaves every output as it was: checked before ds2 is cleared
+  NTS_CHECK_ARG((v4 ? F / 4 : F) <= 256, kGatWidthMsg);
+  if (src_size) NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * sizeof(float), st));
   if (v_size) {
     const uint32_t n = v_size;
 #define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm

@@ -40,7 +40,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                fuse_loss=True, sampler_cus=0, sampler_gate=0, pad_features=True, cache_rate=-1.0,
                up_degree=False, gat=False, pd_cache=False, pd_rate=0.2, pd_super_batch=4,
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
-               multi_label=False, root_weight=False, aggregator="sum"):
+               multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9):
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
     E = ext()
@@ -50,6 +50,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.batch_size = int(batch_size)
     c.learn_rate = float(learn_rate)
     c.weight_decay = float(weight_decay)
+    c.epsilon = float(epsilon)  # Adam's; 1.0 makes the first step read the gradient out (tests)
     c.drop_rate = float(drop_rate)
     c.rng_mode = int(rng_mode)
     c.sample_gpu = bool(sample_gpu)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from gat_blocks import gat_chain as _gat_torch  # the materialised-message reference chain
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -456,7 +457,9 @@ def test_adam_matches_reference_torch_expressions(hip, bias_correction):
                                    # LDS-resident-weight NN / row-streaming TN kernels:
                                    # odd K, 128-column slices, narrow N, tails
                                    (4097, 128, 301), (3001, 256, 200), (2100, 64, 602),
-                                   (333, 256, 5000), (700, 128, 3)])
+                                   (333, 256, 5000), (700, 128, 3),
+                                   # the GAT driver's dW_att = H^T dS with trans_a: N = 2, 8-byte rows
+                                   (32, 2, 1500), (256, 2, 70)])
 @pytest.mark.parametrize("trans_a", [False, True])
 def test_gemm_f32_mfma(hip, M, N, K, trans_a):
     """MFMA fp32 GEMM vs torch fp64 (asymmetric data, ragged tails, long split
@@ -1031,24 +1034,6 @@ def test_feature_cache_two_tier(hip, cora, rate, F):
     assert np.isnan(st[~cold]).all()  # cached rows are never staged
     assert np.array_equal(y2.cpu().numpy(), Y_ref)
     host.close()
-
-
-def _gat_torch(H, att, co, ri, dl, F):
-    """The reference layer chain (GAT_SAMPLE_ALL_GPU.hpp:354-388) in torch fp64 with
-    materialised messages: msg = [H[src], H[dst]], m = leaky(msg W_att), per-dst
-    softmax (max-subtracted, edge_softmax_forward_norm_block), sum a*H[src], relu."""
-    v = co.numel() - 1
-    deg = (co[1:] - co[:-1]).long()
-    d_of_e = torch.repeat_interleave(torch.arange(v, device=H.device), deg)
-    msg = torch.cat([H[ri.long()], H[dl.long()[d_of_e]]], 1)
-    m = torch.nn.functional.leaky_relu(msg @ att.view(2 * F, 1), 0.2).view(-1)
-    mx = torch.full((v,), -float("inf"), dtype=H.dtype, device=H.device).scatter_reduce(
-        0, d_of_e, m, "amax")
-    ex = torch.exp(m - mx[d_of_e])
-    sm = torch.zeros(v, dtype=H.dtype, device=H.device).index_add(0, d_of_e, ex)
-    a = ex / sm[d_of_e]
-    Z = torch.zeros(v, F, dtype=H.dtype, device=H.device).index_add(0, d_of_e, H[ri.long()] * a[:, None])
-    return torch.relu(Z), m, a
 
 
 @pytest.mark.parametrize("F", [16, 7, 256])

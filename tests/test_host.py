@@ -196,6 +196,53 @@ def test_training_step_matches_oracle_step(E, graph, tf, pt):
         torch.testing.assert_close(w1, ref, rtol=1e-5, atol=1e-5)
 
 
+def _gcn_chain_grads(drv, feat, labels, W0, dtype):
+    """gradients of the two weights through the GCN chain in `dtype`, on the
+    trained batch's own sampled layers and edge weights"""
+    top, bottom = drv.last_layers
+
+    def agg(lay, X):
+        co, ri = lay["column_offset"].cpu().long(), lay["row_indices"].cpu().long()
+        w = lay["edge_weight_forward"].cpu().to(dtype)
+        d_of_e = torch.repeat_interleave(torch.arange(co.numel() - 1), co[1:] - co[:-1])
+        return torch.zeros(co.numel() - 1, X.shape[1], dtype=dtype).index_add(0, d_of_e, X[ri] * w[:, None])
+
+    W = [w.to(dtype).requires_grad_() for w in W0]
+    X0 = feat.cpu().to(dtype)[bottom["source"].cpu().long()]
+    X1 = torch.relu(agg(bottom, X0) @ W[0])
+    out = (agg(top, X1) @ W[1]).log_softmax(1)
+    tgt = labels.cpu()[top["destination"].cpu().long()]
+    torch.nn.functional.nll_loss(out.log_softmax(1), tgt).backward()
+    return [w.grad for w in W]
+
+
+@pytest.mark.parametrize("tf,pt", [(0, 0), (0, 1), (1, 0), (1, 1)])
+def test_training_step_gradients_keep_their_magnitude(E, graph, tf, pt):
+    """test_training_step_matches_oracle_step compares weights after a step
+    that, with epsilon = 1e-9, moves each by lr * 3.16 * sign(gradient): a
+    backward chain off by a positive factor passes it.  Here the step reads the
+    gradient out (tests/step_check.py) and both weights' gradients are held to
+    C times the float32 chain's own error of float64 autograd."""
+    import step_check
+    from nts import host, synthetic
+    F, C, B, H = 64, 7, 200, 32
+    feat = synthetic.features(graph["V"], F, device=DEV)
+    labels, masks = synthetic.labels_masks(graph["V"], C, device=DEV)
+    train = torch.nonzero(masks == 0).flatten().to(torch.int32).cpu()
+    cfg = step_check.readout(host.gcn_config([F, H, C], [10, 5], B, drop_rate=0.0, shuffle=False,
+                                             transform_first=tf, pair_table=pt))
+    drv = E.GCN_SAMPLE_ALLGPU_impl(graph["G"], feat, labels, train, cfg, None)
+    assert drv.transform_first == bool(tf)
+    W0 = [w.cpu().clone() for w in drv.weights()]
+    drv.train_batch()
+    drv.synchronize()
+    W1 = [w.cpu().clone() for w in drv.weights()]
+    g64 = _gcn_chain_grads(drv, feat, labels, W0, torch.float64)
+    g32 = _gcn_chain_grads(drv, feat, labels, W0, torch.float32)
+    print(f"GCN tf={tf} pt={pt}")
+    step_check.check_step_grads(W0, W1, g64, g32, step_check.C)
+
+
 @pytest.mark.parametrize("tf", [0, 1])
 def test_atomic_backward_trains_like_the_csr_backward(E, graph, tf):
     """deterministic_backward=False (graph-op backward by atomic CSC scatter,

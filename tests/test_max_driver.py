@@ -138,6 +138,48 @@ def test_one_training_step_matches_the_float64_chain(E, data, root, fuse_loss):
         torch.testing.assert_close(w1.cpu().double(), r, rtol=1e-5, atol=1e-5)
 
 
+def _chain_grads(drv, data, W0, root, dtype):
+    """the gradients of reference_step's chain in `dtype`, and its top-hop gap"""
+    top, bottom = drv.last_layers
+    feat = data["feat"].cpu().to(dtype)
+    W = [w.to(dtype).requires_grad_() for w in W0]
+    X0 = feat[bottom["source"].cpu().long()]
+    Y0, _ = _max_agg(bottom, X0)
+    if root:
+        Y0 = torch.cat([Y0, feat[bottom["destination"].cpu().long()]], 1)
+    X1 = torch.relu(Y0 @ W[0])
+    Y1, gap = _max_agg(top, X1)
+    if root:
+        Y1 = torch.cat([Y1, X1[top["dst_local_id"].cpu().long()]], 1)
+    out = (Y1 @ W[1]).log_softmax(1)
+    tgt = data["labels"].cpu()[top["destination"].cpu().long()]
+    torch.nn.functional.nll_loss(out.log_softmax(1), tgt).backward()
+    return [w.grad for w in W], gap
+
+
+@pytest.mark.parametrize("root", [False, True], ids=["plain", "root_weight"])
+def test_one_training_step_gradients_keep_their_magnitude(E, data, root):
+    """The step above moves each weight by lr * 3.16 * sign(gradient) (epsilon =
+    1e-9): it checks signs.  Here the step reads the gradient out
+    (tests/step_check.py) and both weights' gradients are held to C times the
+    float32 chain's own error of float64 autograd (same winners: the gap is
+    asserted as above)."""
+    import step_check
+    from nts import host
+    cfg = step_check.readout(host.gcn_config(LAYERS, FANOUT, BATCH, drop_rate=0.0, shuffle=False,
+                                             aggregator="max", root_weight=root))
+    drv = E.GCN_SAMPLE_ALLGPU_impl(data["G"], data["feat"], data["labels"], data["train"], cfg)
+    W0 = [w.cpu().clone() for w in drv.weights()]
+    drv.train_batch()
+    drv.synchronize()
+    W1 = [w.cpu().clone() for w in drv.weights()]
+    g64, gap = _chain_grads(drv, data, W0, root, torch.float64)
+    g32, _ = _chain_grads(drv, data, W0, root, torch.float32)
+    print(f"max root={root}: top-hop gap {gap:.3e}")
+    assert gap > GAP, "the reference's winners are too close: pick another DATA_SEED"
+    step_check.check_step_grads(W0, W1, g64, g32, step_check.C)
+
+
 def _full_reference(data, W, root):
     g = data["g"]
     src, dst = g.src.cpu().numpy().astype(np.int64), g.dst.cpu().numpy().astype(np.int64)

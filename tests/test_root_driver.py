@@ -103,6 +103,41 @@ def test_one_training_step_matches_the_float64_chain(E, data, weight, fuse_loss,
         torch.testing.assert_close(w1.cpu().double(), r, rtol=1e-5, atol=1e-5)
 
 
+def _chain_grads(drv, data, W0, dtype):
+    """the gradients of _reference_step's chain in `dtype`"""
+    top, bottom = drv.last_layers
+    feat = data["feat"].cpu().to(dtype)
+    W = [w.to(dtype).requires_grad_() for w in W0]
+    X0 = feat[bottom["source"].cpu().long()]
+    X1 = torch.relu(torch.cat([_agg(bottom, X0), feat[bottom["destination"].cpu().long()]], 1) @ W[0])
+    out = (torch.cat([_agg(top, X1), X1[top["dst_local_id"].cpu().long()]], 1) @ W[1]).log_softmax(1)
+    tgt = data["labels"].cpu()[top["destination"].cpu().long()]
+    torch.nn.functional.nll_loss(out.log_softmax(1), tgt).backward()
+    return [w.grad for w in W]
+
+
+@pytest.mark.parametrize("fuse_loss", [True, False], ids=["fused_loss", "torch_loss"])
+@pytest.mark.parametrize("weight", ["sum", "mean"])
+def test_one_training_step_gradients_keep_their_magnitude(E, data, weight, fuse_loss):
+    """The step above moves each weight by lr * 3.16 * sign(gradient) (epsilon =
+    1e-9): it checks signs.  Here the step reads the gradient out
+    (tests/step_check.py) and both stacked weights' gradients are held to C
+    times the float32 chain's own error of float64 autograd."""
+    import step_check
+    from nts import host
+    cfg = step_check.readout(host.gcn_config(LAYERS, FANOUT, BATCH, drop_rate=0.0, shuffle=False,
+                                             root_weight=True, weight=weight, fuse_loss=fuse_loss))
+    drv = E.GCN_SAMPLE_ALLGPU_impl(data["G"], data["feat"], data["labels"], data["train"], cfg)
+    W0 = [w.cpu().clone() for w in drv.weights()]
+    drv.train_batch()
+    drv.synchronize()
+    W1 = [w.cpu().clone() for w in drv.weights()]
+    g64 = _chain_grads(drv, data, W0, torch.float64)
+    g32 = _chain_grads(drv, data, W0, torch.float32)
+    print(f"root {weight} fuse_loss={fuse_loss}")
+    step_check.check_step_grads(W0, W1, g64, g32, step_check.C)
+
+
 def _full_reference(data, W, mean):
     g = data["g"]
     src, dst = g.src.cpu().long(), g.dst.cpu().long()
