@@ -495,6 +495,38 @@ int nts_hip_gat_backward(nts_hip_ctx *ctx, const uint32_t *column_offset,
                          const float *att, const float *a, const float *m, const float *Y,
                          uint64_t ldy, const float *GY, uint64_t ldg, float *du, float *ds2,
                          float *GM, uint64_t ldm, float *dH, uint64_t lddh, float *dS);
+/* The multi-head layer: K = heads heads of D columns, F = K D.  Head h owns
+ * columns [hD, (h+1)D) of H, of a1 = att[0:F] and of a2 = att[F:2F], and has a
+ * softmax of its own over the edges of each destination:
+ *   m[e,h] = leaky_relu(H[src_e]_h . a1_h + H[dst_local(d)]_h . a2_h, 0.2),
+ *   a[e,h] = softmax over the edges of d of m[., h],  Z_h[d] = sum_e a[e,h] H[src_e]_h;
+ *   mean == 0 (concat): Y[d] = relu([Z_0 | ... | Z_{K-1}])   (F wide)
+ *   mean != 0:          Y[d] = relu((1/K) sum_h Z_h[d])      (D wide)
+ * m_out / a_out / du are edge-major [e, K], ds2 is [src_size, K], dS is
+ * [src_size, 2K] (ds1 of every head, then ds2 of every head: dW_att's a1 part
+ * is sum_v H[v,hD+j] dS[v,h], its a2 part the same with dS[v,K+h]).  Y and GY
+ * are F wide (concat) or D wide (mean); GM and dH are F wide, GM holding GY
+ * (mean: GY / K, for every head) masked by Y > 0.  The neighbour row is read
+ * once for all heads (one wave per destination / source, as above).  Width
+ * limit: F <= 1024 on the float4 path, which needs D % 4 == 0 besides the
+ * single-head rule on F, the pitches and the pointers; F <= 256 otherwise.
+ * heads == 0, D == 0 or a wider F return NTS_ERR_INVALID and write nothing
+ * (the backward's clearing of ds2 included).  heads == 1 computes the
+ * single-head layer (both modes). */
+int nts_hip_gat_forward_heads(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                              const uint32_t *row_indices, const uint32_t *dst_local_id,
+                              uint32_t v_size, const float *H, uint64_t ldh, uint32_t heads,
+                              uint32_t D, const float *att, float *m_out, float *a_out, float *Y,
+                              uint64_t ldy, int mean);
+int nts_hip_gat_backward_heads(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                               const uint32_t *row_indices, const uint32_t *dst_local_id,
+                               uint32_t v_size, const uint32_t *row_offset,
+                               const uint32_t *column_indices, const uint32_t *csr_edge_id,
+                               uint32_t src_size, const float *H, uint64_t ldh, uint32_t heads,
+                               uint32_t D, const float *att, const float *a, const float *m,
+                               const float *Y, uint64_t ldy, const float *GY, uint64_t ldg,
+                               float *du, float *ds2, float *GM, uint64_t ldm, float *dH,
+                               uint64_t lddh, float *dS, int mean);
 
 /* ---- dense layer update (MFMA fp32) -------------------------------------- */
 /* Row-major fp32 GEMM on the matrix cores (v_mfma_f32_16x16x4_f32 /

@@ -291,6 +291,385 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src(
   }
 }
 
+// ---- multi-head layer -----------------------------------------------------------
+// K heads of D columns, F = K D: head h owns columns [hD, (h+1)D) of H, a1 and
+// a2, and has its own softmax over each destination's edges.  The F-wide
+// neighbour row is still read once, by the same lane / chunk layout (vector
+// col = lane + 64 c); D % VEC == 0, so every vector lies in one head: head of
+// col = col / g with g = D / VEC lanes per head.  Each lane keeps one online
+// softmax state (running max, running sum) per chunk, that of the head its
+// vector of the chunk belongs to.  The per-head dot products are segmented
+// wave reductions (head_sums), by the shape of g:
+//   kHeadsPow2   g a power of two below 64: xor butterfly over o < g, log2(g)
+//                steps give every head's score at once;
+//   kHeadsChunk  g a multiple of 64: whole chunks belong to one head, the
+//                chunks of a head are added and reduced over the wave;
+//   kHeadsAny    anything else (heads that end inside a chunk): one masked
+//                wave reduction per head.
+// The per-edge arrays are edge-major ([e, K]); the lane holding the first
+// vector of a head (lead) writes that head's entries.
+enum { kHeadsPow2 = 0, kHeadsChunk = 1, kHeadsAny = 2 };
+
+// p[u][c]: this lane's partial dot product of row u in chunk c.  On return
+// p[u][c] is the sum over the whole head of (lane, c), in every lane of it.
+template <int MODE, int NCH, int U>
+__device__ __forceinline__ void head_sums(float (&p)[U][NCH], const uint32_t (&hc)[NCH],
+                                          uint32_t g, uint32_t heads) {
+  if (MODE == kHeadsPow2) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+      if ((uint32_t)o < g) {  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) p[u][c] += __shfl_xor(p[u][c], o, 64);
+      }
+  } else if (MODE == kHeadsChunk) {
+    float q[U][NCH];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        q[u][c] = 0.f;
+#pragma unroll
+        for (int c2 = 0; c2 < NCH; ++c2)
+          if (hc[c2] == hc[c]) q[u][c] += p[u][c2];  // wave-uniform: 64 | g
+      }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) q[u][c] += __shfl_xor(q[u][c], o, 64);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) p[u][c] = q[u][c];
+  } else {
+    float q[U][NCH];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) q[u][c] = 0.f;
+    for (uint32_t h = 0; h < heads; ++h) {
+      float t[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        t[u] = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) t[u] += hc[c] == h ? p[u][c] : 0.f;
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1)
+#pragma unroll
+        for (int u = 0; u < U; ++u) t[u] += __shfl_xor(t[u], o, 64);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+          if (hc[c] == h) q[u][c] = t[u];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) p[u][c] = q[u][c];
+  }
+}
+
+template <int VEC, int NCH, int MODE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
+    const uint32_t* __restrict__ co, const uint32_t* __restrict__ ri,
+    const uint32_t* __restrict__ dl, uint32_t nv_dst, const float* __restrict__ H, uint64_t ldh,
+    uint32_t nvec, uint32_t g, uint32_t heads, const float* __restrict__ att,
+    float* __restrict__ m_out, float* __restrict__ a_out, float* __restrict__ Y, uint64_t ldy,
+    int mean) {
+  using G = GV<VEC>;
+  using T = typename G::T;
+  // mean mode only (dynamic LDS, none in concat mode): the wave's normalised
+  // row, NCH * 64 vectors, for the sum over heads
+  extern __shared__ float4 gat_heads_lds[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  T* zrow = reinterpret_cast<T*>(gat_heads_lds) + wave * (NCH * 64);
+  const uint32_t d = blockIdx.x * (kGatThreads / 64) + wave;
+  if (d >= nv_dst) return;
+  const T* a1 = reinterpret_cast<const T*>(att);
+  const T* a2 = reinterpret_cast<const T*>(att + (uint64_t)nvec * VEC);
+  const T* hd = reinterpret_cast<const T*>(H + (uint64_t)dl[d] * ldh);
+  T w1[NCH];
+  uint32_t hc[NCH];
+  bool lead[NCH];
+  float s2[1][NCH];  // score of the destination's own row, per head
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const uint32_t col = lane + 64 * c;
+    hc[c] = col / g;
+    lead[c] = col < nvec && col == hc[c] * g;
+    w1[c] = col < nvec ? a1[col] : G::zero();
+    s2[0][c] = col < nvec ? G::dot(hd[col], a2[col]) : 0.f;
+  }
+  head_sums<MODE, NCH, 1>(s2, hc, g, heads);
+  const uint32_t beg = co[d], end = co[d + 1];
+  T acc[NCH];
+  float M[NCH], S[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    acc[c] = G::zero();
+    M[c] = -INFINITY;
+    S[c] = 0.f;
+  }
+  for (uint32_t cb = beg; cb < end; cb += 64) {
+    const uint32_t ne = min(end - cb, 64u);
+    const uint32_t my_r = lane < (int)ne ? ri[cb + lane] : 0u;
+    for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {  // kGatU neighbour rows in flight
+      T x[kGatU][NCH];
+      float p1[kGatU][NCH];
+#pragma unroll
+      for (int u = 0; u < kGatU; ++u) {
+        const bool ok = j0 + u < ne;
+        const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+        const T* hr = reinterpret_cast<const T*>(H + (uint64_t)r * ldh);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const uint32_t col = lane + 64 * c;
+          x[u][c] = (ok && col < nvec) ? hr[col] : G::zero();
+          p1[u][c] = G::dot(x[u][c], w1[c]);
+        }
+      }
+      head_sums<MODE, NCH, kGatU>(p1, hc, g, heads);
+#pragma unroll
+      for (int u = 0; u < kGatU; ++u) {
+        if (j0 + u >= ne) break;
+        const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const float m = leaky(p1[u][c] + s2[0][c]);
+          if (lead[c]) m_out[eb + hc[c]] = m;
+          const float Mn = fmaxf(M[c], m);
+          const float sc = expf(M[c] - Mn);  // 0 for the first edge (M = -inf)
+          const float p = expf(m - Mn);
+          S[c] = S[c] * sc + p;
+          acc[c] = G::axpy(G::scale(acc[c], sc), p, x[u][c]);
+          M[c] = Mn;
+        }
+      }
+    }
+  }
+  float inv[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    inv[c] = S[c] > 0.f ? 1.f / S[c] : 0.f;
+    acc[c] = G::scale(acc[c], inv[c]);
+  }
+  T* y = reinterpret_cast<T*>(Y + (uint64_t)d * ldy);
+  if (!mean) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const uint32_t col = lane + 64 * c;
+      if (col < nvec) y[col] = G::relu(acc[c]);
+    }
+  } else {  // Y[d] = relu(mean over heads), heads added in order
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const uint32_t col = lane + 64 * c;
+      if (col < nvec) zrow[col] = acc[c];
+    }
+    // the row is the wave's own: its LDS writes are ordered before its reads
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float rk = 1.f / (float)heads;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const uint32_t col = lane + 64 * c;
+      if (col < g) {
+        T t = zrow[col];
+        for (uint32_t h = 1; h < heads; ++h) t = G::axpy(t, 1.f, zrow[h * g + col]);
+        y[col] = G::relu(G::scale(t, rk));
+      }
+    }
+  }
+  // attention coefficients (needed by the backward): each head's lead lane
+  // reads back the scores it wrote
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    if (lead[c]) {
+#pragma unroll 4
+      for (uint32_t e = beg; e < end; ++e) {
+        const uint64_t i = (uint64_t)e * heads + hc[c];
+        a_out[i] = expf(m_out[i] - M[c]) * inv[c];
+      }
+    }
+}
+
+template <int VEC, int NCH, int MODE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
+    const uint32_t* __restrict__ co, const uint32_t* __restrict__ ri,
+    const uint32_t* __restrict__ dl, uint32_t nv_dst, const float* __restrict__ H, uint64_t ldh,
+    uint32_t nvec, uint32_t g, uint32_t heads, const float* __restrict__ a,
+    const float* __restrict__ m, const float* __restrict__ Y, uint64_t ldy,
+    const float* __restrict__ GY, uint64_t ldg, float* __restrict__ du, float* __restrict__ ds2,
+    float* __restrict__ GM, uint64_t ldm, int mean) {
+  using G = GV<VEC>;
+  using T = typename G::T;
+  const int lane = threadIdx.x & 63;
+  const uint32_t d = blockIdx.x * (kGatThreads / 64) + (threadIdx.x >> 6);
+  if (d >= nv_dst) return;
+  const T* gy = reinterpret_cast<const T*>(GY + (uint64_t)d * ldg);
+  const T* yy = reinterpret_cast<const T*>(Y + (uint64_t)d * ldy);
+  T* gm = reinterpret_cast<T*>(GM + (uint64_t)d * ldm);
+  const float rk = 1.f / (float)heads;
+  T gv[NCH];
+  uint32_t hc[NCH];
+  bool lead[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const uint32_t col = lane + 64 * c;
+    hc[c] = col / g;
+    lead[c] = col < nvec && col == hc[c] * g;
+    gv[c] = G::zero();
+    if (col < nvec) {
+      // mean mode: every head gets GY / K under the mask of the D-wide Y
+      const uint32_t q = mean ? col - hc[c] * g : col;
+      gv[c] = G::mask(gy[q], yy[q]);
+      if (mean) gv[c] = G::scale(gv[c], rk);
+      gm[col] = gv[c];  // read per edge by k_gat_bwd_src_heads
+    }
+  }
+  const uint32_t beg = co[d], end = co[d + 1];
+  // pass 1: ga[e, h] = g_h . H[src_e]_h, parked in du by the head's lead lane,
+  // which also sums a ga in edge order
+  float sag[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) sag[c] = 0.f;
+  for (uint32_t cb = beg; cb < end; cb += 64) {
+    const uint32_t ne = min(end - cb, 64u);
+    const uint32_t my_r = lane < (int)ne ? ri[cb + lane] : 0u;
+    for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {
+      float p[kGatU][NCH], av[kGatU][NCH];
+#pragma unroll
+      for (int u = 0; u < kGatU; ++u) {
+        const bool ok = j0 + u < ne;
+        const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+        const T* hr = reinterpret_cast<const T*>(H + (uint64_t)r * ldh);
+        const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const uint32_t col = lane + 64 * c;
+          p[u][c] = (ok && col < nvec) ? G::dot(gv[c], hr[col]) : 0.f;
+          av[u][c] = (ok && lead[c]) ? a[eb + hc[c]] : 0.f;
+        }
+      }
+      head_sums<MODE, NCH, kGatU>(p, hc, g, heads);
+#pragma unroll
+      for (int u = 0; u < kGatU; ++u) {
+        if (j0 + u >= ne) break;
+        const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+          if (lead[c]) {
+            du[eb + hc[c]] = p[u][c];
+            sag[c] += av[u][c] * p[u][c];
+          }
+      }
+    }
+  }
+  // pass 2: softmax and leaky_relu backward, per head by its lead lane
+  const uint64_t dd = (uint64_t)dl[d] * heads;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    if (lead[c]) {
+      float s = 0.f;
+#pragma unroll 4
+      for (uint32_t e = beg; e < end; ++e) {
+        const uint64_t i = (uint64_t)e * heads + hc[c];
+        const float dm = a[i] * (du[i] - sag[c]);
+        const float u = m[i] > 0.f ? dm : 0.2f * dm;
+        du[i] = u;
+        s += u;
+      }
+      ds2[dd + hc[c]] = s;
+    }
+}
+
+template <int VEC, int NCH, int = 0>  // (no reduction here: one form for every g)
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src_heads(
+    const uint32_t* __restrict__ ro, const uint32_t* __restrict__ ci,
+    const uint32_t* __restrict__ ceid, uint32_t nv_src, uint32_t nvec, uint32_t g, uint32_t heads,
+    const float* __restrict__ a, const float* __restrict__ du, const float* __restrict__ ds2,
+    const float* __restrict__ att, const float* __restrict__ GM, uint64_t ldm,
+    float* __restrict__ dH, uint64_t lddh, float* __restrict__ dS) {
+  using G = GV<VEC>;
+  using T = typename G::T;
+  const int lane = threadIdx.x & 63;
+  const uint32_t v = blockIdx.x * (kGatThreads / 64) + (threadIdx.x >> 6);
+  if (v >= nv_src) return;
+  uint32_t hc[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) hc[c] = (lane + 64 * c) / g;
+  const uint32_t beg = ro[v], end = ro[v + 1];
+  T acc[NCH];
+  float s1[NCH];  // every lane sums its head's du in edge order: no reduction
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    acc[c] = G::zero();
+    s1[c] = 0.f;
+  }
+  for (uint32_t cb = beg; cb < end; cb += 64) {
+    const uint32_t ne = min(end - cb, 64u);
+    uint32_t my_d = 0, my_e = 0;
+    if (lane < (int)ne) {
+      my_e = ceid[cb + lane];
+      my_d = ci[cb + lane];
+    }
+    for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {
+      T x[kGatU][NCH];
+      float w[kGatU][NCH], uu[kGatU][NCH];
+#pragma unroll
+      for (int u = 0; u < kGatU; ++u) {
+        const bool ok = j0 + u < ne;
+        const int jj = (int)min(j0 + u, ne - 1);
+        const uint32_t dd = (uint32_t)__shfl((int)my_d, jj, 64);
+        const uint64_t eb = (uint64_t)(uint32_t)__shfl((int)my_e, jj, 64) * heads;
+        const T* gm = reinterpret_cast<const T*>(GM + (uint64_t)dd * ldm);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+          const uint32_t col = lane + 64 * c;
+          const bool in = ok && col < nvec;
+          x[u][c] = in ? gm[col] : G::zero();
+          w[u][c] = in ? a[eb + hc[c]] : 0.f;
+          uu[u][c] = in ? du[eb + hc[c]] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kGatU; ++u)
+        if (j0 + u < ne) {  // edge order kept
+#pragma unroll
+          for (int c = 0; c < NCH; ++c) {
+            acc[c] = G::axpy(acc[c], w[u][c], x[u][c]);
+            s1[c] += uu[u][c];
+          }
+        }
+    }
+  }
+  const T* a1 = reinterpret_cast<const T*>(att);
+  const T* a2 = reinterpret_cast<const T*>(att + (uint64_t)nvec * VEC);
+  T* out = reinterpret_cast<T*>(dH + (uint64_t)v * lddh);
+  float* ds = dS + 2 * (uint64_t)v * heads;
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const uint32_t col = lane + 64 * c;
+    if (col < nvec) {
+      const float s2 = ds2[(uint64_t)v * heads + hc[c]];
+      out[col] = G::axpy(G::axpy(acc[c], s1[c], a1[col]), s2, a2[col]);
+      if (col == hc[c] * g) {
+        ds[hc[c]] = s1[c];
+        ds[heads + hc[c]] = s2;
+      }
+    }
+  }
+}
+
 static bool gat_vec4(uint32_t F, uint64_t l1, uint64_t l2, const void* p1, const void* p2,
                      const void* att) {
   return F % 4 == 0 && l1 % 4 == 0 && l2 % 4 == 0 && ((uintptr_t)p1 % 16) == 0 &&
@@ -330,7 +709,135 @@ static const char kGatWidthMsg[] =
     NTS_LAUNCH_CHECK();                                                                  \
   } while (0)
 
+// ---- multi-head entry points: checks and dispatch ---------------------------------
+static const char kGatHeadsWidthMsg[] =
+    "feature width too large (F = heads * D <= 1024 on 16-byte aligned rows with pitches that "
+    "are multiples of 4 and D a multiple of 4, F <= 256 otherwise)";
+
+namespace {
+struct HeadsShape {
+  uint32_t nvec, g;
+  int nch, mode;
+};
+// the shape of a (heads, D) layer on the float4 (v4) or the scalar path
+HeadsShape heads_shape(uint32_t heads, uint32_t D, bool v4) {
+  HeadsShape s;
+  s.g = v4 ? D / 4 : D;
+  s.nvec = heads * s.g;
+  s.nch = (int)((s.nvec + 63) / 64);
+  s.mode = (s.g < 64 && (s.g & (s.g - 1)) == 0) ? kHeadsPow2
+           : s.g % 64 == 0                      ? kHeadsChunk
+                                                : kHeadsAny;
+  return s;
+}
+}  // namespace
+
+#define NTS_GAT_HEADS_NCH(KERNEL, V, ...)                                                       \
+  switch (hs.nch) {                                                                             \
+    case 1: hipLaunchKernelGGL((KERNEL<V, 1, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    case 2: hipLaunchKernelGGL((KERNEL<V, 2, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    case 3: hipLaunchKernelGGL((KERNEL<V, 3, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    default: hipLaunchKernelGGL((KERNEL<V, 4, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+  }
+#define NTS_GAT_HEADS_MODE(KERNEL, V)                                     \
+  switch (hs.mode) {                                                      \
+    case kHeadsPow2: NTS_GAT_HEADS_NCH(KERNEL, V, kHeadsPow2) break;      \
+    case kHeadsChunk: NTS_GAT_HEADS_NCH(KERNEL, V, kHeadsChunk) break;    \
+    default: NTS_GAT_HEADS_NCH(KERNEL, V, kHeadsAny) break;               \
+  }
+// KERNEL<VEC, NCH, MODE> over n waves (hs, v4, st, lds and ARGS in scope)
+#define NTS_GAT_HEADS_DISPATCH(KERNEL)                                    \
+  do {                                                                    \
+    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));         \
+    if (v4) {                                                             \
+      NTS_GAT_HEADS_MODE(KERNEL, 4)                                       \
+    } else {                                                              \
+      NTS_GAT_HEADS_MODE(KERNEL, 1)                                       \
+    }                                                                     \
+    NTS_LAUNCH_CHECK();                                                   \
+  } while (0)
+
 extern "C" {
+
+int nts_hip_gat_forward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                              const uint32_t* row_indices, const uint32_t* dst_local_id,
+                              uint32_t v_size, const float* H, uint64_t ldh, uint32_t heads,
+                              uint32_t D, const float* att, float* m_out, float* a_out, float* Y,
+                              uint64_t ldy, int mean) {
+  NTS_CHECK_ARG(ctx && column_offset && row_indices && dst_local_id && H && att && m_out &&
+                    a_out && Y,
+                "NULL argument");
+  NTS_CHECK_ARG(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
+  NTS_CHECK_ARG((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  const uint32_t F = heads * D, FY = mean ? D : F;
+  NTS_CHECK_ARG(ldh >= F && ldy >= FY, "leading dimension");
+  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att);
+  const HeadsShape hs = heads_shape(heads, D, v4);
+  NTS_CHECK_ARG(hs.nch <= 4, kGatHeadsWidthMsg);
+  if (v_size == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const uint32_t n = v_size;
+  // mean mode: one row of nch * 64 vectors per wave (16 KiB a block at VEC 4, NCH 4)
+  const size_t lds = mean ? (size_t)(kGatThreads / 64) * hs.nch * 64 * (v4 ? 16 : 4) : 0;
+#define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, att, \
+             m_out, a_out, Y, ldy, mean
+  NTS_GAT_HEADS_DISPATCH(k_gat_fwd_heads);
+#undef ARGS
+  return NTS_OK;
+}
+
+int nts_hip_gat_backward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                               const uint32_t* row_indices, const uint32_t* dst_local_id,
+                               uint32_t v_size, const uint32_t* row_offset,
+                               const uint32_t* column_indices, const uint32_t* csr_edge_id,
+                               uint32_t src_size, const float* H, uint64_t ldh, uint32_t heads,
+                               uint32_t D, const float* att, const float* a, const float* m,
+                               const float* Y, uint64_t ldy, const float* GY, uint64_t ldg,
+                               float* du, float* ds2, float* GM, uint64_t ldm, float* dH,
+                               uint64_t lddh, float* dS, int mean) {
+  NTS_CHECK_ARG(ctx && column_offset && row_indices && dst_local_id && row_offset &&
+                    column_indices && csr_edge_id && H && att && a && m && Y && GY && du &&
+                    ds2 && GM && dH && dS,
+                "NULL argument");
+  NTS_CHECK_ARG(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
+  NTS_CHECK_ARG((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  const uint32_t F = heads * D, FY = mean ? D : F;
+  NTS_CHECK_ARG(ldm >= F, "leading dimension of GM");
+  NTS_CHECK_ARG(ldh >= F && ldy >= FY && ldg >= FY && lddh >= F, "leading dimension");
+  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 &&
+                  lddh % 4 == 0 && ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 &&
+                  ((uintptr_t)dH % 16) == 0 && ((uintptr_t)GM % 16) == 0;
+  const HeadsShape hs = heads_shape(heads, D, v4);
+  // a refused shape leaves every output as it was: checked before ds2 is cleared
+  NTS_CHECK_ARG(hs.nch <= 4, kGatHeadsWidthMsg);
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const size_t lds = 0;  // the backward kernels use no LDS
+  if (src_size)
+    NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * heads * sizeof(float), st));
+  if (v_size) {
+    const uint32_t n = v_size;
+#define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, a, m, \
+             Y, ldy, GY, ldg, du, ds2, GM, ldm, mean
+    NTS_GAT_HEADS_DISPATCH(k_gat_bwd_dst_heads);
+#undef ARGS
+  }
+  if (src_size) {
+    const uint32_t n = src_size;
+    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));
+#define ARGS row_offset, column_indices, csr_edge_id, src_size, hs.nvec, hs.g, heads, a, du, ds2, \
+             att, GM, ldm, dH, lddh, dS
+    if (v4) {
+      NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 4, 0)
+    } else {
+      NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 1, 0)
+    }
+#undef ARGS
+    NTS_LAUNCH_CHECK();
+  }
+  return NTS_OK;
+}
 
 int nts_hip_gat_forward(nts_hip_ctx* ctx, const uint32_t* column_offset,
                         const uint32_t* row_indices, const uint32_t* dst_local_id,

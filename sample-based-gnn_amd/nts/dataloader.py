@@ -269,6 +269,17 @@ def _aggregator(value: str) -> str:
     return v
 
 
+def _gat_heads(value: str) -> list:
+    try:
+        heads = [int(x) for x in value.strip().split("-")]
+    except ValueError:
+        heads = []
+    if not heads or min(heads) < 1:
+        raise ValueError(f"GAT_HEADS:{value}: head counts >= 1, one per layer, dash-separated "
+                         "(8-1)")
+    return heads
+
+
 @dataclass
 class InputInfo:
     """InputInfo (core/GraphSegment.h:156-244) — the cfg keys of Appendix C."""
@@ -305,6 +316,11 @@ class InputInfo:
     # weight type, the default) or max (GraphSAGE's max aggregator; the weight
     # type is then ignored; GCN / GraphSAGE algorithms without PD cache)
     aggregator: str = "sum"
+    # GAT_HEADS (this build's key): attention heads per layer, bottom first,
+    # dash-separated like LAYERS (8-1); hidden layers concatenate their heads
+    # (LAYERS keeps the concatenated width), the last layer averages them.
+    # GAT algorithms only; absent = single-head
+    gat_heads: list = field(default_factory=list)
     extra: dict = field(default_factory=dict)
 
     @property
@@ -333,6 +349,7 @@ class InputInfo:
             "MULTI_LABEL": ("multi_label", int),
             "ROOT_WEIGHT": ("root_weight", int),
             "AGGREGATOR": ("aggregator", _aggregator),
+            "GAT_HEADS": ("gat_heads", _gat_heads),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -129,6 +129,33 @@ class HipContext:
             F, ptr(att), ptr(a), ptr(m), ptr(Y), Y.stride(0), ptr(GY), GY.stride(0), ptr(du), ptr(ds2),
             ptr(GM), GM.stride(0), ptr(dH), dH.stride(0), ptr(dS)))
 
+    def gat_forward_heads(self, co, ri, dl, v, H, heads, att, m, a, Y, mean=False):
+        """The multi-head layer: H [s, heads * D], att [2 heads D], m / a [e, heads]
+        (edge-major); Y [v, heads * D] (concat) or [v, D] (mean over heads)."""
+        heads = int(heads)
+        D = H.shape[1] // heads if heads > 0 else H.shape[1]
+        if heads > 0 and D * heads != H.shape[1]:
+            raise ValueError(f"gat_forward_heads: {heads} heads do not divide width {H.shape[1]}")
+        check(self.lib.nts_hip_gat_forward_heads(
+            self.h, ptr(co), ptr(ri), ptr(dl), v, ptr(H), H.stride(0), heads, D, ptr(att), ptr(m),
+            ptr(a), ptr(Y), Y.stride(0), int(bool(mean))))
+
+    def gat_backward_heads(self, co, ri, dl, v, ro, ci, ceid, s, H, heads, att, a, m, Y, GY, du, ds2,
+                           dH, dS, GM=None, mean=False):
+        """Its backward: du [e, heads], ds2 [s, heads], dS [s, 2 heads] (ds1 of
+        every head, then ds2), GM [v, heads * D], dH [s, heads * D]."""
+        heads = int(heads)
+        F = H.shape[1]
+        D = F // heads if heads > 0 else F
+        if heads > 0 and D * heads != F:
+            raise ValueError(f"gat_backward_heads: {heads} heads do not divide width {F}")
+        if GM is None:
+            GM = torch.empty(max(v, 1), F, device=H.device)
+        check(self.lib.nts_hip_gat_backward_heads(
+            self.h, ptr(co), ptr(ri), ptr(dl), v, ptr(ro), ptr(ci), ptr(ceid), s, ptr(H), H.stride(0),
+            heads, D, ptr(att), ptr(a), ptr(m), ptr(Y), Y.stride(0), ptr(GY), GY.stride(0), ptr(du),
+            ptr(ds2), ptr(GM), GM.stride(0), ptr(dH), dH.stride(0), ptr(dS), int(bool(mean))))
+
     def gather_labels(self, labels, index, n_dev, n_cap, out):
         check(self.lib.nts_hip_gather_labels(self.h, ptr(labels), ptr(index), ptr(n_dev),
                                              n_cap, ptr(out)))

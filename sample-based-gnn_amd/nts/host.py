@@ -32,6 +32,35 @@ def ext():
     return _ext
 
 
+def check_gat_heads(layers, gat, gat_heads):
+    """gat_heads as a list of ints (empty: single-head), or a ValueError that
+    names the option: one entry >= 1 per layer, bottom first, with gat only;
+    a hidden layer's width is split into its heads, the last layer's heads
+    (of layers[-1] columns each) are averaged.  K heads of D columns need
+    K D <= 1024 when D is a multiple of 4, else K D <= 256 (the kernels' limit)."""
+    if gat_heads is None:
+        return []
+    heads = [int(k) for k in gat_heads]
+    layers = list(layers)
+    if not heads:
+        return []
+    if not gat:
+        raise ValueError("gat_heads is not supported without gat (attention layers only)")
+    if len(heads) != len(layers) - 1:
+        raise ValueError(f"gat_heads needs one entry per layer ({len(layers) - 1}), got {len(heads)}")
+    for l, k in enumerate(heads):
+        if k < 1:
+            raise ValueError(f"gat_heads[{l}] must be >= 1, got {k}")
+        last = l == len(heads) - 1
+        if not last and layers[l + 1] % k:
+            raise ValueError(f"gat_heads[{l}] = {k} does not divide layer width {layers[l + 1]}")
+        d = layers[l + 1] if last else layers[l + 1] // k
+        if k > 1 and k * d > (1024 if d % 4 == 0 else 256):
+            raise ValueError(f"gat_heads[{l}] = {k} heads of {d} columns: K D = {k * d} is outside "
+                             "the kernels' width limit (1024 when D is a multiple of 4, else 256)")
+    return heads
+
+
 def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, drop_rate=0.5,
                rng_mode=_abi.NTS_RNG_PHILOX, weight="sum", fused_gather=True,
                bias_correction=False, deterministic_backward=True, shuffle=True, profile=False,
@@ -40,9 +69,11 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                fuse_loss=True, sampler_cus=0, sampler_gate=0, pad_features=True, cache_rate=-1.0,
                up_degree=False, gat=False, pd_cache=False, pd_rate=0.2, pd_super_batch=4,
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
-               multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9):
+               multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
+               gat_heads=None):
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
+    gat_heads = check_gat_heads(layers, gat, gat_heads)
     E = ext()
     c = E.GCNConfig()
     c.layer_size = list(layers)
@@ -79,6 +110,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.cache_rate = float(cache_rate)
     c.up_degree = bool(up_degree)
     c.gat = bool(gat)
+    c.gat_heads = gat_heads
     c.pd_cache = bool(pd_cache)
     c.pd_rate = float(pd_rate)
     c.pd_super_batch = int(pd_super_batch)

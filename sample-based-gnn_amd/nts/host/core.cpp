@@ -1356,14 +1356,24 @@ void KernelProfiler::reset() {
 // the fused attention/softmax/aggregation/relu kernel; the backward runs the
 // two deterministic GAT backward passes and three GEMMs (dW = X^T dH,
 // dW_att = H^T dS, dX = dH W^T).
+// heads > 1: the multi-head entry points (K heads of D = F / K columns; Y is
+// their concatenation, or with `mean` their mean, D wide).  dW_att is then the
+// same TN GEMM with N = 2K, T = H^T dS [F, 2K], of which head h's rows keep
+// columns h and K + h (the other columns, products of one head's rows with
+// another head's dS, are dropped): the GEMM is the MFMA kernel that is there,
+// deterministic, and at K <= 8 its 2K columns still fill one 16-column tile.
 struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
   static NtsVar forward(AutogradContext* ctx, NtsVar X, NtsVar W, NtsVar Watt, int64_t sg_ptr,
-                        int64_t cs_ptr, int64_t prof_ptr) {
+                        int64_t cs_ptr, int64_t prof_ptr, int64_t heads, bool mean) {
     auto* sg = reinterpret_cast<sampCSC*>(sg_ptr);
     auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
     auto* prof = reinterpret_cast<KernelProfiler*>(prof_ptr);
     TORCH_CHECK(sg->dst_local_id.defined() && sg->csr_edge_id.defined(),
                 "GAT needs a merged src/dst layer with its CSR (set_merge_src_dst)");
+    TORCH_CHECK(heads >= 1 && W.size(1) % heads == 0, "GAT layer: ", heads,
+                " heads do not divide width ", W.size(1));
+    const int64_t K = heads, D = W.size(1) / heads;
+    if (K == 1) mean = false;  // one head: both modes are the single-head layer
     NtsVar Xc = row_major(X), Wc = W.contiguous(), Ac = Watt.contiguous();
     const int64_t s = sg->src_size, v = sg->v_size, e = sg->e_size;
     const int64_t Fin = Xc.size(1), F = Wc.size(1);
@@ -1374,22 +1384,35 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                                (uint64_t)Xc.stride(0), Wc.data_ptr<float>(), (uint64_t)F,
                                H.data_ptr<float>(), (uint64_t)F),
               "nts_hip_gemm_f32(H)");
-    NtsVar m = torch::empty({std::max<int64_t>(e, 1)}, f32_opts(dev));
-    NtsVar a = torch::empty({std::max<int64_t>(e, 1)}, f32_opts(dev));
-    NtsVar Y = torch::empty({v, F}, f32_opts(dev));
+    NtsVar m = torch::empty({std::max<int64_t>(e, 1) * K}, f32_opts(dev));
+    NtsVar a = torch::empty({std::max<int64_t>(e, 1) * K}, f32_opts(dev));
+    const int64_t FY = mean ? D : F;
+    NtsVar Y = torch::empty({v, FY}, f32_opts(dev));
     hipStream_t st = (hipStream_t)cs->stream();
     if (prof) prof->begin(KernelProfiler::GAT_FWD, st);
-    hip_check(nts_hip_gat_forward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
-                                  (uint32_t)v, H.data_ptr<float>(), (uint64_t)F, (uint32_t)F,
-                                  Ac.data_ptr<float>(), m.data_ptr<float>(), a.data_ptr<float>(),
-                                  Y.data_ptr<float>(), (uint64_t)F),
-              "nts_hip_gat_forward");
+    if (K == 1)
+      hip_check(nts_hip_gat_forward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
+                                    (uint32_t)v, H.data_ptr<float>(), (uint64_t)F, (uint32_t)F,
+                                    Ac.data_ptr<float>(), m.data_ptr<float>(), a.data_ptr<float>(),
+                                    Y.data_ptr<float>(), (uint64_t)F),
+                "nts_hip_gat_forward");
+    else
+      hip_check(nts_hip_gat_forward_heads(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(),
+                                          sg->dev_dst_local_id(), (uint32_t)v, H.data_ptr<float>(),
+                                          (uint64_t)F, (uint32_t)K, (uint32_t)D,
+                                          Ac.data_ptr<float>(), m.data_ptr<float>(),
+                                          a.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)FY,
+                                          mean ? 1 : 0),
+                "nts_hip_gat_forward_heads");
     // compulsory bytes: H rows once, offsets, row index + score + weight per
     // edge, dst local ids, W_att, output rows
     if (prof)
       prof->end(KernelProfiler::GAT_FWD, st,
-                4.0 * F * s + 4.0 * (v + 1) + 12.0 * e + 4.0 * v + 8.0 * F + 4.0 * F * v);
+                4.0 * F * s + 4.0 * (v + 1) + (4.0 + 8.0 * K) * e + 4.0 * v + 8.0 * F +
+                    4.0 * FY * v);
     ctx->save_for_backward({Xc, Wc, Ac, H, Y, m, a});
+    ctx->saved_data["heads"] = K;
+    ctx->saved_data["mean"] = mean;
     ctx->saved_data["sg"] = sg_ptr;
     ctx->saved_data["cs"] = cs_ptr;
     ctx->saved_data["x_grad"] = X.requires_grad();
@@ -1404,31 +1427,52 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     NtsVar GY = grads[0].contiguous();
     const int64_t s = H.size(0), F = H.size(1), Fin = X.size(1), v = Y.size(0);
     const int64_t e = sg->e_size;
+    const int64_t K = ctx->saved_data["heads"].toInt(), D = F / K;
+    const bool mean = ctx->saved_data["mean"].toBool();
+    const int64_t FY = mean ? D : F;
     const int dev = cs->device();
     auto guard = cs->guard();
-    NtsVar du = torch::empty({std::max<int64_t>(e, 1)}, f32_opts(dev));
-    NtsVar ds2 = torch::empty({std::max<int64_t>(s, 1)}, f32_opts(dev));
+    NtsVar du = torch::empty({std::max<int64_t>(e, 1) * K}, f32_opts(dev));
+    NtsVar ds2 = torch::empty({std::max<int64_t>(s, 1) * K}, f32_opts(dev));
     NtsVar dH = torch::empty({s, F}, f32_opts(dev));
-    NtsVar dS = torch::empty({s, 2}, f32_opts(dev));
+    NtsVar dS = torch::empty({s, 2 * K}, f32_opts(dev));
     NtsVar GM = torch::empty({std::max<int64_t>(v, 1), F}, f32_opts(dev));
-    hip_check(nts_hip_gat_backward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
-                                   (uint32_t)v, sg->dev_r_o(), sg->dev_c_i(),
-                                   dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s, H.data_ptr<float>(),
-                                   (uint64_t)F, (uint32_t)F, A.data_ptr<float>(), a.data_ptr<float>(),
-                                   m.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)F,
-                                   GY.data_ptr<float>(), (uint64_t)F, du.data_ptr<float>(),
-                                   ds2.data_ptr<float>(), GM.data_ptr<float>(), (uint64_t)F,
-                                   dH.data_ptr<float>(), (uint64_t)F, dS.data_ptr<float>()),
-              "nts_hip_gat_backward");
+    if (K > 1)
+      hip_check(nts_hip_gat_backward_heads(
+                    cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
+                    sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
+                    H.data_ptr<float>(), (uint64_t)F, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(),
+                    a.data_ptr<float>(), m.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)FY,
+                    GY.data_ptr<float>(), (uint64_t)FY, du.data_ptr<float>(), ds2.data_ptr<float>(),
+                    GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(), (uint64_t)F,
+                    dS.data_ptr<float>(), mean ? 1 : 0),
+                "nts_hip_gat_backward_heads");
+    else
+      hip_check(nts_hip_gat_backward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
+                                     (uint32_t)v, sg->dev_r_o(), sg->dev_c_i(),
+                                     dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
+                                     H.data_ptr<float>(), (uint64_t)F, (uint32_t)F,
+                                     A.data_ptr<float>(), a.data_ptr<float>(), m.data_ptr<float>(),
+                                     Y.data_ptr<float>(), (uint64_t)F, GY.data_ptr<float>(),
+                                     (uint64_t)F, du.data_ptr<float>(), ds2.data_ptr<float>(),
+                                     GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(),
+                                     (uint64_t)F, dS.data_ptr<float>()),
+                "nts_hip_gat_backward");
     NtsVar dW = torch::empty({Fin, F}, f32_opts(dev));
     hip_check(nts_hip_gemm_f32(cs->ctx(), 1, (int)Fin, (int)F, (int)s, X.data_ptr<float>(),
                                (uint64_t)X.stride(0), dH.data_ptr<float>(), (uint64_t)F,
                                dW.data_ptr<float>(), (uint64_t)F),
               "nts_hip_gemm_f32(dW)");
-    NtsVar T = torch::empty({F, 2}, f32_opts(dev));
-    hip_check(nts_hip_gemm_f32(cs->ctx(), 1, (int)F, 2, (int)s, H.data_ptr<float>(), (uint64_t)F,
-                               dS.data_ptr<float>(), 2, T.data_ptr<float>(), 2),
+    NtsVar T = torch::empty({F, 2 * K}, f32_opts(dev));
+    hip_check(nts_hip_gemm_f32(cs->ctx(), 1, (int)F, (int)(2 * K), (int)s, H.data_ptr<float>(),
+                               (uint64_t)F, dS.data_ptr<float>(), (uint64_t)(2 * K),
+                               T.data_ptr<float>(), (uint64_t)(2 * K)),
               "nts_hip_gemm_f32(dW_att)");
+    if (K > 1) {  // row hD + j keeps columns h (a1) and K + h (a2)
+      NtsVar h = torch::arange(F, torch::TensorOptions().dtype(torch::kInt64).device(T.device()))
+                     .floor_divide(D);
+      T = T.gather(1, torch::stack({h, h + K}, 1));
+    }
     NtsVar dA = T.t().contiguous().view({2 * F, 1});  // [a1 | a2] as W_att's rows
     NtsVar dX;
     if (ctx->saved_data["x_grad"].toBool()) {
@@ -1439,14 +1483,15 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                                  dX.data_ptr<float>(), (uint64_t)Fin),
                 "nts_hip_gemm_f32(dX)");
     }
-    return {dX, dW, dA.view(A.sizes()), NtsVar(), NtsVar(), NtsVar()};
+    return {dX, dW, dA.view(A.sizes()), NtsVar(), NtsVar(), NtsVar(), NtsVar(), NtsVar()};
   }
 };
 
 NtsVar hip_gat_layer(const NtsVar& x, const NtsVar& W, const NtsVar& Watt, sampCSC* sg,
-                     NtsStream* cs, KernelProfiler* prof) {
+                     NtsStream* cs, KernelProfiler* prof, int heads, bool mean) {
   return HipGATLayerFn::apply(x, W, Watt, reinterpret_cast<int64_t>(sg),
-                              reinterpret_cast<int64_t>(cs), reinterpret_cast<int64_t>(prof));
+                              reinterpret_cast<int64_t>(cs), reinterpret_cast<int64_t>(prof),
+                              (int64_t)heads, mean);
 }
 
 NtsVar hip_linear(const NtsVar& x, const NtsVar& W, NtsStream* cs) {

@@ -70,6 +70,22 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     TORCH_CHECK(!cfg.up_degree, "aggregator = max is not supported with up_degree (it takes no "
                                 "edge weights)");
   }
+  if (!cfg.gat_heads.empty()) {
+    const size_t nl = cfg.layer_size.size() - 1;
+    TORCH_CHECK(cfg.gat, "gat_heads is not supported without gat (attention layers only)");
+    TORCH_CHECK(cfg.gat_heads.size() == nl, "gat_heads needs one entry per layer (", nl, "), got ",
+                cfg.gat_heads.size());
+    for (size_t l = 0; l < nl; ++l) {
+      const int64_t K = cfg.gat_heads[l], w = cfg.layer_size[l + 1];
+      TORCH_CHECK(K >= 1, "gat_heads[", l, "] must be >= 1, got ", K);
+      const bool last = l + 1 == nl;
+      TORCH_CHECK(last || w % K == 0, "gat_heads[", l, "] = ", K, " does not divide layer width ", w);
+      const int64_t D = last ? w : w / K, Fl = K * D;
+      TORCH_CHECK(K == 1 || Fl <= (D % 4 == 0 ? 1024 : 256), "gat_heads[", l, "] = ", K, " heads of ",
+                  D, " columns: K D = ", Fl, " is outside the kernels' width limit (1024 when D is a "
+                  "multiple of 4, else 256)");
+    }
+  }
   if (cfg.sample_gpu) {
     TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
     TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
@@ -360,12 +376,14 @@ double GCN_SAMPLE_ALLGPU_impl::bottom_bytes(SampledSubgraph* sg, bool fused_map)
 void GCN_SAMPLE_ALLGPU_impl::init_nn() {
   for (size_t i = 0; i + 1 < cfg.layer_size.size(); ++i) {
     // root_weight: the stacked [W_n; W_s]
-    P.push_back(new Parameter((cfg.root_weight ? 2 : 1) * cfg.layer_size[i], cfg.layer_size[i + 1],
+    // gat_heads: the last layer's K heads of layer_size.back() columns each
+    const int64_t out = gat_width((int)i);
+    P.push_back(new Parameter((cfg.root_weight ? 2 : 1) * cfg.layer_size[i], out,
                               cfg.learn_rate, cfg.beta1,
                               cfg.beta2, cfg.epsilon, cfg.weight_decay, graph->device,
                               cfg.seed + (int64_t)i));
     if (cfg.gat)  // attention vector W_att [2 F_{l+1}, 1] (GAT_SAMPLE_ALL_GPU.hpp:141-147)
-      P.push_back(new Parameter(2 * cfg.layer_size[i + 1], 1, cfg.learn_rate, cfg.beta1,
+      P.push_back(new Parameter(2 * out, 1, cfg.learn_rate, cfg.beta1,
                                 cfg.beta2, cfg.epsilon, cfg.weight_decay, graph->device,
                                 cfg.seed + 1000 + (int64_t)i));
   }
@@ -562,7 +580,7 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_gat(SampledSubgraph* sg) {
   for (int l = 0; l < L; ++l) {
     const int hop = L - 1 - l;  // X_{l+1} = relu(attention aggregate of X_l W_l)
     X = hip_gat_layer(X, P[2 * l]->W, P[2 * l + 1]->W, sg->sampled_sgs[hop], cs.get(),
-                      profiler());
+                      profiler(), gat_heads(l), l == L - 1 && gat_heads(l) > 1);
     acts.push_back(X);
   }
   return acts;

@@ -20,6 +20,14 @@ struct GCNConfig {
   WeightType weight_type = WeightType::Sum;  // GraphSAGE toolkits: Mean
   bool up_degree = false;             // UP_DEGREE cfg key (core/GraphSegment.cpp:273-276)
   bool gat = false;                   // GAT_SAMPLE_ALL_GPU model (attention layers)
+  // Multi-head attention (gat only; no reference counterpart): one head count
+  // per layer, bottom first; empty = 1 everywhere.  A hidden layer with K heads
+  // splits its layer_size[l+1] columns into K heads of layer_size[l+1] / K and
+  // concatenates them, so the widths of layer_size keep their meaning.  The
+  // last layer with K > 1 averages K heads of layer_size.back() columns: its W
+  // is [F_in, K C] and its W_att [2 K C, 1].  Every layer's K D must be within
+  // the kernels' width limit (1024 when D % 4 == 0, else 256).
+  std::vector<int> gat_heads;
   bool fused_gather = true;           // gather features inside the bottom aggregation
   bool bias_correction = false;       // false: learn_local_with_decay_Adam (GPU drivers)
   bool deterministic_backward = true; // CSR transpose gather instead of atomics
@@ -259,6 +267,13 @@ class GCN_SAMPLE_ALLGPU_impl {
   bool tf_ = false;  // transform-first bottom layer (cfg.transform_first)
   // cfg.aggregator: the max graph op, and the weights the samplers then build (none)
   bool max_aggr() const { return cfg.aggregator == 1; }
+  // cfg.gat_heads: layer l's head count, and the width of its W (the last
+  // layer's heads are averaged, so its W holds K heads of layer_size.back())
+  int gat_heads(int l) const { return cfg.gat_heads.empty() ? 1 : cfg.gat_heads[(size_t)l]; }
+  int64_t gat_width(int l) const {
+    const bool last = (size_t)l + 2 == cfg.layer_size.size();
+    return (last ? gat_heads(l) : 1) * (int64_t)cfg.layer_size[(size_t)l + 1];
+  }
   WeightType sample_weight() const {
     return cfg.gat || max_aggr() ? WeightType::None : cfg.weight_type;
   }

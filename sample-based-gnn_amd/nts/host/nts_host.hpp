@@ -448,10 +448,14 @@ class NtsContext {
 // backward: dW = x^T dZ (split-reduction, deterministic), dx = dZ W^T.
 NtsVar hip_linear(const NtsVar& x, const NtsVar& W, NtsStream* cs);
 // one GAT layer (H = X W, attention softmax over each dst's sampled edges,
-// relu(sum a H[src])) on a merged src/dst layer: [src_size, F_in] -> [v_size, F]
+// relu(sum a H[src])) on a merged src/dst layer: [src_size, F_in] -> [v_size, F].
+// heads > 1: W's F columns are `heads` heads of F / heads columns, each with
+// its own softmax; the output is their concatenation [v_size, F], or with
+// `mean` the mean over the heads [v_size, F / heads] (relu in both).
 class KernelProfiler;
 NtsVar hip_gat_layer(const NtsVar& x, const NtsVar& W, const NtsVar& Watt, sampCSC* sg,
-                     NtsStream* cs, KernelProfiler* prof = nullptr);
+                     NtsStream* cs, KernelProfiler* prof = nullptr, int heads = 1,
+                     bool mean = false);
 // CU masks splitting the device: `n` CUs spread evenly over the chip
 // (every (total/n)-th CU) and the complement
 std::vector<uint32_t> cu_mask_spread(int device, int n, bool complement);

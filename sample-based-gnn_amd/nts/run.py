@@ -108,6 +108,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.root_weight and (model == "gat" or place is not None):
         raise SystemExit(f"ALGORITHM {info.algorithm}: ROOT_WEIGHT is not supported with GAT, "
                          "PD-cache or GCN_SAMPLE_GPU algorithms")
+    if info.gat_heads and model != "gat":
+        raise SystemExit(f"ALGORITHM {info.algorithm}: GAT_HEADS is not supported with GCN / "
+                         "GraphSAGE algorithms (GAT only)")
     if info.aggregator == "max" and (model == "gat" or place is not None):
         raise SystemExit(f"ALGORITHM {info.algorithm}: AGGREGATOR:max is not supported with GAT, "
                          "PD-cache or GCN_SAMPLE_GPU algorithms")
@@ -126,7 +129,7 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         cache_rate=cache_rate, shuffle=True, pd_cache=pd, pd_rate=info.cache_rate,
         pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu",
         multi_label=bool(info.multi_label), root_weight=bool(info.root_weight),
-        aggregator=info.aggregator)
+        aggregator=info.aggregator, gat_heads=info.gat_heads or None)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 

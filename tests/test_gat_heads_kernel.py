@@ -1,0 +1,382 @@
+"""The multi-head GAT kernels (csrc/gat.hip: k_gat_fwd_heads,
+k_gat_bwd_dst_heads, k_gat_bwd_src_heads) through the wrappers, on the
+synthetic block of tests/gat_blocks.py (columns of 0 ... 200 edges, a CSR row
+of ~95 slots), with the padded, NaN-poisoned inputs and sentinel-filled outputs
+of tests/test_gat_kernel.py.
+
+Cases cover every reduction scheme (g = D / VEC lanes per head a power of two
+below 64, a multiple of 64, anything else), both vector widths, 1 to 4 chunks
+and both output modes, each in the moderate (att = randn * 0.3) and the extreme
+(att = randn * 150 / (1.4 sqrt(D))) score regime.
+
+Bound, for each of Y, m, a, dH, dW_att against float64 autograd through the
+per-head chain of tests/gat_heads_blocks.py, with q32 the same chain in float32:
+
+    err(kernel) <= C * err(q32) + 8 * 2^-24,   C = 8 (tests/step_check.py),
+
+for every case and quantity but one.  Measured on an MI355X (the table is in
+DESIGN.md §8i) every ratio err(kernel) / err(q32) is at or below 2.12, except
+in (8, 7, mean) with extreme scores: dH 5.06 (within C = 8) and dW_att 11.80.
+There heads of 7 columns see post-leaky scores up to 574 and the attention is
+one-hot to the last bit.  The single-head kernels, run head by head on the same
+inputs (with this layer's Y and GY / K), give the same figures (dH 5.06, dW_att
+11.75): the excess belongs to the arithmetic the two share on this input, not
+to the multi-head reductions.  That one quantity of that one case is held to
+the constant its own ratio defines (the smallest power of two at least twice
+it, 32: C_EXCEPT); step_check.C stays 8 for everything else.  A reduction over
+the wrong lanes or a missing 1/K shows as 1e-1 or worse
+(tests/test_gat_heads_cpu.py).
+
+Incoming gradients are zeroed where the float64 pre-activation has |Z| < 1e-4;
+their number is capped at 1e-3 of the elements of non-empty rows, or one
+element, whichever is more.
+"""
+import numpy as np
+import pytest
+import torch
+
+import gat_blocks
+import gat_heads_blocks as ghb
+from step_check import C, err, yardstick_bound
+
+# (case, regime, quantity) -> constant, where the measured ratio needs more than C
+C_EXCEPT = {("K8-D7-mean-scalar", "extreme", "dW_att"): 32}
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SENT = -12345.5
+MASK_EPS, MASK_CAP = 1e-4, 1e-3
+EXTRA_ROWS, EXTRA_E = 3, 64
+
+# id: (K, D, mean, base offset in floats of every row operand)
+CASES = {
+    "K8-D8-concat-g2": (8, 8, False, 0),
+    "K4-D16-concat-g4": (4, 16, False, 0),
+    "K2-D128-concat-g32": (2, 128, False, 0),
+    "K4-D256-concat-chunk-per-head": (4, 256, False, 0),
+    "K2-D512-concat-two-chunks-per-head": (2, 512, False, 0),
+    "K2-D132-concat-g33": (2, 132, False, 0),
+    "K3-D20-concat-g5": (3, 20, False, 0),
+    "K3-D7-concat-scalar": (3, 7, False, 0),
+    "K5-D51-concat-scalar-straddle": (5, 51, False, 0),
+    "K8-D32-concat-base+4B-scalar": (8, 32, False, 1),
+    "K8-D7-mean-scalar": (8, 7, True, 0),
+    "K4-D16-mean": (4, 16, True, 0),
+    "K2-D128-mean": (2, 128, True, 0),
+    "K3-D41-mean-scalar": (3, 41, True, 0),
+}
+
+
+def _pitch(width):
+    """a pitch wider than the row that keeps float4 rows aligned where they can be"""
+    return width + (4 if width % 4 == 0 else 3)
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from nts.hip import HipContext
+    return HipContext(0, seed=2000)
+
+
+@pytest.fixture(scope="module")
+def block():
+    b = gat_blocks.make_block()
+    dev = {k: torch.from_numpy(b[k].view(np.int32)).to(DEV)
+           for k in ("column_offset", "row_indices", "dst_local_id", "row_offset",
+                     "column_indices", "csr_edge_id")}
+    cpu = {k: torch.from_numpy(b[k].astype(np.int64))
+           for k in ("column_offset", "row_indices", "dst_local_id")}
+    return dict(np=b, dev=dev, cpu=cpu, v=b["v"], s=b["s"], e=b["e"])
+
+
+def _rows(rows, width, off, fill):
+    """(flat, view): rows + EXTRA_ROWS rows of _pitch(width) floats starting `off`
+    floats into a fresh allocation, all `fill`"""
+    pitch = _pitch(width)
+    n = (rows + EXTRA_ROWS) * pitch
+    flat = torch.full((n + 4,), fill, device=DEV)
+    return flat, flat[off:off + n].view(rows + EXTRA_ROWS, pitch)
+
+
+def _in_rows(x, off):
+    rows, width = x.shape
+    _, view = _rows(rows, width, off, float("nan"))
+    view[:rows, :width] = x.to(DEV)
+    return view[:rows, :width]
+
+
+def _padding_intact(flat, view, rows, width):
+    inside = int((view[:rows, :width] == SENT).sum())
+    return int((flat == SENT).sum()) - inside == flat.numel() - rows * width
+
+
+class Run:
+    """One forward + backward through the multi-head wrappers on padded buffers."""
+
+    def __init__(self, hip, block, H, att, GY, K, D, mean, off, single=False):
+        v, s, e = block["v"], block["s"], block["e"]
+        d = block["dev"]
+        F, FY = K * D, (D if mean else K * D)
+        self.v, self.s, self.e, self.F, self.FY, self.K = v, s, e, F, FY, K
+        self.H = _in_rows(H, off)
+        self.att = att.to(DEV)
+        self.m = torch.full((e * K + EXTRA_E,), SENT, device=DEV)
+        self.a = torch.full((e * K + EXTRA_E,), SENT, device=DEV)
+        self.Yflat, self.Yv = _rows(v, FY, off, SENT)
+        Y = self.Yv[:v, :FY]
+        co, ri, dl = d["column_offset"], d["row_indices"], d["dst_local_id"]
+        if single:  # the existing single-head entry points (K = 1)
+            hip.gat_forward(co, ri, dl, v, self.H, self.att, self.m, self.a, Y)
+        else:
+            hip.gat_forward_heads(co, ri, dl, v, self.H, K, self.att, self.m, self.a, Y, mean=mean)
+        self.bwd = None
+        if GY is None:
+            torch.cuda.synchronize()
+            return
+        self.GY = _in_rows(GY, off)
+        self.du = torch.full((e * K + EXTRA_E,), SENT, device=DEV)
+        self.ds2 = torch.full(((s + 8) * K,), SENT, device=DEV)
+        self.dS = torch.full((s + 8, 2 * K), SENT, device=DEV)
+        self.dHflat, self.dHv = _rows(s, F, off, SENT)
+        self.GMflat, self.GMv = _rows(v, F, off, SENT)
+        tail = (d["row_offset"], d["column_indices"], d["csr_edge_id"], s, self.H)
+        if single:
+            hip.gat_backward(co, ri, dl, v, *tail, self.att, self.a, self.m, Y, self.GY, self.du,
+                             self.ds2, self.dHv[:s, :F], self.dS, GM=self.GMv[:v, :F])
+        else:
+            hip.gat_backward_heads(co, ri, dl, v, *tail, K, self.att, self.a, self.m, Y, self.GY,
+                                   self.du, self.ds2, self.dHv[:s, :F], self.dS,
+                                   GM=self.GMv[:v, :F], mean=mean)
+        torch.cuda.synchronize()
+        self.bwd = True
+
+    def outputs(self):
+        out = dict(Y=self.Yflat, m=self.m, a=self.a)
+        if self.bwd:
+            out.update(du=self.du, ds2=self.ds2, dS=self.dS, dH=self.dHflat, GM=self.GMflat)
+        return {k: t.cpu() for k, t in out.items()}
+
+    def assert_untouched(self):
+        v, s, e, F, FY, K = self.v, self.s, self.e, self.F, self.FY, self.K
+        assert _padding_intact(self.Yflat, self.Yv, v, FY), "Y: rows past v_size or padding written"
+        assert bool((self.m[e * K:] == SENT).all()) and bool((self.a[e * K:] == SENT).all()), \
+            "m / a past e K"
+        if self.bwd:
+            assert bool((self.du[e * K:] == SENT).all()), "du past e K"
+            assert bool((self.ds2[s * K:] == SENT).all()) and bool((self.dS[s:] == SENT).all())
+            assert _padding_intact(self.dHflat, self.dHv, s, F), "dH: past src_size or padding written"
+            assert _padding_intact(self.GMflat, self.GMv, v, F), "GM: past v_size or padding written"
+
+    def results(self, H):
+        """Y, m [e, K], a [e, K], dH, dW_att (H^T dS per head, in float64) on the host"""
+        v, s, e, F, FY, K = self.v, self.s, self.e, self.F, self.FY, self.K
+        D = F // K
+        got = dict(Y=self.Yv[:v, :FY].cpu(), m=self.m[:e * K].cpu().view(e, K),
+                   a=self.a[:e * K].cpu().view(e, K))
+        if self.bwd:
+            dS = self.dS[:s].cpu().double()
+            Hh = H.double().view(s, K, D)
+            dA1 = torch.einsum("vkd,vk->kd", Hh, dS[:, :K]).reshape(-1)
+            dA2 = torch.einsum("vkd,vk->kd", Hh, dS[:, K:]).reshape(-1)
+            got.update(dH=self.dHv[:s, :F].cpu(), dW_att=torch.cat([dA1, dA2]))
+        return got
+
+
+def _inputs(block, K, D, mean, regime):
+    F = K * D
+    g = torch.Generator().manual_seed(1000 * F + 10 * K + 2 * int(mean) + (regime == "extreme"))
+    H = torch.randn(block["s"], F, generator=g)
+    scale = 0.3 if regime == "moderate" else 150.0 / (1.4 * D ** 0.5)
+    att = torch.randn(2 * F, generator=g) * scale
+    GY = torch.randn(block["v"], D if mean else F, generator=g)
+    return H, att, GY
+
+
+def _reference(block, H, att, GY, K, D, mean, dtype):
+    c = block["cpu"]
+    Hd = H.detach().to(dtype).clone().requires_grad_(True)
+    ad = att.detach().to(dtype).clone().requires_grad_(True)
+    Z, m, a = ghb.heads_chain_z(Hd, ad, c["column_offset"], c["row_indices"], c["dst_local_id"],
+                                K, D, mean)
+    Y = torch.relu(Z)
+    Y.backward(GY.to(dtype))
+    return dict(Y=Y.detach(), m=m.detach(), a=a.detach(), dH=Hd.grad, dW_att=ad.grad,
+                Z=Z.detach())
+
+
+def _masked_gy(block, H, att, GY, K, D, mean, tag):
+    """GY zeroed where the float64 pre-activation is within MASK_EPS of 0"""
+    co = block["cpu"]["column_offset"]
+    probe = _reference(block, H, att, GY, K, D, mean, torch.float64)
+    nonempty = (co[1:] > co[:-1])[:, None]
+    near = (probe["Z"].abs() < MASK_EPS) & nonempty
+    total = int(nonempty.sum()) * probe["Z"].shape[1]
+    print(f"{tag}: |Z| < {MASK_EPS:g} at {int(near.sum())} of {total} elements of non-empty rows "
+          f"({int(near.sum()) / total:.2e})")
+    assert int(near.sum()) <= max(MASK_CAP * total, 1)
+    return torch.where(near, torch.zeros(()), GY)
+
+
+def _check_bound(got, r64, r32, case, regime, keys=("Y", "m", "a", "dH", "dW_att")):
+    bad = []
+    for k in keys:
+        ek, e32 = err(got[k], r64[k]), err(r32[k], r64[k])
+        bound = yardstick_bound(e32, C_EXCEPT.get((case, regime, k), C))
+        print(f"  {k}: err(kernel) {ek:.3e} err(fp32 chain) {e32:.3e} "
+              f"ratio {ek / max(e32, 2.0 ** -30):.2f} bound {bound:.3e}")
+        if not ek <= bound:
+            bad.append(f"{k}: {ek:.3e} > {bound:.3e}")
+    assert not bad, "; ".join(bad)
+
+
+@pytest.mark.parametrize("regime", ["moderate", "extreme"])
+@pytest.mark.parametrize("case", list(CASES))
+def test_heads_kernels_match_the_float64_chain(hip, block, case, regime):
+    """Y, m, a, dH and dW_att within C times the float32 chain's own error
+    (measured ratios: DESIGN.md §8i), with the exact properties of empty
+    columns, untouched padding and run-to-run bit identity."""
+    K, D, mean, off = CASES[case]
+    F, FY = K * D, (D if mean else K * D)
+    v, s, e = block["v"], block["s"], block["e"]
+    H, att, GY = _inputs(block, K, D, mean, regime)
+    GY = _masked_gy(block, H, att, GY, K, D, mean, f"{case} {regime}")
+    r64 = _reference(block, H, att, GY, K, D, mean, torch.float64)
+    r32 = _reference(block, H, att, GY, K, D, mean, torch.float32)
+    if regime == "extreme":
+        print(f"  post-leaky scores {float(r64['m'].min()):.1f} ... {float(r64['m'].max()):.1f}")
+        assert float(r64["m"].max()) > 89.0  # float32 exp overflows there
+
+    run = Run(hip, block, H, att, GY, K, D, mean, off)
+    run.assert_untouched()
+    got = run.results(H)
+    for k, t in got.items():
+        assert bool(torch.isfinite(t).all()), f"{k} has a NaN or inf"
+    assert bool(torch.isfinite(run.du[:e * K]).all()) and bool(torch.isfinite(run.ds2[:s * K]).all())
+    Y, a = got["Y"], got["a"]
+
+    b = block["np"]
+    co = b["column_offset"].astype(np.int64)
+    dl = b["dst_local_id"].astype(np.int64)
+    deg = np.diff(co)
+    ds2 = run.ds2[:s * K].view(s, K)
+    for d in np.flatnonzero(deg == 1):
+        assert bool((a[co[d]] == 1.0).all())
+    for d in np.flatnonzero(deg == 0):  # empty columns: a zero row, zero ds2
+        assert not Y[d].any()
+        assert not ds2[dl[d]].any()
+    rest = np.setdiff1d(np.arange(s), dl)
+    assert not ds2[torch.from_numpy(rest).to(DEV)].any()
+    assert torch.equal(run.dS[:s, K:], ds2)
+    # each head's attention sums to 1 over every non-empty column
+    d_of_e = np.repeat(np.arange(v), deg)
+    for h in range(K):
+        sums = np.bincount(d_of_e, weights=a[:, h].double().numpy(), minlength=v)
+        assert np.all(np.abs(sums - 1.0)[deg > 0] <= deg[deg > 0] * 2.0 ** -23)
+    # GM: GY (mean: GY times float32(1 / K), for every head) under the relu mask
+    gm = torch.where(Y > 0, GY, torch.zeros(()))
+    if mean:
+        gm = (gm * (torch.ones(()) / K)).repeat(1, K)
+    assert torch.equal(run.GMv[:v, :F].cpu(), gm)
+
+    _check_bound(got, r64, r32, case, regime)
+
+    again = Run(hip, block, H, att, GY, K, D, mean, off)
+    first, second = run.outputs(), again.outputs()
+    for k in first:
+        assert torch.equal(first[k], second[k]), f"{k} differs between two runs"
+
+
+@pytest.mark.parametrize("D,mean", [(16, False), (16, True), (67, False), (256, True)])
+def test_one_head_agrees_with_the_single_head_entry_points(hip, block, D, mean):
+    """heads = 1 through the new entry points (both modes) against the existing
+    kernels: every quantity within the yardstick bound of them."""
+    H, att, GY = _inputs(block, 1, D, mean, "moderate")
+    GY = _masked_gy(block, H, att, GY, 1, D, mean, f"K1-D{D}")
+    r64 = _reference(block, H, att, GY, 1, D, mean, torch.float64)
+    r32 = _reference(block, H, att, GY, 1, D, mean, torch.float32)
+    new = Run(hip, block, H, att, GY, 1, D, mean, 0)
+    old = Run(hip, block, H, att, GY, 1, D, False, 0, single=True)
+    new.assert_untouched()
+    got, ref = new.results(H), old.results(H)
+    bad = []
+    for k in ("Y", "m", "a", "dH", "dW_att"):
+        ek, bound = err(got[k], ref[k]), yardstick_bound(err(r32[k], r64[k]), C)
+        print(f"  {k}: err(new vs single-head) {ek:.3e} bound {bound:.3e}")
+        if not ek <= bound:
+            bad.append(f"{k}: {ek:.3e} > {bound:.3e}")
+    assert not bad, "; ".join(bad)
+
+
+@pytest.mark.parametrize("case", ["K8-D8-concat-g2", "K5-D51-concat-scalar-straddle", "K4-D16-mean"])
+def test_zero_attention_is_uniform(hip, block, case):
+    """att = 0: every score is 0 and a[e, h] = float32(1) / float32(deg) bit for
+    bit for every head; Y is the relu of the float32 mean, the same for every
+    head (so the mean over heads is that mean again within rounding)."""
+    K, D, mean, off = CASES[case]
+    F = K * D
+    v, e = block["v"], block["e"]
+    H, _, _ = _inputs(block, K, D, mean, "moderate")
+    run = Run(hip, block, H, torch.zeros(2 * F), None, K, D, mean, off)
+    run.assert_untouched()
+    b = block["np"]
+    co, ri = b["column_offset"].astype(np.int64), b["row_indices"].astype(np.int64)
+    m = run.m[:e * K].cpu().numpy().reshape(e, K)
+    a = run.a[:e * K].cpu().numpy().reshape(e, K)
+    Y = run.Yv[:v, :(D if mean else F)].cpu().numpy()
+    assert not m.any()
+    Hn = H.numpy()
+    for d in range(v):
+        n = int(co[d + 1] - co[d])
+        if n == 0:
+            assert not Y[d].any()
+            continue
+        inv = np.float32(1) / np.float32(n)
+        assert np.all(a[co[d]:co[d + 1]] == inv), d
+        acc = np.zeros(F, np.float32)
+        for j in range(co[d], co[d + 1]):
+            acc = acc + Hn[ri[j]]
+        z = acc * inv
+        if mean:
+            t = z[:D].copy()
+            for h in range(1, K):
+                t = t + z[h * D:(h + 1) * D]
+            z = t * (np.float32(1) / np.float32(K))
+        assert np.array_equal(Y[d], np.maximum(z, np.float32(0))), d
+
+
+@pytest.mark.parametrize("K,D,off", [(0, 16, 0), (257, 4, 0), (1, 257, 0), (2, 130, 0)],
+                         ids=["heads0", "F1028", "F257-scalar", "K2-D130-aligned"])
+def test_refused_shapes_write_nothing(hip, block, K, D, off):
+    """heads = 0, F = 1028 (257 heads of 4: float4-eligible), F = 257 (scalar) and (2, 130) on
+    aligned rows (D % 4 != 0: scalar, F = 260) are errors that state the limits,
+    from the forward and from the backward, and no output is written (the
+    backward's clearing of ds2 included)."""
+    v, s, e = block["v"], block["s"], block["e"]
+    d = block["dev"]
+    co, ri, dl = d["column_offset"], d["row_indices"], d["dst_local_id"]
+    Kb = max(K, 1)
+    F = Kb * D
+    H = _in_rows(torch.randn(s, F), off)
+    att = torch.randn(2 * F, device=DEV)
+    m = torch.full((e * Kb,), SENT, device=DEV)
+    a = torch.full((e * Kb,), SENT, device=DEV)
+    Yflat, Yv = _rows(v, F, off, SENT)
+    msg = r"heads must be >= 1" if K == 0 else r"1024.*256"
+    with pytest.raises(RuntimeError, match=msg):
+        hip.gat_forward_heads(co, ri, dl, v, H, K, att, m, a, Yv[:v, :F])
+    torch.cuda.synchronize()
+    for t in (m, a, Yflat):
+        assert bool((t == SENT).all())
+    GY = _in_rows(torch.randn(v, F), off)
+    du = torch.full((e * Kb,), SENT, device=DEV)
+    ds2 = torch.full((s * Kb,), SENT, device=DEV)
+    dS = torch.full((s, 2 * Kb), SENT, device=DEV)
+    dHflat, dHv = _rows(s, F, off, SENT)
+    GMflat, GMv = _rows(v, F, off, SENT)
+    with pytest.raises(RuntimeError, match=msg):
+        hip.gat_backward_heads(co, ri, dl, v, d["row_offset"], d["column_indices"], d["csr_edge_id"],
+                               s, H, K, att, a, m, Yv[:v, :F], GY, du, ds2, dHv[:s, :F], dS,
+                               GM=GMv[:v, :F])
+    torch.cuda.synchronize()
+    for t in (du, ds2, dS, dHflat, GMflat):
+        assert bool((t == SENT).all())
