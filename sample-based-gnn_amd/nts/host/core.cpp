@@ -546,186 +546,141 @@ void FastSampler::load_label_gpu(NtsStream& cs, SampledSubgraph* sg, NtsVar& loc
 }
 
 // ---------------------------------------------------------------------------
+void spmm_csc_fwd(NtsStream& cs, AggKind kind, const sampCSC* s, const NtsVar& x, bool gather,
+                  const uint32_t* v_dev, uint32_t v_rows, NtsVar& y, uint32_t* arg, bool early) {
+  const float* xp = x.data_ptr<float>();
+  const uint64_t ldx = (uint64_t)x.stride(0), ldy = (uint64_t)y.stride(0);
+  const uint32_t F = (uint32_t)x.size(1);
+  const VertexId* map = gather ? s->dev_src() : nullptr;
+  const VertexId* self = !kind.root ? nullptr : gather ? s->dev_dst() : s->dev_dst_local_id();
+  if (kind.max)
+    hip_check(nts_hip_spmm_csc_fwd_max(cs.ctx(), s->dev_c_o(), s->dev_r_i(), v_dev, v_rows, xp,
+                                       ldx, map, self, F, y.data_ptr<float>(), ldy, arg),
+              early ? "nts_hip_spmm_csc_fwd_max(early)" : "nts_hip_spmm_csc_fwd_max");
+  else if (kind.root)  // [A X | X[self rows]], one launch
+    hip_check(nts_hip_spmm_csc_fwd_root(cs.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(),
+                                        v_dev, v_rows, xp, ldx, map, self, F,
+                                        y.data_ptr<float>(), ldy),
+              early ? "nts_hip_spmm_csc_fwd_root(early)" : "nts_hip_spmm_csc_fwd_root");
+  else
+    hip_check(nts_hip_spmm_csc_fwd(cs.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(), v_dev,
+                                   v_rows, xp, ldx, map, F, y.data_ptr<float>(), ldy),
+              early ? "nts_hip_spmm_csc_fwd(early)" : "nts_hip_spmm_csc_fwd");
+}
+
 namespace op {
 
 SingleGPUAllSampleGraphOp::SingleGPUAllSampleGraphOp(SampledSubgraph* sgs, FullyRepGraph* graph,
                                                      int layer_, NtsStream* cs, bool gather,
-                                                     const FeatureCache* fc)
+                                                     const FeatureCache* fc, AggKind kind_,
+                                                     bool csr_only_)
     : subgraphs(sgs), layer(layer_), cuda_stream(cs), gather_from_table(gather),
-      feature_cache(fc) {
+      feature_cache(fc), kind(kind_), csr_only(csr_only_) {
   (void)graph;
   TORCH_CHECK(!fc || gather, "a feature cache needs gather_from_table");
+  TORCH_CHECK(!fc || !(kind.max || kind.root),
+              "a feature cache takes the sum aggregator without root weight");
 }
 
 NtsVar SingleGPUAllSampleGraphOp::forward(NtsVar& f_input) {
   sampCSC* sg = subgraphs->sampled_sgs[layer];
+  const int dev = cuda_stream->device();
+  NtsVar f_output;
   if (feature_cache) {  // two-tier table: f_input only carries the width
     const FeatureCache& fc = *feature_cache;
-    NtsVar f_output = row_padded_empty((int64_t)sg->v_size, fc.F, cuda_stream->device());
+    f_output = row_padded_empty((int64_t)sg->v_size, fc.F, dev);
     NtsVar stage = torch::empty({(int64_t)std::max<uint32_t>(sg->src_size, 1), (int64_t)fc.ld},
-                                f32_opts(cuda_stream->device()));
+                                f32_opts(dev));
     fc.aggregate(cuda_stream->ctx(), sg, nullptr, sg->v_size, nullptr, sg->src_size,
                  stage.data_ptr<float>(), f_output.data_ptr<float>(), (uint64_t)f_output.stride(0));
-    if (output_requires_grad) f_output.set_requires_grad(true);
-    return f_output;
+  } else {
+    TORCH_CHECK(!kind.root || sg->dst_local_id.defined(),
+                "root weight needs a merged src/dst layer");
+    TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
+                    f_input.stride(1) == 1,
+                "graph op input must be a row-major fp32 CUDA matrix");
+    TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
+                "graph op input has fewer rows than src_size");
+    const int64_t F = f_input.size(1);
+    f_output = row_padded_empty((int64_t)sg->v_size, (kind.root ? 2 : 1) * F, dev);
+    // max: the winners only where a backward will read them (never the bottom hop)
+    if (kind.max && output_requires_grad && sg->has_csr) {
+      TORCH_CHECK(sg->csr_edge_id.defined(), "max aggregator backward needs csr_edge_id");
+      arg = torch::empty({std::max<int64_t>(sg->v_size, 1), F}, u32_opts(dev));
+    }
+    // (the sum kernel takes the exact host row count, the other two also the device's)
+    spmm_csc_fwd(*cuda_stream, kind, sg, f_input, gather_from_table,
+                 kind.max || kind.root ? sg->dev_v_size() : nullptr, sg->v_size, f_output,
+                 dptr<uint32_t>(arg));
   }
-  TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
-                  f_input.stride(1) == 1,
-              "graph op input must be a row-major fp32 CUDA matrix");
-  TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
-              "graph op input has fewer rows than src_size");
-  const int64_t F = f_input.size(1);
-  NtsVar f_output = row_padded_empty((int64_t)sg->v_size, F, cuda_stream->device());
-  hip_check(nts_hip_spmm_csc_fwd(cuda_stream->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_e_w_f(),
-                                 nullptr, sg->v_size, f_input.data_ptr<float>(),
-                                 (uint64_t)f_input.stride(0),
-                                 gather_from_table ? sg->dev_src() : nullptr, (uint32_t)F,
-                                 f_output.data_ptr<float>(), (uint64_t)f_output.stride(0)),
-            "nts_hip_spmm_csc_fwd");
   if (output_requires_grad) f_output.set_requires_grad(true);
   return f_output;
 }
 
 NtsVar SingleGPUAllSampleGraphOp::backward(NtsVar& g) {
   sampCSC* sg = subgraphs->sampled_sgs[layer];
+  nts_hip_ctx* c = cuda_stream->ctx();
+  TORCH_CHECK(!csr_only || sg->has_csr, "SingleGPUSampleGraphOp needs the CSR transpose");
+  if (kind.max) {
+    TORCH_CHECK(sg->has_csr && sg->csr_edge_id.defined() && arg.defined(),
+                "max aggregator backward needs the CSR transpose, its edge ids and the forward's arg");
+    TORCH_CHECK(!kind.root || sg->src_dst.defined(), "root weight backward needs the inverse map");
+  } else if (kind.root) {
+    TORCH_CHECK(sg->has_csr && sg->src_dst.defined(),
+                "root weight backward needs the CSR transpose and the inverse map");
+  }
   NtsVar go = g.contiguous();
-  const int64_t F = go.size(1);
-  TORCH_CHECK(go.size(0) == (int64_t)sg->v_size, "output grad rows != v_size");
-  if (sg->has_csr) {
-    NtsVar gi = torch::empty({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
-    if (sg->post_mask_bits)  // the same, the mask read as bits
-      hip_check(nts_hip_spmm_csr_bwd_postmask_bits(
-                    cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(), nullptr,
-                    sg->src_size, go.data_ptr<float>(), (uint64_t)F, sg->post_mask_bits,
-                    sg->post_mask_scale, (uint32_t)F, gi.data_ptr<float>(), (uint64_t)F),
-                "nts_hip_spmm_csr_bwd_postmask_bits");
-    else if (sg->post_mask)  // the transform-first bottom layer's activation backward fused
-      hip_check(nts_hip_spmm_csr_bwd_postmask(cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(),
-                                              sg->dev_e_w_b(), nullptr, sg->src_size,
-                                              go.data_ptr<float>(), (uint64_t)F, sg->post_mask,
-                                              sg->post_mask_ld, sg->post_mask_scale, (uint32_t)F,
-                                              gi.data_ptr<float>(), (uint64_t)F),
-                "nts_hip_spmm_csr_bwd_postmask");
-    else
-      hip_check(nts_hip_spmm_csr_bwd(cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(),
-                                     sg->dev_e_w_b(), nullptr, sg->src_size, go.data_ptr<float>(),
-                                     (uint64_t)F, (uint32_t)F, gi.data_ptr<float>(), (uint64_t)F),
-                "nts_hip_spmm_csr_bwd");
+  const bool rows_ok = go.size(0) == (int64_t)sg->v_size;
+  const int64_t ldg = go.size(1);
+  const int64_t F = kind.max ? arg.size(1) : kind.root ? ldg / 2 : ldg;
+  if (kind.max) {
+    TORCH_CHECK(rows_ok && ldg == (kind.root ? 2 : 1) * F,
+                "output grad must be [v_size, F] ([v_size, 2 F] under root weight)");
+  } else if (kind.root) {
+    TORCH_CHECK(rows_ok && ldg % 2 == 0, "output grad must be [v_size, 2 F]");
+  } else {
+    TORCH_CHECK(rows_ok, "output grad rows != v_size");
+  }
+  const float* gp = go.data_ptr<float>();
+  const FusedActBwd& ab = sg->act_bwd;
+  if (!sg->has_csr) {  // (the plain sum alone gets here)
+    TORCH_CHECK(!ab.mask, "a fused activation backward needs the CSR backward");
+    NtsVar gi = torch::zeros({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
+    hip_check(nts_hip_spmm_csc_bwd_atomic(c, sg->dev_c_o(), sg->dev_r_i(), sg->dev_e_w_f(), nullptr,
+                                          sg->v_size, gp, (uint64_t)F, (uint32_t)F,
+                                          gi.data_ptr<float>(), (uint64_t)F),
+              "nts_hip_spmm_csc_bwd_atomic");
     return gi;
   }
-  TORCH_CHECK(!sg->post_mask, "a fused activation backward needs the CSR backward");
-  NtsVar gi = torch::zeros({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
-  hip_check(nts_hip_spmm_csc_bwd_atomic(cuda_stream->ctx(), sg->dev_c_o(), sg->dev_r_i(),
-                                        sg->dev_e_w_f(), nullptr, sg->v_size, go.data_ptr<float>(),
-                                        (uint64_t)F, (uint32_t)F, gi.data_ptr<float>(), (uint64_t)F),
-            "nts_hip_spmm_csc_bwd_atomic");
-  return gi;
-}
-
-NtsVar SingleGPUSampleGraphOp::backward(NtsVar& g) {
-  TORCH_CHECK(subgraphs->sampled_sgs[layer]->has_csr,
-              "SingleGPUSampleGraphOp needs the CSR transpose");
-  return SingleGPUAllSampleGraphOp::backward(g);
-}
-
-SingleGPURootGraphOp::SingleGPURootGraphOp(SampledSubgraph* sgs, int layer_, NtsStream* cs,
-                                           bool gather)
-    : subgraphs(sgs), layer(layer_), cuda_stream(cs), gather_from_table(gather) {}
-
-NtsVar SingleGPURootGraphOp::forward(NtsVar& f_input) {
-  sampCSC* sg = subgraphs->sampled_sgs[layer];
-  TORCH_CHECK(sg->dst_local_id.defined(), "root weight needs a merged src/dst layer");
-  TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
-                  f_input.stride(1) == 1,
-              "graph op input must be a row-major fp32 CUDA matrix");
-  TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
-              "graph op input has fewer rows than src_size");
-  const int64_t F = f_input.size(1);
-  NtsVar f_output = row_padded_empty((int64_t)sg->v_size, 2 * F, cuda_stream->device());
-  hip_check(nts_hip_spmm_csc_fwd_root(
-                cuda_stream->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_e_w_f(),
-                sg->dev_v_size(), sg->v_size, f_input.data_ptr<float>(),
-                (uint64_t)f_input.stride(0), gather_from_table ? sg->dev_src() : nullptr,
-                gather_from_table ? sg->dev_dst() : sg->dev_dst_local_id(), (uint32_t)F,
-                f_output.data_ptr<float>(), (uint64_t)f_output.stride(0)),
-            "nts_hip_spmm_csc_fwd_root");
-  if (output_requires_grad) f_output.set_requires_grad(true);
-  return f_output;
-}
-
-NtsVar SingleGPURootGraphOp::backward(NtsVar& g) {
-  sampCSC* sg = subgraphs->sampled_sgs[layer];
-  TORCH_CHECK(sg->has_csr && sg->src_dst.defined(),
-              "root weight backward needs the CSR transpose and the inverse map");
-  NtsVar go = g.contiguous();
-  TORCH_CHECK(go.size(0) == (int64_t)sg->v_size && go.size(1) % 2 == 0,
-              "output grad must be [v_size, 2 F]");
-  const int64_t F = go.size(1) / 2;
   NtsVar gi = torch::empty({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
-  hip_check(nts_hip_spmm_csr_bwd_root(cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(),
-                                      sg->dev_e_w_b(), sg->dev_src_size(), sg->src_size,
-                                      go.data_ptr<float>(), (uint64_t)(2 * F),
-                                      dptr<uint32_t>(sg->src_dst), sg->post_mask, sg->post_mask_ld,
-                                      sg->post_mask_scale, (uint32_t)F, gi.data_ptr<float>(),
-                                      (uint64_t)F),
-            "nts_hip_spmm_csr_bwd_root");
-  return gi;
-}
-
-SingleGPUMaxGraphOp::SingleGPUMaxGraphOp(SampledSubgraph* sgs, int layer_, NtsStream* cs,
-                                         bool gather, bool root)
-    : subgraphs(sgs), layer(layer_), cuda_stream(cs), gather_from_table(gather), root_weight(root) {}
-
-NtsVar SingleGPUMaxGraphOp::forward(NtsVar& f_input) {
-  sampCSC* sg = subgraphs->sampled_sgs[layer];
-  TORCH_CHECK(!root_weight || sg->dst_local_id.defined(),
-              "root weight needs a merged src/dst layer");
-  TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
-                  f_input.stride(1) == 1,
-              "graph op input must be a row-major fp32 CUDA matrix");
-  TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
-              "graph op input has fewer rows than src_size");
-  const int64_t F = f_input.size(1);
-  NtsVar f_output =
-      row_padded_empty((int64_t)sg->v_size, (root_weight ? 2 : 1) * F, cuda_stream->device());
-  // the winners only where a backward will read them (never the bottom hop)
-  const bool keep = output_requires_grad && sg->has_csr;
-  if (keep) {
-    TORCH_CHECK(sg->csr_edge_id.defined(), "max aggregator backward needs csr_edge_id");
-    arg = torch::empty({std::max<int64_t>(sg->v_size, 1), F}, u32_opts(cuda_stream->device()));
-  }
-  const VertexId* self = !root_weight        ? nullptr
-                         : gather_from_table ? sg->dev_dst()
-                                             : sg->dev_dst_local_id();
-  hip_check(nts_hip_spmm_csc_fwd_max(
-                cuda_stream->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_v_size(), sg->v_size,
-                f_input.data_ptr<float>(), (uint64_t)f_input.stride(0),
-                gather_from_table ? sg->dev_src() : nullptr, self, (uint32_t)F,
-                f_output.data_ptr<float>(), (uint64_t)f_output.stride(0),
-                keep ? dptr<uint32_t>(arg) : nullptr),
-            "nts_hip_spmm_csc_fwd_max");
-  if (output_requires_grad) f_output.set_requires_grad(true);
-  return f_output;
-}
-
-NtsVar SingleGPUMaxGraphOp::backward(NtsVar& g) {
-  sampCSC* sg = subgraphs->sampled_sgs[layer];
-  TORCH_CHECK(sg->has_csr && sg->csr_edge_id.defined() && arg.defined(),
-              "max aggregator backward needs the CSR transpose, its edge ids and the forward's arg");
-  TORCH_CHECK(!root_weight || sg->src_dst.defined(), "root weight backward needs the inverse map");
-  NtsVar go = g.contiguous();
-  const int64_t F = arg.size(1);
-  TORCH_CHECK(go.size(0) == (int64_t)sg->v_size && go.size(1) == (root_weight ? 2 : 1) * F,
-              "output grad must be [v_size, F] ([v_size, 2 F] under root weight)");
-  NtsVar gi = torch::empty({(int64_t)sg->src_size, F}, f32_opts(cuda_stream->device()));
-  hip_check(nts_hip_spmm_csr_bwd_max(cuda_stream->ctx(), sg->dev_r_o(), sg->dev_c_i(),
-                                     dptr<uint32_t>(sg->csr_edge_id), sg->dev_src_size(),
-                                     sg->src_size, go.data_ptr<float>(), (uint64_t)go.size(1),
-                                     dptr<uint32_t>(arg),
-                                     root_weight ? dptr<uint32_t>(sg->src_dst) : nullptr,
-                                     sg->post_mask, sg->post_mask_ld, sg->post_mask_scale,
-                                     (uint32_t)F, gi.data_ptr<float>(), (uint64_t)F),
-            "nts_hip_spmm_csr_bwd_max");
+  float* ip = gi.data_ptr<float>();
+  if (kind.max)
+    hip_check(nts_hip_spmm_csr_bwd_max(c, sg->dev_r_o(), sg->dev_c_i(),
+                                       dptr<uint32_t>(sg->csr_edge_id), sg->dev_src_size(),
+                                       sg->src_size, gp, (uint64_t)ldg, dptr<uint32_t>(arg),
+                                       kind.root ? dptr<uint32_t>(sg->src_dst) : nullptr, ab.mask,
+                                       ab.ld, ab.scale, (uint32_t)F, ip, (uint64_t)F),
+              "nts_hip_spmm_csr_bwd_max");
+  else if (kind.root)
+    hip_check(nts_hip_spmm_csr_bwd_root(c, sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(),
+                                        sg->dev_src_size(), sg->src_size, gp, (uint64_t)(2 * F),
+                                        dptr<uint32_t>(sg->src_dst), ab.mask, ab.ld, ab.scale,
+                                        (uint32_t)F, ip, (uint64_t)F),
+              "nts_hip_spmm_csr_bwd_root");
+  else if (ab.bits)  // the transform-first bottom layer's activation backward fused, its mask as bits
+    hip_check(nts_hip_spmm_csr_bwd_postmask_bits(c, sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(),
+                                                 nullptr, sg->src_size, gp, (uint64_t)F, ab.bits,
+                                                 ab.scale, (uint32_t)F, ip, (uint64_t)F),
+              "nts_hip_spmm_csr_bwd_postmask_bits");
+  else if (ab.mask)  // the same, the mask read from the activation's rows
+    hip_check(nts_hip_spmm_csr_bwd_postmask(c, sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(),
+                                            nullptr, sg->src_size, gp, (uint64_t)F, ab.mask, ab.ld,
+                                            ab.scale, (uint32_t)F, ip, (uint64_t)F),
+              "nts_hip_spmm_csr_bwd_postmask");
+  else
+    hip_check(nts_hip_spmm_csr_bwd(c, sg->dev_r_o(), sg->dev_c_i(), sg->dev_e_w_b(), nullptr,
+                                   sg->src_size, gp, (uint64_t)F, (uint32_t)F, ip, (uint64_t)F),
+              "nts_hip_spmm_csr_bwd");
   return gi;
 }
 
@@ -1054,7 +1009,7 @@ struct HipBottomTFFn : public torch::autograd::Function<HipBottomTFFn> {
     // dZ = dX1 ⊙ mask once per dst row, then the plain CSR gather (measured
     // faster than applying the mask to every gathered row:
     // nts_hip_spmm_csr_bwd_masked reads two rows per edge); premasked: the
-    // graph op above applied the activation backward already (post_mask)
+    // graph op above applied the activation backward already (its act_bwd)
     NtsVar dZ = sg->grad_premasked ? g : torch::empty({std::max<int64_t>(v, 1), N}, f32_opts(dev));
     if (!sg->grad_premasked)
       hip_check(nts_hip_act_backward(cs->ctx(), (uint32_t)v, (uint32_t)N, g.data_ptr<float>(),

@@ -42,31 +42,27 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     TORCH_CHECK(L_GT.dim() == 1, "labels must be int64 [V] (a [V, C] 0/1 label tensor needs "
                                  "multi_label)");
   }
-  if (cfg.root_weight) {
-    TORCH_CHECK(!cfg.gat, "root_weight is not supported with gat (GCN / GraphSAGE layers only)");
-    TORCH_CHECK(!cfg.pd_cache, "root_weight is not supported with pd_cache");
-    TORCH_CHECK(!cfg.sample_gpu, "root_weight is not supported with sample_gpu");
-    TORCH_CHECK(cfg.transform_first != 1,
-                "root_weight is not supported with transform_first = 1 (aggregate-first only)");
-    TORCH_CHECK(cfg.pair_table <= 0, "root_weight is not supported with pair_table > 0");
-    TORCH_CHECK(cfg.cache_rate < 0.0, "root_weight is not supported with cache_rate >= 0");
-    TORCH_CHECK(cfg.fused_gather, "root_weight is not supported with fused_gather = false");
-    TORCH_CHECK(cfg.deterministic_backward,
-                "root_weight needs deterministic_backward (its backward runs over the CSR)");
-  }
+  // what root_weight and aggregator = max both refuse, in the order it is
+  // reported; tf_why: the option's own reason inside the transform_first text
+  auto refuse_conflicts = [&](const char* option, const char* tf_why) {
+    const std::pair<bool, std::string> conflicts[] = {
+        {cfg.gat, " is not supported with gat (GCN / GraphSAGE layers only)"},
+        {cfg.pd_cache, " is not supported with pd_cache"},
+        {cfg.sample_gpu, " is not supported with sample_gpu"},
+        {cfg.transform_first == 1, std::string(" is not supported with transform_first = 1 (") +
+                                       tf_why + "aggregate-first only)"},
+        {cfg.pair_table > 0, " is not supported with pair_table > 0"},
+        {!(cfg.cache_rate < 0.0), " is not supported with cache_rate >= 0"},
+        {!cfg.fused_gather, " is not supported with fused_gather = false"},
+        {!cfg.deterministic_backward,
+         " needs deterministic_backward (its backward runs over the CSR)"},
+    };
+    for (const auto& c : conflicts) TORCH_CHECK(!c.first, option, c.second);
+  };
+  if (cfg.root_weight) refuse_conflicts("root_weight", "");
   TORCH_CHECK(cfg.aggregator == 0 || cfg.aggregator == 1, "aggregator must be 0 (sum) or 1 (max)");
   if (max_aggr()) {
-    TORCH_CHECK(!cfg.gat, "aggregator = max is not supported with gat (GCN / GraphSAGE layers only)");
-    TORCH_CHECK(!cfg.pd_cache, "aggregator = max is not supported with pd_cache");
-    TORCH_CHECK(!cfg.sample_gpu, "aggregator = max is not supported with sample_gpu");
-    TORCH_CHECK(cfg.transform_first != 1,
-                "aggregator = max is not supported with transform_first = 1 (a maximum does not "
-                "commute with W: aggregate-first only)");
-    TORCH_CHECK(cfg.pair_table <= 0, "aggregator = max is not supported with pair_table > 0");
-    TORCH_CHECK(cfg.cache_rate < 0.0, "aggregator = max is not supported with cache_rate >= 0");
-    TORCH_CHECK(cfg.fused_gather, "aggregator = max is not supported with fused_gather = false");
-    TORCH_CHECK(cfg.deterministic_backward,
-                "aggregator = max needs deterministic_backward (its backward runs over the CSR)");
+    refuse_conflicts("aggregator = max", "a maximum does not commute with W: ");
     TORCH_CHECK(!cfg.up_degree, "aggregator = max is not supported with up_degree (it takes no "
                                 "edge weights)");
   }
@@ -335,27 +331,8 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
       fcache->aggregate(st.ctx(), s, dptr<uint32_t>(s->sizes), s->v_cap,
                         dptr<uint32_t>(s->sizes) + 2, s->s_cap, stage_[slot].data_ptr<float>(),
                         y.data_ptr<float>(), (uint64_t)y.stride(0));
-    else if (max_aggr())  // the bottom hop has no backward: no arg
-      hip_check(nts_hip_spmm_csc_fwd_max(st.ctx(), s->dev_c_o(), s->dev_r_i(),
-                                         dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
-                                         (uint64_t)F.stride(0), s->dev_src(),
-                                         cfg.root_weight ? s->dev_dst() : nullptr,
-                                         (uint32_t)F.size(1), y.data_ptr<float>(),
-                                         (uint64_t)y.stride(0), nullptr),
-                "nts_hip_spmm_csc_fwd_max(early)");
-    else if (cfg.root_weight)  // [A X | X[destination]] from the table, one launch
-      hip_check(nts_hip_spmm_csc_fwd_root(st.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(),
-                                          dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
-                                          (uint64_t)F.stride(0), s->dev_src(), s->dev_dst(),
-                                          (uint32_t)F.size(1), y.data_ptr<float>(),
-                                          (uint64_t)y.stride(0)),
-                "nts_hip_spmm_csc_fwd_root(early)");
-    else
-      hip_check(nts_hip_spmm_csc_fwd(st.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(),
-                                     dptr<uint32_t>(s->sizes), s->v_cap, F.data_ptr<float>(),
-                                     (uint64_t)F.stride(0), s->dev_src(), (uint32_t)F.size(1),
-                                     y.data_ptr<float>(), (uint64_t)y.stride(0)),
-                "nts_hip_spmm_csc_fwd(early)");
+    else  // from the table, sizes on the device; the bottom hop has no backward: no arg
+      spmm_csc_fwd(st, agg_kind(), s, F, true, s->dev_v_size(), s->v_cap, y, nullptr, true);
     // bytes are added when the batch's sizes are known (train_batch)
     if (cfg.profile) prof.end(KernelProfiler::BOTTOM_AGG, (hipStream_t)st.stream(), 0.0);
   }
@@ -422,11 +399,9 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::vertexForward(int l, NtsVar& a) {
   const int L = (int)P.size();
   if (l == L - 1)  // multi_label: raw logits (the sigmoid is the loss's)
     return cfg.multi_label ? P[l]->forward(a) : P[l]->forward(a).log_softmax(1);
-  if (cfg.hip_gemm && cfg.fuse_activation) {
-    const double p = ctx.is_train() ? cfg.drop_rate : 0.0;
-    return hip_linear_act(a, P[l]->W, p, (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1,
-                          dropout_calls_++, cs.get(), cfg.pair_table > 0);
-  }
+  if (cfg.hip_gemm && cfg.fuse_activation)
+    return hip_linear_act(a, P[l]->W, drop_rate(), dropout_key(), dropout_calls_++, cs.get(),
+                          cfg.pair_table > 0);
   return torch::dropout(torch::relu(P[l]->forward(a)), cfg.drop_rate, ctx.is_train());
 }
 
@@ -435,6 +410,11 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
                                                      const NtsVar* loss_target) {
   const int L = (int)P.size();
   std::vector<NtsVar> acts;
+  auto keep_pair = [&](const NtsVar& Y, const NtsVar& X) {  // a layer's aggregation and output
+    if (!keep) return;
+    acts.push_back(Y.detach());
+    acts.push_back(X.detach());
+  };
   NtsVar X0;
   if (!cfg.fused_gather && !tf_) {
     if (fcache)
@@ -448,10 +428,7 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
     NtsVar Y = pre_y->narrow(0, 0, (int64_t)sg->sampled_sgs[L - 1]->v_size);
     flush_update();
     X = ctx.runVertexForward([&](NtsVar& a) { return vertexForward(0, a); }, Y);
-    if (keep) {
-      acts.push_back(Y.detach());
-      acts.push_back(X.detach());
-    }
+    keep_pair(Y, X);
     l0 = 1;
   } else {
     X = X0;
@@ -463,16 +440,14 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
     if (bottom && tf_) {  // transform-first: H = X[src] W, X1 = act(A H) (one NN op)
       flush_update();
       sampCSC* s = sg->sampled_sgs[hop];
-      const double p = ctx.is_train() ? cfg.drop_rate : 0.0;
+      const double p = drop_rate();
       NtsVar h;
       if (keep) h = torch::empty({(int64_t)std::max<uint32_t>(s->src_size, 1), P[0]->W.size(1)},
                                  f32_opts(graph->device));
       const uint64_t off = dropout_calls_++;
       X = ctx.runVertexForward(
           [&](NtsVar& t) {
-            return hip_bottom_transform(t, P[0]->W, s, p,
-                                        (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1, off,
-                                        cs.get(), profiler(),
+            return hip_bottom_transform(t, P[0]->W, s, p, dropout_key(), off, cs.get(), profiler(),
                                         keep ? h.data_ptr<float>() : nullptr, pairs_.get());
           },
           F);
@@ -482,15 +457,15 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
       // (only over a CSR: with the atomic CSC backward the layer above has
       // none, and this layer then runs nts_hip_act_backward itself)
       const bool fuse = ctx.is_train() && hop >= 1 && sg->sampled_sgs[hop - 1]->has_csr;
-      if (hop >= 1) {
-        sampCSC* up = sg->sampled_sgs[hop - 1];
-        up->post_mask = fuse ? X.data_ptr<float>() : nullptr;
-        up->post_mask_bits = fuse && s->act_bits.defined() &&
-                                     nts_hip_act_bits_words((uint32_t)X.size(1))
-                                 ? reinterpret_cast<const uint32_t*>(s->act_bits.data_ptr<int32_t>())
-                                 : nullptr;
-        up->post_mask_ld = (uint64_t)X.stride(0);
-        up->post_mask_scale = p < 1.0 ? 1.0f / (1.0f - (float)p) : 0.f;
+      if (hop >= 1) {  // set, or cleared where an earlier batch in this slot left one
+        FusedActBwd ab;
+        if (fuse) {
+          const bool bits = s->act_bits.defined() && nts_hip_act_bits_words((uint32_t)X.size(1));
+          ab = {X.data_ptr<float>(), (uint64_t)X.stride(0),
+                p < 1.0 ? 1.0f / (1.0f - (float)p) : 0.f,
+                bits ? reinterpret_cast<const uint32_t*>(s->act_bits.data_ptr<int32_t>()) : nullptr};
+        }
+        sg->sampled_sgs[hop - 1]->act_bwd = ab;
       }
       s->grad_premasked = fuse;
       if (keep) {
@@ -500,21 +475,13 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
       continue;
     }
     if (bottom && cfg.profile) prof.begin(KernelProfiler::BOTTOM_AGG, (hipStream_t)cs->stream());
-    if (max_aggr())
-      Y = ctx.runGraphOp<op::SingleGPUMaxGraphOp>(bottom ? F : X, sg, hop, cs.get(), bottom,
-                                                  cfg.root_weight);
-    else if (cfg.root_weight)
-      Y = ctx.runGraphOp<op::SingleGPURootGraphOp>(bottom ? F : X, sg, hop, cs.get(), bottom);
-    else if (cfg.sample_gpu && bottom && cfg.fused_gather)
-      Y = ctx.runGraphOp<op::SingleGPUSampleGraphOp>(F, sg, graph.get(), hop, cs.get(), true,
-                                                     fcache.get());
-    else if (cfg.sample_gpu)
-      Y = ctx.runGraphOp<op::SingleGPUSampleGraphOp>(X, sg, graph.get(), hop, cs.get(), false);
-    else if (bottom && cfg.fused_gather)
-      Y = ctx.runGraphOp<op::SingleGPUAllSampleGraphOp>(F, sg, graph.get(), hop, cs.get(), true,
-                                                        fcache.get());
-    else
-      Y = ctx.runGraphOp<op::SingleGPUAllSampleGraphOp>(X, sg, graph.get(), hop, cs.get(), false);
+    // the bottom op gathers its rows from the table; sample_gpu: the
+    // reference's SingleGPUSampleGraphOp, whose backward insists on the CSR
+    const bool gather = bottom && cfg.fused_gather;
+    Y = ctx.runGraphOp<op::SingleGPUAllSampleGraphOp>(gather ? F : X, sg, graph.get(), hop,
+                                                      cs.get(), gather,
+                                                      gather ? fcache.get() : nullptr, agg_kind(),
+                                                      cfg.sample_gpu);
     if (bottom && cfg.profile)
       prof.end(KernelProfiler::BOTTOM_AGG, (hipStream_t)cs->stream(),
                bottom_bytes(sg, cfg.fused_gather));
@@ -528,7 +495,7 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
       // sampled edges, so their rows of Y are zero and add nothing to dW.
       sampCSC* s = sg->sampled_sgs[hop];
       const uint64_t off = dropout_calls_++;
-      const double p = ctx.is_train() ? cfg.drop_rate : 0.0;
+      const double p = drop_rate();
       X = ctx.runVertexForward(
           [&](NtsVar& a) {
             NtsVar Z = P[0]->forward(a);
@@ -538,14 +505,10 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
                                             Z.data_ptr<float>(), (uint64_t)Z.stride(0)),
                       "nts_hip_pd_load_share");
             if (l == L - 1) return Z.log_softmax(1);
-            return hip_relu_dropout(Z, p, (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1, off,
-                                    cs.get());
+            return hip_relu_dropout(Z, p, dropout_key(), off, cs.get());
           },
           Y);
-      if (keep) {
-        acts.push_back(Y.detach());
-        acts.push_back(X.detach());
-      }
+      keep_pair(Y, X);
       continue;
     }
     if (loss_target && l == L - 1)  // vertexForward + Loss of the last layer, fused
@@ -559,10 +522,7 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
           Y);
     else
       X = ctx.runVertexForward([&](NtsVar& a) { return vertexForward(l, a); }, Y);
-    if (keep) {
-      acts.push_back(Y.detach());
-      acts.push_back(X.detach());
-    }
+    keep_pair(Y, X);
   }
   acts.push_back(X);
   return acts;
@@ -825,18 +785,27 @@ float GCN_SAMPLE_ALLGPU_impl::run_epoch() {
   return l;
 }
 
+// An evaluation's sampler over `ids`: sampled like training (weights, merged
+// layers, RNG mode), one slot, CSRs only where the forward reads them (GAT).
+std::unique_ptr<FastSampler> GCN_SAMPLE_ALLGPU_impl::eval_sampler(const std::vector<VertexId>& ids,
+                                                                  int batch, uint64_t batch_seq) {
+  const int L = (int)cfg.fanout.size();
+  auto s = std::make_unique<FastSampler>(graph, ids, L, batch, cfg.fanout, 1,
+                                         std::vector<bool>(L, cfg.gat),
+                                         sample_weight() != WeightType::None,
+                                         cfg.gat || cfg.root_weight);
+  s->rng_mode = cfg.rng_mode;
+  s->up_degree = cfg.up_degree;
+  s->batch_seq = batch_seq;
+  return s;
+}
+
 std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_eval(const std::vector<VertexId>& seeds,
                                                          uint64_t batch_seq) {
   flush_update();
   auto guard = cs->guard();
-  const int L = (int)cfg.fanout.size();
-  std::vector<bool> csr(L, cfg.gat);
-  FastSampler s(graph, seeds, L, (int)seeds.size(), cfg.fanout, 1, csr,
-                sample_weight() != WeightType::None, cfg.gat || cfg.root_weight);
-  s.rng_mode = cfg.rng_mode;
-  s.up_degree = cfg.up_degree;
-  s.batch_seq = batch_seq;
-  SampledSubgraph* sg = s.sample_gpu_fast((int)seeds.size(), 0, *cs, sample_weight());
+  auto s = eval_sampler(seeds, (int)seeds.size(), batch_seq);
+  SampledSubgraph* sg = s->sample_gpu_fast((int)seeds.size(), 0, *cs, sample_weight());
   ctx.eval();
   torch::NoGradGuard ng;
   std::vector<NtsVar> acts;
@@ -909,12 +878,8 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
   auto guard = cs->guard();
   const int L = (int)cfg.fanout.size();
   const WeightType wt = sample_weight();
-  std::vector<bool> csr(L, cfg.gat);
-  FastSampler s(graph, nids, L, cfg.batch_size, cfg.fanout, 1, csr, wt != WeightType::None,
-                cfg.gat || cfg.root_weight);
-  s.rng_mode = cfg.rng_mode;
-  s.up_degree = cfg.up_degree;
-  s.batch_seq = eval_seq;
+  auto sp = eval_sampler(nids, cfg.batch_size, eval_seq);
+  FastSampler& s = *sp;
   NtsVar correct = torch::zeros({cfg.multi_label ? 3 : 1}, u32_opts(graph->device));
   const bool fuse_loss = cfg.multi_label
                              ? fuse_bce()

@@ -267,6 +267,13 @@ class GCN_SAMPLE_ALLGPU_impl {
   bool tf_ = false;  // transform-first bottom layer (cfg.transform_first)
   // cfg.aggregator: the max graph op, and the weights the samplers then build (none)
   bool max_aggr() const { return cfg.aggregator == 1; }
+  AggKind agg_kind() const { return {max_aggr(), cfg.root_weight}; }  // every layer's graph op
+  // the fused dropout masks: their Philox key, and the rate (none in eval mode)
+  uint64_t dropout_key() const { return (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1; }
+  double drop_rate() const { return ctx.is_train() ? cfg.drop_rate : 0.0; }
+  // forward_eval's and evaluate()'s sampler: batches of `batch` over `ids`
+  std::unique_ptr<FastSampler> eval_sampler(const std::vector<VertexId>& ids, int batch,
+                                            uint64_t batch_seq);
   // cfg.gat_heads: layer l's head count, and the width of its W (the last
   // layer's heads are averaged, so its W holds K heads of layer_size.back())
   int gat_heads(int l) const { return cfg.gat_heads.empty() ? 1 : cfg.gat_heads[(size_t)l]; }

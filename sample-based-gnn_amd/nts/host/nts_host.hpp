@@ -7,6 +7,8 @@
 //   FastSampler             core/ntsFastSampler.hpp:28-1326  (GPU ctor + sample_gpu_fast)
 //   nts::op::ntsGraphOp     core/ntsBaseOp.hpp:28-45
 //   SingleGPUAllSampleGraphOp / SingleGPUSampleGraphOp  core/ntsSingleGPUSampleGraphOp.hpp:50-294
+//     (one implementation: AggKind selects the sum / max aggregator and the
+//      root-weight self term, spmm_csc_fwd launches its forward kernel)
 //   nts::ctx::NtsContext    core/ntsContext.hpp:95-680
 //   Parameter               core/NtsScheduler.hpp:680-1029
 //   Cuda_Stream             cuda/ntsCUDA.hpp:177-595  -> NtsStream (one nts_hip_ctx)
@@ -108,6 +110,17 @@ class FullyRepGraph {
   nts_graph_dev dev() const;
 };
 
+// An activation backward fused into a graph-op backward: the op's output rows
+// are multiplied by [mask > 0] * scale (mask = the activation's output, row
+// pitch ld; bits = the same keep mask packed, where the width has a bits
+// kernel).  mask == nullptr: none.
+struct FusedActBwd {
+  const float* mask = nullptr;
+  uint64_t ld = 0;
+  float scale = 1.f;
+  const uint32_t* bits = nullptr;
+};
+
 // ---------------------------------------------------------------------------
 // sampCSC: one sampled layer, device arrays sized by capacity (the
 // reference's dev_* mirrors + its global_data_buffer arena in one).
@@ -129,13 +142,10 @@ class sampCSC {
   // PD cache (sampled with an omit map): per dst its cache row or NTS_NOT_CACHED
   torch::Tensor omit_row;
   // transform-first training: this layer's graph-op backward also applies the
-  // bottom layer's relu/dropout backward to its output (rows of post_mask =
-  // the bottom activation X1, > 0 kept, times post_mask_scale), and the
-  // bottom layer then receives dZ instead of dX1 (grad_premasked on it)
-  const float* post_mask = nullptr;
-  uint64_t post_mask_ld = 0;
-  float post_mask_scale = 1.f;
-  const uint32_t* post_mask_bits = nullptr;  // that mask as bits (act_bits of the layer below)
+  // bottom layer's relu/dropout backward to its output (act_bwd, set on the
+  // layer above the bottom one), and the bottom layer then receives dZ
+  // instead of dX1 (grad_premasked on it).  The driver's forward sets both.
+  FusedActBwd act_bwd;
   torch::Tensor act_bits;  // transform-first bottom layer: its output's keep mask as bits
   bool grad_premasked = false;
 
@@ -305,6 +315,22 @@ class FastSampler {
 // ---------------------------------------------------------------------------
 // graph operators
 // ---------------------------------------------------------------------------
+// What a sampled graph op aggregates: the weighted sum (default) or the
+// per-column maximum, alone or with the dst's own row beside it (root weight).
+struct AggKind {
+  bool max = false, root = false;
+};
+// The sampled forward aggregation of `kind` over layer `s`: y = A x, max x or
+// [. | x[self rows]] on nts_hip_spmm_csc_fwd / _max / _root.  gather: x is the
+// global table and rows go through the layer's `source` (self rows:
+// `destination`), else x holds the layer's source rows (self rows:
+// dst_local_id).  v_dev / v_rows: the device row count, or NULL and the exact
+// one.  arg: the max kernel's winners (nullable).  early: the driver's launch
+// behind the sampling (the error label says so).
+void spmm_csc_fwd(NtsStream& cs, AggKind kind, const sampCSC* s, const NtsVar& x, bool gather,
+                  const uint32_t* v_dev, uint32_t v_rows, NtsVar& y, uint32_t* arg = nullptr,
+                  bool early = false);
+
 namespace op {
 
 class ntsGraphOp {
@@ -325,13 +351,24 @@ class ntsGraphOp {
 // (deterministic), otherwise the atomic CSC scatter (Push_From_Dst_To_Src).
 // With `gather_from_table`, f_input is the global feature table and rows are
 // fetched through the layer's `source` (fused load_feature_gpu + aggregate).
+// `kind` (no reference counterpart) selects the GraphSAGE variants, all of
+// them CSR-only in the backward:
+//   root: Ycat = [A X | X[dst rows]] in one launch over a merged src/dst layer
+//         (dst_local_id; with gather_from_table the self rows are the table's
+//         `destination` rows); backward dX = A^T dYcat[:, :F] + dYcat[src_dst, F:]
+//         over the CSR and the layer's inverse map.
+//   max:  Y[d] = max over d's sampled edges of X[src] per column, in CSC edge
+//         order (ties to the earliest edge), the winning edge kept in `arg`
+//         where a backward follows; backward routes each dY[d, c] to the
+//         source of that edge over the CSR and its csr_edge_id.
 class SingleGPUAllSampleGraphOp : public ntsGraphOp {
  public:
   // feature_cache: with gather_from_table, rows come from the two-tier table
-  // (HBM cache + host spill) instead of f_input
+  // (HBM cache + host spill) instead of f_input (the plain sum only)
   SingleGPUAllSampleGraphOp(SampledSubgraph* subgraphs, FullyRepGraph* graph, int layer,
                             NtsStream* cs, bool gather_from_table = false,
-                            const FeatureCache* feature_cache = nullptr);
+                            const FeatureCache* feature_cache = nullptr, AggKind kind = {},
+                            bool csr_only = false);
   NtsVar forward(NtsVar& f_input) override;
   NtsVar backward(NtsVar& f_output_grad) override;
 
@@ -340,52 +377,20 @@ class SingleGPUAllSampleGraphOp : public ntsGraphOp {
   NtsStream* cuda_stream;
   bool gather_from_table;
   const FeatureCache* feature_cache;
+  AggKind kind;
+  bool csr_only;      // SingleGPUSampleGraphOp: the backward refuses a layer without a CSR
+  torch::Tensor arg;  // max: u32 [v_size, F], forward to backward
 };
 
 // SingleGPUSampleGraphOp (core/ntsSingleGPUSampleGraphOp.hpp:50-176): same
 // forward; backward always through the CSR (row_offset/column_indices/e_w_b).
 class SingleGPUSampleGraphOp : public SingleGPUAllSampleGraphOp {
  public:
-  using SingleGPUAllSampleGraphOp::SingleGPUAllSampleGraphOp;
-  NtsVar backward(NtsVar& f_output_grad) override;
-};
-
-// GraphSAGE root weight (no reference counterpart): forward Ycat = [A X |
-// X[dst rows]] in one launch over a merged src/dst layer (dst_local_id; with
-// gather_from_table the self rows are the table's `destination` rows);
-// backward dX = A^T dYcat[:, :F] + dYcat[src_dst, F:] over the CSR and the
-// layer's inverse map.
-class SingleGPURootGraphOp : public ntsGraphOp {
- public:
-  SingleGPURootGraphOp(SampledSubgraph* subgraphs, int layer, NtsStream* cs,
-                       bool gather_from_table = false);
-  NtsVar forward(NtsVar& f_input) override;
-  NtsVar backward(NtsVar& f_output_grad) override;
-
-  SampledSubgraph* subgraphs;
-  int layer;
-  NtsStream* cuda_stream;
-  bool gather_from_table;
-};
-
-// GraphSAGE max aggregator (no reference counterpart): forward Y[d] = max over
-// d's sampled edges of X[src] per column, in CSC edge order (ties to the
-// earliest edge), the winning edge kept in `arg` where a backward follows;
-// backward routes each dY[d, c] to the source of that edge over the CSR and
-// its csr_edge_id.  root_weight: Ycat = [max | X[dst rows]] on a merged layer
-// and the self term in the backward, as SingleGPURootGraphOp.
-class SingleGPUMaxGraphOp : public ntsGraphOp {
- public:
-  SingleGPUMaxGraphOp(SampledSubgraph* subgraphs, int layer, NtsStream* cs,
-                      bool gather_from_table = false, bool root_weight = false);
-  NtsVar forward(NtsVar& f_input) override;
-  NtsVar backward(NtsVar& f_output_grad) override;
-
-  SampledSubgraph* subgraphs;
-  int layer;
-  NtsStream* cuda_stream;
-  bool gather_from_table, root_weight;
-  torch::Tensor arg;  // u32 [v_size, F], forward to backward
+  SingleGPUSampleGraphOp(SampledSubgraph* subgraphs, FullyRepGraph* graph, int layer,
+                         NtsStream* cs, bool gather_from_table = false,
+                         const FeatureCache* feature_cache = nullptr)
+      : SingleGPUAllSampleGraphOp(subgraphs, graph, layer, cs, gather_from_table, feature_cache,
+                                  AggKind{}, true) {}
 };
 
 }  // namespace op

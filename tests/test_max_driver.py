@@ -291,6 +291,23 @@ def test_refused_combinations_name_the_option(E, data, kw, name):
     with pytest.raises(RuntimeError, match="aggregator") as ei:
         _driver(E, data, aggregator="max", **kw)
     assert name in str(ei.value)
+    assert str(ei.value).splitlines()[0] == REFUSALS[name]
+
+
+# the constructor's refusals, whole (the first line of the error: libtorch appends its trace)
+REFUSALS = {
+    "gat": "aggregator = max is not supported with gat (GCN / GraphSAGE layers only)",
+    "pd_cache": "aggregator = max is not supported with pd_cache",
+    "sample_gpu": "aggregator = max is not supported with sample_gpu",
+    "transform_first": "aggregator = max is not supported with transform_first = 1 (a maximum does not "
+                       "commute with W: aggregate-first only)",
+    "pair_table": "aggregator = max is not supported with pair_table > 0",
+    "cache_rate": "aggregator = max is not supported with cache_rate >= 0",
+    "fused_gather": "aggregator = max is not supported with fused_gather = false",
+    "deterministic_backward": "aggregator = max needs deterministic_backward (its backward runs over "
+                              "the CSR)",
+    "up_degree": "aggregator = max is not supported with up_degree (it takes no edge weights)",
+}
 
 
 def test_sum_is_the_default(E, data):

@@ -240,11 +240,26 @@ def test_multi_label_with_root_weight(E, data):
     (dict(pair_table=1), "pair_table"),
     (dict(cache_rate=0.5), "cache_rate"),
     (dict(fused_gather=False), "fused_gather"),
+    (dict(deterministic_backward=False), "deterministic_backward"),
 ])
 def test_refused_combinations_name_the_option(E, data, kw, name):
     with pytest.raises(RuntimeError, match="root_weight") as ei:
         _driver(E, data, root_weight=True, **kw)
     assert name in str(ei.value)
+    assert str(ei.value).splitlines()[0] == REFUSALS[name]
+
+
+# the constructor's refusals, whole (the first line of the error: libtorch appends its trace)
+REFUSALS = {
+    "gat": "root_weight is not supported with gat (GCN / GraphSAGE layers only)",
+    "pd_cache": "root_weight is not supported with pd_cache",
+    "sample_gpu": "root_weight is not supported with sample_gpu",
+    "transform_first": "root_weight is not supported with transform_first = 1 (aggregate-first only)",
+    "pair_table": "root_weight is not supported with pair_table > 0",
+    "cache_rate": "root_weight is not supported with cache_rate >= 0",
+    "fused_gather": "root_weight is not supported with fused_gather = false",
+    "deterministic_backward": "root_weight needs deterministic_backward (its backward runs over the CSR)",
+}
 
 
 def test_cfg_runner_trains_with_root_weight(tmp_path):
