@@ -782,6 +782,35 @@ int nts_hip_spmm_csr_bwd_max(nts_hip_ctx *ctx, const uint32_t *row_offset,
 int nts_hip_spmm_graph_fwd_max(nts_hip_ctx *ctx, const nts_graph_dev *graph, uint64_t v_begin,
                                uint64_t v_end, int relu, const float *x, uint64_t ldx,
                                uint32_t feature_size, float *y, uint64_t ldy);
+/* The per-vertex scores of a GAT layer (heads K of D columns, F = K D, the
+ * layout of nts_hip_gat_forward_heads): S [rows, 2K] contiguous,
+ *   S[v, h] = H[v]_h . a1_h,  S[v, K + h] = H[v]_h . a2_h,
+ * a1 = att[0:F], a2 = att[F:2F], head h owning columns [hD, (h+1)D).  One pass
+ * over H in a fixed summation order; float4 where D % 4 == 0, ldh % 4 == 0 and
+ * H and att are 16-byte aligned, scalar otherwise.  heads == 0 or D == 0:
+ * NTS_ERR_INVALID. */
+int nts_hip_gat_scores(nts_hip_ctx *ctx, const float *H, uint64_t ldh, uint64_t rows,
+                       uint32_t heads, uint32_t D, const float *att, float *S);
+/* The GAT layer over ALL in-edges of d in the GLOBAL CSC of `graph`, for
+ * v_begin <= d < v_end (layer-wise inference, dst_local(d) = d), from H [V, F]
+ * and the scores S of nts_hip_gat_scores over the same H:
+ *   m[e,h] = leaky_relu(S[src_e, h] + S[d, K + h], 0.2), a = softmax over d's edges,
+ *   Z_h[d] = sum_e a[e,h] H[src_e]_h,
+ *   mean == 0: Y[d] = relu([Z_0 | .. | Z_{K-1}]) (F wide),
+ *   mean != 0: Y[d] = relu((1/K) sum_h Z_h[d]) (D wide; heads added in order).
+ * Nothing E-sized is written (no m, no a: there is no backward).  An online
+ * softmax per (row, column slice) lane group in CSC edge order; hub columns
+ * are split by column slice, never by edge range, so every output element is
+ * one fixed sequence of operations and two calls give the same bytes.  An
+ * empty column writes a zero row; rows outside the range and pitch padding
+ * are not touched; any F (wider rows take more slices).  float4 needs
+ * D % 4 == 0 besides 16-byte aligned rows.  No atomics, no grid barrier.
+ * heads == 0, D == 0 or a range outside the graph: NTS_ERR_INVALID, nothing
+ * written.  Mean mode keeps [v_end - v_begin, F] floats in the context's
+ * scratch. */
+int nts_hip_gat_graph_fwd(nts_hip_ctx *ctx, const nts_graph_dev *graph, uint64_t v_begin,
+                          uint64_t v_end, const float *H, uint64_t ldh, uint32_t heads,
+                          uint32_t D, const float *S, float *Y, uint64_t ldy, int mean);
 
 /* ---- optimiser ---------------------------------------------------------- */
 /* Fused Adam step on one parameter (n elements), element-wise identical to

@@ -60,6 +60,7 @@ EXPORTED = (
     "nts_hip_spmm_csc_fwd_root", "nts_hip_root_inverse_map", "nts_hip_spmm_csr_bwd_root",
     "nts_hip_spmm_csc_fwd_max", "nts_hip_spmm_csr_bwd_max", "nts_hip_spmm_graph_fwd_max",
     "nts_hip_gat_forward_heads", "nts_hip_gat_backward_heads",
+    "nts_hip_gat_scores", "nts_hip_gat_graph_fwd",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -185,6 +186,8 @@ def lib() -> C.CDLL:
         "nts_hip_gat_forward_heads": ([P, P, P, P, U32, P, U64, U32, U32, P, P, P, P, U64, I], I),
         "nts_hip_gat_backward_heads": ([P, P, P, P, U32, P, P, P, U32, P, U64, U32, U32, P, P, P, P,
                                         U64, P, U64, P, P, P, U64, P, U64, P, I], I),
+        "nts_hip_gat_scores": ([P, P, U64, U64, U32, U32, P, P], I),
+        "nts_hip_gat_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, P, U64, U32, U32, P, P, U64, I], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

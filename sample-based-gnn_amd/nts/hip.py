@@ -265,6 +265,39 @@ class HipContext:
                                                   int(bool(relu)), ptr(x), x.stride(0), x.shape[1],
                                                   ptr(y), y.stride(0)))
 
+    def gat_scores(self, H, heads, att, S):
+        """S [rows, 2 heads] (contiguous): S[v, h] = H[v]_h . a1_h, S[v, heads + h] =
+        H[v]_h . a2_h, with att = [a1 | a2] and head h owning columns [hD, (h+1)D)."""
+        heads = int(heads)
+        D = H.shape[1] // heads if heads > 0 else H.shape[1]
+        if heads > 0 and D * heads != H.shape[1]:
+            raise ValueError(f"gat_scores: {heads} heads do not divide width {H.shape[1]}")
+        if heads > 0 and (not S.is_contiguous() or tuple(S.shape) != (H.shape[0], 2 * heads)):
+            raise ValueError(f"gat_scores: S must be a contiguous [{H.shape[0]}, {2 * heads}]")
+        check(self.lib.nts_hip_gat_scores(self.h, ptr(H), H.stride(0), H.shape[0], heads, D,
+                                          ptr(att), ptr(S)))
+
+    def gat_graph_fwd(self, graph, H, heads, S, Y, mean=False, v_begin=0, v_end=None):
+        """The GAT layer over ALL in-edges of every v_begin <= d < v_end of the
+        global CSC of `graph`: H [V, heads * D], S = gat_scores of it; Y [V, heads * D]
+        (concat) or [V, D] (mean over heads), relu'd.  Nothing E-sized is written."""
+        heads = int(heads)
+        D = H.shape[1] // heads if heads > 0 else H.shape[1]
+        if heads > 0 and D * heads != H.shape[1]:
+            raise ValueError(f"gat_graph_fwd: {heads} heads do not divide width {H.shape[1]}")
+        g = graph.as_struct()
+        if v_end is None:
+            v_end = graph.n_vertices
+        V = graph.n_vertices
+        if heads > 0 and v_end <= V and (
+                H.shape[0] < V or not S.is_contiguous() or tuple(S.shape) != (V, 2 * heads)
+                or Y.shape[0] < v_end or Y.shape[1] != (D if mean and heads > 1 else H.shape[1])):
+            raise ValueError("gat_graph_fwd: H [V, heads D], S [V, 2 heads] contiguous and "
+                             "Y [>= v_end, heads D or D] expected")
+        check(self.lib.nts_hip_gat_graph_fwd(self.h, C.byref(g), int(v_begin), int(v_end), ptr(H),
+                                             H.stride(0), heads, D, ptr(S), ptr(Y), Y.stride(0),
+                                             int(bool(mean))))
+
     def spmm_csr_bwd_masked(self, ro, ci, wb, s_dev, s_cap, g_out, x_act, g_in, scale=1.0):
         """g_in = A^T (g_out * (x_act > 0) * scale) over the CSR."""
         F = g_out.shape[1]

@@ -288,6 +288,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return d.evaluate_full(ids);
            },
            py::arg("nids"))
+      .def("infer_full_gat", &GCN_SAMPLE_ALLGPU_impl::infer_full_gat,
+           py::call_guard<py::gil_scoped_release>())
+      .def("evaluate_full_gat",
+           [](GCN_SAMPLE_ALLGPU_impl& d, const torch::Tensor& nids) {
+             auto ids = to_ids(nids);
+             py::gil_scoped_release nogil;
+             return d.evaluate_full_gat(ids);
+           },
+           py::arg("nids"))
       .def_readonly("full_agg_ms", &GCN_SAMPLE_ALLGPU_impl::full_agg_ms)
       .def("weights", &GCN_SAMPLE_ALLGPU_impl::weights)
       .def("reset_stats", &GCN_SAMPLE_ALLGPU_impl::reset_stats)

@@ -932,7 +932,8 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate(const std::vector<VertexId>& nids) {
 // the global CSC plus one GEMM over all V rows, on the narrower side of the
 // layer.  Peak activation footprint V (F_l + F_{l+1}) 4 bytes.
 NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
-  TORCH_CHECK(!cfg.gat, "infer_full: GAT layers are not supported (GCN / GraphSAGE only)");
+  TORCH_CHECK(!cfg.gat, "infer_full: GAT layers are not supported (GCN / GraphSAGE only); a GAT "
+                        "driver has infer_full_gat() / evaluate_full_gat()");
   TORCH_CHECK(!cfg.up_degree,
               "infer_full: UP_DEGREE weights are a property of a sample, not of the whole graph");
   TORCH_CHECK(max_aggr() || cfg.weight_type != WeightType::MeanSampled,
@@ -1028,6 +1029,86 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate_full(const std::vector<VertexId>& nids) 
              unpack_label_bits(label_bits_.index_select(0, idx), cfg.layer_size.back()));
     return micro_f1(counts);
   }
+  // labels gathered and rows counted on the device; one scalar comes back
+  NtsVar n_ok = out.index_select(0, idx).argmax(1).eq(L_GT.index_select(0, idx)).sum();
+  const int64_t correct = n_ok.cpu().item<int64_t>();
+  return (double)correct / (double)nids.size();
+}
+
+// Full-neighbour inference of a GAT driver: per layer one GEMM
+// H = X W over all V rows, the per-vertex scores S = H [a1 | a2] once, and one
+// fused attention pass over the global CSC (nts_hip_gat_graph_fwd: online
+// softmax per row, nothing E-sized written).  Footprint V (F_l + F_{l+1} + 2 K)
+// floats, plus V F_{l+1} in the last layer's mean mode.
+NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full_gat() {
+  TORCH_CHECK(cfg.gat, "infer_full_gat: attention layers only; a GCN / GraphSAGE driver has "
+                       "infer_full() / evaluate_full()");
+  TORCH_CHECK(!fcache, "infer_full_gat: needs the whole feature table in HBM (cache_rate < 0)");
+  flush_update();
+  auto guard = cs->guard();
+  const int L = (int)P.size() / 2;
+  const int64_t V = (int64_t)graph->global_vertices;
+  const nts_graph_dev g = graph->dev();
+  hipStream_t st = (hipStream_t)cs->stream();
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+  ctx.eval();
+  NtsVar X = F;
+  {
+    torch::NoGradGuard ng;
+    for (int l = 0; l < L; ++l) {
+      const int64_t K = gat_heads(l);
+      const bool mean = l == L - 1 && K > 1;
+      NtsVar H = row_major(P[2 * l]->forward(X));
+      NtsVar A = P[2 * l + 1]->W.contiguous();
+      const int64_t Fl = H.size(1), D = Fl / K;
+      TORCH_CHECK(D * K == Fl && A.numel() == 2 * Fl, "infer_full_gat: layer ", l, " shapes");
+      NtsVar S = torch::empty({V, 2 * K}, f32_opts(graph->device));
+      NtsVar Y = row_padded_empty(V, mean ? D : Fl, graph->device);
+      if (cfg.profile) {
+        hipEvent_t a, b;
+        TORCH_CHECK(hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess,
+                    "hipEventCreate");
+        evs.push_back({a, b});
+        (void)hipEventRecord(a, st);
+      }
+      hip_check(nts_hip_gat_scores(cs->ctx(), H.data_ptr<float>(), (uint64_t)H.stride(0),
+                                   (uint64_t)V, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(),
+                                   S.data_ptr<float>()),
+                "nts_hip_gat_scores");
+      hip_check(nts_hip_gat_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, H.data_ptr<float>(),
+                                      (uint64_t)H.stride(0), (uint32_t)K, (uint32_t)D,
+                                      S.data_ptr<float>(), Y.data_ptr<float>(),
+                                      (uint64_t)Y.stride(0), mean ? 1 : 0),
+                "nts_hip_gat_graph_fwd");
+      if (cfg.profile) (void)hipEventRecord(evs.back().second, st);
+      X = Y;
+    }
+    X = X.log_softmax(1);  // what Loss() applies to the last layer's relu'd output
+  }
+  ctx.train();
+  cs->synchronize();
+  full_agg_ms.clear();
+  for (auto& e : evs) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e.first, e.second);
+    full_agg_ms.push_back((double)ms);
+    (void)hipEventDestroy(e.first);
+    (void)hipEventDestroy(e.second);
+  }
+  return X;
+}
+
+double GCN_SAMPLE_ALLGPU_impl::evaluate_full_gat(const std::vector<VertexId>& nids) {
+  NtsVar out = infer_full_gat();
+  if (nids.empty()) return 0.0;
+  for (VertexId v : nids)
+    TORCH_CHECK((uint64_t)v < graph->global_vertices, "evaluate_full_gat: vertex id ", v,
+                " >= vertex count ", graph->global_vertices);
+  auto guard = cs->guard();
+  torch::NoGradGuard ng;
+  NtsVar idx = torch::from_blob((void*)nids.data(), {(int64_t)nids.size()}, torch::kInt32)
+                   .to(torch::Device(torch::kCUDA, graph->device))
+                   .to(torch::kInt64);
   // labels gathered and rows counted on the device; one scalar comes back
   NtsVar n_ok = out.index_select(0, idx).argmax(1).eq(L_GT.index_select(0, idx)).sum();
   const int64_t correct = n_ok.cpu().item<int64_t>();

@@ -177,7 +177,18 @@ class GCN_SAMPLE_ALLGPU_impl {
   // correct / |nids| of infer_full()'s argmax rows (counted on the device);
   // multi_label: the micro-F1 of its logits > 0 over the rows `nids`
   double evaluate_full(const std::vector<VertexId>& nids);
+  // The same for a GAT driver (infer_full() refuses one): per layer H = X W
+  // over all V rows, the per-vertex scores (nts_hip_gat_scores) and one fused
+  // attention pass over the global CSC (nts_hip_gat_graph_fwd), gat_heads as in
+  // training (the last layer the mean over its heads); returns log_softmax of
+  // the last layer's relu'd output, what Loss() applies in training.  The same
+  // contract: nothing of the sampler, eval_seq or the dropout offsets is
+  // touched.  Not for a GCN / GraphSAGE driver or a spilled feature table.
+  NtsVar infer_full_gat();
+  // correct / |nids| of infer_full_gat()'s argmax rows (counted on the device)
+  double evaluate_full_gat(const std::vector<VertexId>& nids);
   // cfg.profile: device ms of each layer's aggregation in the last infer_full()
+  // (infer_full_gat(): scores + attention pass)
   std::vector<double> full_agg_ms;
   // PD cache: the hot vertices of every super-batch (preSample on the device,
   // per super-batch counts + their concatenated ids, the PRE_SAMPLE_FILE

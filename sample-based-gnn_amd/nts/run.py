@@ -231,9 +231,11 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
         # FULL_INFERENCE:1 — the exact score of the final weights: every vertex
         # with its whole neighbourhood, layer by layer over the whole graph
         # (no sampling: the same numbers for every RNG mode and every run)
+        # (a GAT job: the fused attention pass over the whole graph)
+        full = drv.evaluate_full_gat if info.algorithm == "GATSAMPLEALLGPU" else drv.evaluate_full
         for key, name in (("val", "Eval"), ("test", "Test")):
             n = int(ids[key].size)
-            acc = drv.evaluate_full(torch.from_numpy(ids[key])) if n else 0.0
+            acc = full(torch.from_numpy(ids[key])) if n else 0.0
             if info.multi_label:
                 res[f"full_{name.lower()}_f1"] = acc
                 if rank == 0:
