@@ -461,6 +461,47 @@ int nts_hip_relu_dropout_f32(nts_hip_ctx *ctx, uint32_t rows, uint32_t feature_s
                              const float *x, uint64_t ldx, float p, uint64_t seed,
                              uint64_t offset, float *y, uint64_t ldy);
 
+/* ---- LayerNorm + relu + dropout of a hidden layer (no reference counterpart) */
+/* y = dropout(relu(LayerNorm(z)), p) over [rows x feature_size] in one pass:
+ * per row r, mu = mean_c z[r,c], var = mean_c (z[r,c] - mu)^2 (the centred,
+ * two-pass form on the row held in registers, never E[z^2] - mu^2; the centred
+ * row is re-centred once, d -= mean_c d, which takes the rounding of the float
+ * mu out of it), rstd = 1 / sqrt(var + eps),
+ *   n = gamma[c] (z - mu) rstd + beta[c],  y = keep ? relu(n) / (1 - p) : 0,
+ * with the keep bits, the 1 / (1 - p) float scale and the p >= 1 rule of
+ * nts_hip_relu_dropout_f32 / nts_hip_gemm_relu_dropout_f32 for the same (seed,
+ * offset, row, col): the masks are interchangeable.  mean / rstd [rows] receive
+ * mu and rstd for the backward; both may be NULL (eval / inference: nothing
+ * saved, the same y).  One wave per row, four rows per 256-thread block, the
+ * row read once and written once; wave reductions are butterflies in a fixed
+ * lane order and there are no atomics: two calls give the same bytes.
+ * 1 <= feature_size <= 1024.  float4 where feature_size % 4 == 0, z, y, gamma
+ * and beta are 16-byte aligned and both pitches are multiples of 4; scalar
+ * otherwise, over the same range.  A wider row returns NTS_ERR_INVALID and
+ * writes nothing; rows == 0 succeeds and writes nothing. */
+int nts_hip_ln_act_fwd(nts_hip_ctx *ctx, uint64_t rows, uint32_t feature_size, const float *z,
+                       uint64_t ldz, const float *gamma, const float *beta, float eps, float p,
+                       uint64_t seed, uint64_t offset, float *y, uint64_t ldy, float *mean,
+                       float *rstd);
+/* Its backward, from the forward's y, z, mean and rstd (scale = 1 / (1 - p),
+ * 0 for p >= 1):  xh = (z - mean) rstd (re-centred as the forward's: the same
+ * bits),  g = dy [y > 0] scale,  t = g gamma,
+ *   dz = rstd (t - mean_c t - xh mean_c (t xh)),
+ *   dbeta[c] = sum_r g,  dgamma[c] = sum_r g xh.
+ * dz: one wave per row.  dgamma / dbeta: each block owns a contiguous run of
+ * rows whose length depends on `rows` alone (never on the device or on
+ * timing); a wave walks its quarter of the run in row order, the block adds
+ * its four waves in order and writes a [2 feature_size] partial into the
+ * context's scratch; a second kernel sums the partials in block order (four
+ * contiguous segments, then the segments in order).  No float atomics: two
+ * calls give the same bytes.  rows == 0 writes zeros to dgamma / dbeta.  The
+ * width limit, the float4 rule (over dy, y, z, dz and gamma) and the refusal
+ * are the forward's; the refusal comes before any write. */
+int nts_hip_ln_act_bwd(nts_hip_ctx *ctx, uint64_t rows, uint32_t feature_size, const float *dy,
+                       uint64_t lddy, const float *y, uint64_t ldy, const float *z, uint64_t ldz,
+                       const float *mean, const float *rstd, const float *gamma, float scale,
+                       float *dz, uint64_t lddz, float *dgamma, float *dbeta);
+
 /* ---- GAT layer on a merged src/dst sampled block ------------------------- */
 /* The GAT_SAMPLE_ALL_GPU layer (toolkits/GAT_SAMPLE_ALL_GPU.hpp:308-391:
  * BatchGPUSrcDstScatterOp -> leaky_relu(msg . W_att, 0.2) -> BatchGPUEdgeSoftMax

@@ -61,6 +61,7 @@ EXPORTED = (
     "nts_hip_spmm_csc_fwd_max", "nts_hip_spmm_csr_bwd_max", "nts_hip_spmm_graph_fwd_max",
     "nts_hip_gat_forward_heads", "nts_hip_gat_backward_heads",
     "nts_hip_gat_scores", "nts_hip_gat_graph_fwd",
+    "nts_hip_ln_act_fwd", "nts_hip_ln_act_bwd",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -188,6 +189,8 @@ def lib() -> C.CDLL:
                                         U64, P, U64, P, P, P, U64, P, U64, P, I], I),
         "nts_hip_gat_scores": ([P, P, U64, U64, U32, U32, P, P], I),
         "nts_hip_gat_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, P, U64, U32, U32, P, P, U64, I], I),
+        "nts_hip_ln_act_fwd": ([P, U64, U32, P, U64, P, P, F, F, U64, U64, P, U64, P, P], I),
+        "nts_hip_ln_act_bwd": ([P, U64, U32, P, U64, P, U64, P, U64, P, P, P, F, P, U64, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -316,6 +316,9 @@ class InputInfo:
     # weight type, the default) or max (GraphSAGE's max aggregator; the weight
     # type is then ignored; GCN / GraphSAGE algorithms without PD cache)
     aggregator: str = "sum"
+    # LAYER_NORM (this build's key): LayerNorm on every hidden layer, fused with
+    # its relu and dropout (GCN / GraphSAGE algorithms without PD cache)
+    layer_norm: int = 0
     # GAT_HEADS (this build's key): attention heads per layer, bottom first,
     # dash-separated like LAYERS (8-1); hidden layers concatenate their heads
     # (LAYERS keeps the concatenated width), the last layer averages them.
@@ -349,6 +352,7 @@ class InputInfo:
             "MULTI_LABEL": ("multi_label", int),
             "ROOT_WEIGHT": ("root_weight", int),
             "AGGREGATOR": ("aggregator", _aggregator),
+            "LAYER_NORM": ("layer_norm", int),
             "GAT_HEADS": ("gat_heads", _gat_heads),
         }
         for raw in pathlib.Path(path).read_text().splitlines():

@@ -371,6 +371,21 @@ class HipContext:
         check(self.lib.nts_hip_relu_dropout_f32(self.h, rows, F, ptr(x), x.stride(0), float(p),
                                                 int(seed), int(offset), ptr(y), y.stride(0)))
 
+    def ln_act_fwd(self, z, gamma, beta, y, eps=1e-5, p=0.0, seed=0, offset=0, mean=None,
+                   rstd=None):
+        """y = dropout(relu(LayerNorm(z))); mean / rstd [rows] are saved when given."""
+        rows, F = z.shape
+        check(self.lib.nts_hip_ln_act_fwd(self.h, rows, F, ptr(z), z.stride(0), ptr(gamma),
+                                          ptr(beta), float(eps), float(p), int(seed), int(offset),
+                                          ptr(y), y.stride(0), ptr(mean), ptr(rstd)))
+
+    def ln_act_bwd(self, dy, y, z, mean, rstd, gamma, scale, dz, dgamma, dbeta):
+        rows, F = z.shape
+        check(self.lib.nts_hip_ln_act_bwd(self.h, rows, F, ptr(dy), dy.stride(0), ptr(y),
+                                          y.stride(0), ptr(z), z.stride(0), ptr(mean), ptr(rstd),
+                                          ptr(gamma), float(scale), ptr(dz), dz.stride(0),
+                                          ptr(dgamma), ptr(dbeta)))
+
     def gemm_gather(self, A, rows, B, C):
         """C = A[rows] @ B (rows: int32 device tensor of row ids)."""
         M, K, N = rows.numel(), A.shape[1], B.shape[1]

@@ -70,7 +70,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                up_degree=False, gat=False, pd_cache=False, pd_rate=0.2, pd_super_batch=4,
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
-               gat_heads=None):
+               gat_heads=None, layer_norm=False, layer_norm_eps=1e-5):
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
     gat_heads = check_gat_heads(layers, gat, gat_heads)
@@ -104,6 +104,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.multi_label = bool(multi_label)
     c.root_weight = bool(root_weight)
     c.aggregator = {"sum": 0, "max": 1}[aggregator]
+    c.layer_norm = bool(layer_norm)
+    c.layer_norm_eps = float(layer_norm_eps)
     c.sampler_cus = int(sampler_cus)
     c.sampler_gate = int(sampler_gate)
     c.pad_features = bool(pad_features)

@@ -233,6 +233,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("multi_label", &GCNConfig::multi_label)
       .def_readwrite("root_weight", &GCNConfig::root_weight)
       .def_readwrite("aggregator", &GCNConfig::aggregator)
+      .def_readwrite("layer_norm", &GCNConfig::layer_norm)
+      .def_readwrite("layer_norm_eps", &GCNConfig::layer_norm_eps)
       .def_readwrite("sampler_cus", &GCNConfig::sampler_cus)
       .def_readwrite("sampler_gate", &GCNConfig::sampler_gate)
       .def_readwrite("pad_features", &GCNConfig::pad_features)

@@ -1235,6 +1235,64 @@ NtsVar hip_relu_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offse
   return HipActFn::apply(x, p, (int64_t)seed, (int64_t)offset, reinterpret_cast<int64_t>(cs));
 }
 
+// dropout(relu(LayerNorm(z))) in one pass (nts_hip_ln_act_fwd); backward dz,
+// dgamma, dbeta in one pass plus the partials' reduction (nts_hip_ln_act_bwd).
+// Without a backward to come (eval, inference) nothing is saved.
+struct HipLnActFn : public torch::autograd::Function<HipLnActFn> {
+  static NtsVar forward(AutogradContext* ctx, NtsVar z, NtsVar gamma, NtsVar beta, double eps,
+                        double p, int64_t seed, int64_t offset, int64_t cs_ptr, bool train) {
+    auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
+    NtsVar zc = row_major(z), gc = gamma.contiguous(), bc = beta.contiguous();
+    const int64_t M = zc.size(0), N = zc.size(1);
+    TORCH_CHECK(gc.numel() == N && bc.numel() == N, "hip_ln_act: shape mismatch");
+    NtsVar y = torch::empty({M, N}, zc.options());
+    NtsVar mean, rstd;
+    if (train) {
+      mean = torch::empty({M}, zc.options());
+      rstd = torch::empty({M}, zc.options());
+    }
+    hip_check(nts_hip_ln_act_fwd(cs->ctx(), (uint64_t)M, (uint32_t)N, zc.data_ptr<float>(),
+                                 (uint64_t)zc.stride(0), gc.data_ptr<float>(),
+                                 bc.data_ptr<float>(), (float)eps, (float)p, (uint64_t)seed,
+                                 (uint64_t)offset, y.data_ptr<float>(), (uint64_t)N,
+                                 train ? mean.data_ptr<float>() : nullptr,
+                                 train ? rstd.data_ptr<float>() : nullptr),
+              "nts_hip_ln_act_fwd");
+    if (train) ctx->save_for_backward({zc, y, mean, rstd, gc});
+    ctx->saved_data["cs"] = cs_ptr;
+    ctx->saved_data["scale"] = p < 1.0 ? (double)(1.0f / (1.0f - (float)p)) : 0.0;
+    return y;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    TORCH_CHECK(saved.size() == 5, "hip_ln_act: backward without a training forward");
+    NtsVar z = saved[0], y = saved[1], mean = saved[2], rstd = saved[3], gamma = saved[4];
+    auto* cs = reinterpret_cast<NtsStream*>(ctx->saved_data["cs"].toInt());
+    NtsVar g = grads[0].contiguous();
+    const int64_t M = y.size(0), N = y.size(1);
+    NtsVar dz = torch::empty({M, N}, y.options());
+    NtsVar dgamma = torch::empty({N}, y.options()), dbeta = torch::empty({N}, y.options());
+    hip_check(nts_hip_ln_act_bwd(cs->ctx(), (uint64_t)M, (uint32_t)N, g.data_ptr<float>(),
+                                 (uint64_t)N, y.data_ptr<float>(), (uint64_t)N,
+                                 z.data_ptr<float>(), (uint64_t)z.stride(0),
+                                 mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                                 gamma.data_ptr<float>(),
+                                 (float)ctx->saved_data["scale"].toDouble(), dz.data_ptr<float>(),
+                                 (uint64_t)N, dgamma.data_ptr<float>(), dbeta.data_ptr<float>()),
+              "nts_hip_ln_act_bwd");
+    return {dz, dgamma, dbeta, NtsVar(), NtsVar(), NtsVar(), NtsVar(), NtsVar(), NtsVar()};
+  }
+};
+
+NtsVar hip_ln_act(const NtsVar& z, const NtsVar& gamma, const NtsVar& beta, double eps, double p,
+                  uint64_t seed, uint64_t offset, NtsStream* cs) {
+  // a backward follows only under grad mode with an input requiring grad
+  const bool train = torch::GradMode::is_enabled() &&
+                     (z.requires_grad() || gamma.requires_grad() || beta.requires_grad());
+  return HipLnActFn::apply(z, gamma, beta, eps, p, (int64_t)seed, (int64_t)offset,
+                           reinterpret_cast<int64_t>(cs), train);
+}
+
 void set_bottom_gemm_hooks(std::function<void()> after_fwd_gemm,
                            std::function<void()> before_bwd_gemm) {
   g_after_fwd_gemm = std::move(after_fwd_gemm);

@@ -82,6 +82,16 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                   "multiple of 4, else 256)");
     }
   }
+  if (cfg.layer_norm) {
+    TORCH_CHECK(!cfg.gat, "layer_norm is not supported with gat (GCN / GraphSAGE layers only)");
+    TORCH_CHECK(!cfg.pd_cache, "layer_norm is not supported with pd_cache");
+    TORCH_CHECK(cfg.transform_first != 1, "layer_norm is not supported with transform_first = 1 "
+                                          "(LayerNorm does not commute with A: aggregate-first only)");
+    TORCH_CHECK(cfg.pair_table <= 0, "layer_norm is not supported with pair_table > 0");
+    for (size_t l = 1; l + 1 < cfg.layer_size.size(); ++l)
+      TORCH_CHECK(cfg.layer_size[l] <= 1024, "layer_norm is not supported with a hidden width above "
+                                             "1024 (layer ", l - 1, ": ", cfg.layer_size[l], ")");
+  }
   if (cfg.sample_gpu) {
     TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
     TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
@@ -127,7 +137,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // (a table that stays in the Infinity Cache) instead of F_in-wide feature
   // rows, at the price of a GEMM over the src rows instead of the dst rows.
   const bool tf_ok = L >= 2 && !cfg.gat && !fcache && cfg.hip_gemm && cfg.fuse_activation &&
-                     !cfg.pd_cache && !cfg.root_weight && !max_aggr();
+                     !cfg.pd_cache && !cfg.root_weight && !max_aggr() && !cfg.layer_norm;
   if (cfg.transform_first == 1)
     TORCH_CHECK(tf_ok, "transform_first needs >= 2 layers, the MFMA GEMMs with the fused "
                        "activation, no GAT and no feature cache");
@@ -272,7 +282,7 @@ GCN_SAMPLE_ALLGPU_impl::~GCN_SAMPLE_ALLGPU_impl() {
     (void)hipEventDestroy(grads_reduced_);
     (void)hipStreamDestroy(comm_stream_);
   }
-  for (auto* p : P) delete p;
+  for (auto* p : params()) delete p;
 }
 
 // Sampling of one batch into `slot` (sample_gpu_fast's device part), then —
@@ -366,30 +376,45 @@ void GCN_SAMPLE_ALLGPU_impl::init_nn() {
   }
   if (cfg.hip_gemm)
     for (auto* p : P) p->cs = cs.get();
+  if (cfg.layer_norm)  // gamma = 1, beta = 0 per hidden layer; never decayed
+    for (size_t i = 0; i + 2 < cfg.layer_size.size(); ++i)
+      for (float init : {1.f, 0.f}) {
+        auto* q = new Parameter(1, (size_t)cfg.layer_size[i + 1], cfg.learn_rate, cfg.beta1,
+                                cfg.beta2, cfg.epsilon, 0.f, graph->device, cfg.seed);
+        q->W = torch::full({(int64_t)cfg.layer_size[i + 1]}, init, f32_opts(graph->device))
+                   .set_requires_grad(true);
+        q->M = torch::zeros_like(q->W).set_requires_grad(false);
+        q->V = torch::zeros_like(q->W).set_requires_grad(false);
+        LN.push_back(q);
+      }
   int64_t n = 0;
-  for (auto* p : P) n += p->W.numel();
+  for (auto* p : params()) n += p->W.numel();
   grad_bucket = torch::zeros({n}, f32_opts(graph->device));
   if (comm) {  // identical initial weights on every rank (init_parameter / Bcast)
     torch::NoGradGuard ng;
     // the initialisation ran on libtorch's current stream: order it before the
     // broadcast on the driver stream (construction time only)
     TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
-    for (auto* p : P) comm->broadcast(p->W.data_ptr<float>(), (uint64_t)p->W.numel(), 0, cs->stream());
+    for (auto* p : params())
+      comm->broadcast(p->W.data_ptr<float>(), (uint64_t)p->W.numel(), 0, cs->stream());
   }
 }
 
 void GCN_SAMPLE_ALLGPU_impl::set_weights(const std::vector<NtsVar>& ws) {
   flush_update();
   auto guard = cs->guard();
-  TORCH_CHECK(ws.size() == P.size(), "one tensor per layer");
+  const auto all = params();
+  TORCH_CHECK(ws.size() == all.size(), LN.empty() ? "one tensor per layer"
+                                                  : "one tensor per layer, then gamma and beta "
+                                                    "of every hidden layer (the list of weights())");
   torch::NoGradGuard ng;
-  for (size_t i = 0; i < P.size(); ++i) P[i]->W.copy_(ws[i]);
+  for (size_t i = 0; i < all.size(); ++i) all[i]->W.copy_(ws[i].view_as(all[i]->W));
 }
 
 std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::weights() {
   flush_update();
   std::vector<NtsVar> out;
-  for (auto* p : P) out.push_back(p->W.detach().clone());
+  for (auto* p : params()) out.push_back(p->W.detach().clone());
   return out;
 }
 
@@ -399,6 +424,8 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::vertexForward(int l, NtsVar& a) {
   const int L = (int)P.size();
   if (l == L - 1)  // multi_label: raw logits (the sigmoid is the loss's)
     return cfg.multi_label ? P[l]->forward(a) : P[l]->forward(a).log_softmax(1);
+  if (cfg.layer_norm)  // the plain GEMM, then LayerNorm + relu + dropout in one pass
+    return layer_norm_act(l, P[l]->forward(a), drop_rate(), dropout_calls_++);
   if (cfg.hip_gemm && cfg.fuse_activation)
     return hip_linear_act(a, P[l]->W, drop_rate(), dropout_key(), dropout_calls_++, cs.get(),
                           cfg.pair_table > 0);
@@ -566,7 +593,7 @@ void GCN_SAMPLE_ALLGPU_impl::Update() {
     TORCH_CHECK(!pending_update_, "deferred update still pending");
     torch::NoGradGuard ng;
     int64_t off = 0;
-    for (auto* p : P) {
+    for (auto* p : params()) {
       const int64_t n = p->W.numel();
       grad_bucket.narrow(0, off, n).copy_(p->W.grad().reshape({-1}));
       off += n;
@@ -582,20 +609,20 @@ void GCN_SAMPLE_ALLGPU_impl::Update() {
   if (comm) {  // also at one rank: the same bucket, all-reduce and unpack run
     torch::NoGradGuard ng;
     int64_t off = 0;
-    for (auto* p : P) {
+    for (auto* p : params()) {
       const int64_t n = p->W.numel();
       grad_bucket.narrow(0, off, n).copy_(p->W.grad().reshape({-1}));
       off += n;
     }
     comm->allreduce_sum(grad_bucket.data_ptr<float>(), (uint64_t)grad_bucket.numel(), cs->stream());
     off = 0;
-    for (auto* p : P) {
+    for (auto* p : params()) {
       const int64_t n = p->W.numel();
       p->W.mutable_grad().copy_(grad_bucket.narrow(0, off, n).view(p->W.sizes()));
       off += n;
     }
   }
-  for (auto* p : P) {
+  for (auto* p : params()) {
     if (cfg.bias_correction) p->learnC2C_with_decay_Adam(*cs);
     else p->learn_local_with_decay_Adam(*cs);
     p->next();
@@ -609,7 +636,7 @@ void GCN_SAMPLE_ALLGPU_impl::flush_update() {
   TORCH_CHECK(hipStreamWaitEvent((hipStream_t)cs->stream(), grads_reduced_, 0) == hipSuccess,
               "hipStreamWaitEvent");
   int64_t off = 0;
-  for (auto* p : P) {
+  for (auto* p : params()) {
     p->adam_from(*cs, grad_bucket.data_ptr<float>() + off, cfg.bias_correction != 0);
     p->next();
     off += p->W.numel();
@@ -730,7 +757,7 @@ float GCN_SAMPLE_ALLGPU_impl::train_batch() {
   set_bottom_gemm_hooks(nullptr, nullptr);
   gated_slot_ = -1;
   Update();
-  for (auto* p : P) p->zero_grad();
+  for (auto* p : params()) p->zero_grad();
   TORCH_CHECK(hipEventRecord(sg->consumed, (hipStream_t)cs->stream()) == hipSuccess,
               "hipEventRecord");
   mark("T>", *cs);
@@ -984,14 +1011,19 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
     for (int l = 0; l < L; ++l) {
       const bool last = l == L - 1;
       const NtsVar& W = P[l]->W;
+      // layer_norm: the hidden layer's activation is the fused LayerNorm pass
+      // over A X W, whichever way the (linear) product was formed
+      const bool ln = cfg.layer_norm && !last;
       if (!cfg.root_weight && !max_aggr() && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
         NtsVar H = P[l]->forward(X);
-        NtsVar Y = aggregate(H, !last);
-        X = last && !cfg.multi_label ? Y.log_softmax(1) : Y;
+        NtsVar Y = aggregate(H, !last && !ln);
+        X = ln ? layer_norm_act(l, Y, 0.0, 0) : last && !cfg.multi_label ? Y.log_softmax(1) : Y;
       } else {  // aggregate first: act((A X) W)
         NtsVar Y = aggregate(X, false);
         if (last)
           X = cfg.multi_label ? P[l]->forward(Y) : P[l]->forward(Y).log_softmax(1);
+        else if (ln)
+          X = layer_norm_act(l, P[l]->forward(Y), 0.0, 0);
         else if (cfg.hip_gemm && cfg.fuse_activation)  // p = 0: no mask, no offset drawn
           X = hip_linear_act(Y, W, 0.0, 0, 0, cs.get(), false);
         else

@@ -59,6 +59,16 @@ struct GCNConfig {
   // 1, pair_table > 0, cache_rate >= 0, fused_gather = false,
   // deterministic_backward = false or up_degree.
   int aggregator = 0;
+  // LayerNorm on every hidden layer (no reference counterpart): layer l < L-1 is
+  // X' = dropout(relu(LayerNorm((A X) W_l; gamma_l, beta_l))) in one fused pass
+  // over the plain GEMM's output (nts_hip_ln_act_*; fuse_activation has no
+  // effect there); the last layer is unchanged.  gamma_l (ones) and beta_l
+  // (zeros) are [layer_size[l+1]] parameters that take Adam steps without
+  // weight decay.  Aggregate-first only (LayerNorm does not commute with A:
+  // transform_first = -1 resolves to 0).  Not with gat, pd_cache,
+  // transform_first = 1, pair_table > 0 or a hidden width above 1024.
+  bool layer_norm = false;
+  float layer_norm_eps = 1e-5f;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its
@@ -151,6 +161,7 @@ class GCN_SAMPLE_ALLGPU_impl {
   void restart();
   // eval-mode forward over a given seed batch: [Y_0, X_1, Y_1, X_2, ...]
   std::vector<NtsVar> forward_eval(const std::vector<VertexId>& seeds, uint64_t batch_seq);
+  // one tensor per layer; with cfg.layer_norm the list of weights()
   void set_weights(const std::vector<NtsVar>& ws);
   // Accuracy (getCorrect / Test, toolkits/GCN_SAMPLE_ALLGPU.hpp:166-213,361-383):
   // training batches count their correct rows on the device as they train
@@ -196,6 +207,7 @@ class GCN_SAMPLE_ALLGPU_impl {
   std::pair<std::vector<uint32_t>, std::vector<uint32_t>> presample();
   void set_presample(const std::vector<uint32_t>& counts, const std::vector<uint32_t>& ids);
   uint64_t pd_hits = 0;  // bottom-layer dsts served from the PD cache (host count, sampled batches)
+  // [W_0 .. W_{L-1}], then with cfg.layer_norm [gamma_0, beta_0, gamma_1, beta_1, ...]
   std::vector<NtsVar> weights();
   void reset_stats();
   void resolve_profile() { prof.resolve(); }
@@ -209,6 +221,9 @@ class GCN_SAMPLE_ALLGPU_impl {
   std::unique_ptr<FastSampler> sampler;
   std::unique_ptr<FeatureCache> fcache;  // two-tier feature table (cache_rate)
   std::vector<Parameter*> P;
+  // cfg.layer_norm: gamma_0, beta_0, gamma_1, beta_1, ... of the hidden layers
+  // (apart from P, whose size is the layer count)
+  std::vector<Parameter*> LN;
   ctx::NtsContext ctx;
   // statistics
   double sample_time = 0, train_time = 0;
@@ -238,6 +253,17 @@ class GCN_SAMPLE_ALLGPU_impl {
   double bottom_bytes(SampledSubgraph* sg, bool fused_map) const;
   KernelProfiler* profiler() { return cfg.profile ? &prof : nullptr; }
   void Loss(NtsVar& left, NtsVar& right);
+  // every trained tensor, in the order of weights() and of grad_bucket: the W's, then LN
+  std::vector<Parameter*> params() const {
+    std::vector<Parameter*> all(P);
+    all.insert(all.end(), LN.begin(), LN.end());
+    return all;
+  }
+  // hidden layer l's LayerNorm + relu + dropout (p = 0, offset 0: no mask drawn)
+  NtsVar layer_norm_act(int l, const NtsVar& Z, double p, uint64_t offset) {
+    return hip_ln_act(Z, LN[2 * (size_t)l]->W, LN[2 * (size_t)l + 1]->W, cfg.layer_norm_eps, p,
+                      dropout_key(), offset, cs.get());
+  }
   void Update();
   bool defer_ = false;            // overlap_allreduce in effect
   bool pending_update_ = false;   // an all-reduce is in flight, its Adam not yet run

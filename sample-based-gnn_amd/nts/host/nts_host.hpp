@@ -557,6 +557,12 @@ class KernelProfiler {
 
 // dropout(relu(x), p) as its own autograd op (the GEMM epilogue's mask keys)
 NtsVar hip_relu_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offset, NtsStream* cs);
+// dropout(relu(LayerNorm(z; gamma, beta, eps)), p) as one autograd op
+// (nts_hip_ln_act_fwd / _bwd, the same mask keys): gradients for z, gamma [F]
+// and beta [F]; saves z, y, mean, rstd and gamma when a backward can follow,
+// nothing otherwise (eval / inference)
+NtsVar hip_ln_act(const NtsVar& z, const NtsVar& gamma, const NtsVar& beta, double eps, double p,
+                  uint64_t seed, uint64_t offset, NtsStream* cs);
 
 // Transform-first bottom layer (nts_hip.h): X1 = dropout(relu(A (X[source] W)))
 // on the layer's sampled block `sg` (its CSR is needed for the backward);

@@ -33,6 +33,10 @@ sigmoid binary cross-entropy, and the report lines are `Train F1:`, `Eval F1:`,
 `Test F1:` (micro-F1 of logits > 0; `Full Eval F1:` / `Full Test F1:` under
 FULL_INFERENCE:1) instead of the accuracies.
 
+LAYER_NORM:1 (GCN / GraphSAGE algorithms without PD cache): every hidden layer
+is dropout(relu(LayerNorm(.))) in one fused pass, with a gamma and a beta per
+hidden layer that are trained without weight decay.
+
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
 """
@@ -114,6 +118,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.aggregator == "max" and (model == "gat" or place is not None):
         raise SystemExit(f"ALGORITHM {info.algorithm}: AGGREGATOR:max is not supported with GAT, "
                          "PD-cache or GCN_SAMPLE_GPU algorithms")
+    if info.layer_norm and (model == "gat" or place == "pd"):
+        raise SystemExit(f"ALGORITHM {info.algorithm}: LAYER_NORM is not supported with GAT or "
+                         "PD-cache algorithms (GCN / GraphSAGE layers only)")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -129,7 +136,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         cache_rate=cache_rate, shuffle=True, pd_cache=pd, pd_rate=info.cache_rate,
         pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu",
         multi_label=bool(info.multi_label), root_weight=bool(info.root_weight),
-        aggregator=info.aggregator, gat_heads=info.gat_heads or None)
+        aggregator=info.aggregator, gat_heads=info.gat_heads or None,
+        layer_norm=bool(info.layer_norm))
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
