@@ -568,6 +568,65 @@ int nts_hip_gat_backward_heads(nts_hip_ctx *ctx, const uint32_t *column_offset,
                                const float *Y, uint64_t ldy, const float *GY, uint64_t ldg,
                                float *du, float *ds2, float *GM, uint64_t ldm, float *dH,
                                uint64_t lddh, float *dS, int mean);
+/* The dropout forms of the four entry points above (no reference counterpart:
+ * the reference's GAT stores drop_rate and never uses it).  p_attn drops the
+ * normalised attention coefficients, p_out the written Y:
+ *   a[e,h]  = the softmax over ALL edges of d, as above (what a_out receives)
+ *   a~[e,h] = keepA(e,h) ? a[e,h] / (1 - p_attn) : 0
+ *   Z_h[d]  = sum_e a~[e,h] H[src_e]_h,   Y = relu(concat or mean of Z_h)
+ *   Y[d,c] <- keepF(d,c) ? Y[d,c] / (1 - p_out) : 0.
+ * Keep bits, the 1 / (1 - p) float scale and the p >= 1 rule are those of
+ * nts_hip_relu_dropout_f32 under key `seed`: keepA(e,h) is the bit of element
+ * (row = CSC edge position e, col = h) at offset off_attn, keepF(d,c) that of
+ * element (d, c) of Y at offset off_out, so either mask is what
+ * nts_hip_relu_dropout_f32 leaves of a ones tensor of that shape.  The
+ * backward takes the forward's a (undropped), m and Y, regenerates keepA (no
+ * mask is stored) and reads keepF off Y > 0:
+ *   GM = GY [Y > 0] / (1 - p_out) (mean: / K),
+ *   ga[e,h] = (GM[d]_h . H[src_e]_h) keepA(e,h) / (1 - p_attn),
+ *   du = a (ga - sum_e a ga) leaky',  dH[v] = sum_e a~[e] GM[d_e] + ds1 a1 + ds2 a2.
+ * Edge order and the absence of atomics are those of the plain forms: two
+ * calls give the same bytes.  With both rates 0 the plain kernels run (the
+ * same bytes as the plain entry points).  Width limits and refusals are the
+ * plain forms'; a rate that is negative, above 1 or NaN returns
+ * NTS_ERR_INVALID.  Every refusal comes before any write. */
+int nts_hip_gat_forward_drop(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                             const uint32_t *row_indices, const uint32_t *dst_local_id,
+                             uint32_t v_size, const float *H, uint64_t ldh, uint32_t F,
+                             const float *att, float *m_out, float *a_out, float *Y, uint64_t ldy,
+                             float p_attn, float p_out, uint64_t seed, uint64_t off_attn,
+                             uint64_t off_out);
+int nts_hip_gat_backward_drop(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                              const uint32_t *row_indices, const uint32_t *dst_local_id,
+                              uint32_t v_size, const uint32_t *row_offset,
+                              const uint32_t *column_indices, const uint32_t *csr_edge_id,
+                              uint32_t src_size, const float *H, uint64_t ldh, uint32_t F,
+                              const float *att, const float *a, const float *m, const float *Y,
+                              uint64_t ldy, const float *GY, uint64_t ldg, float *du, float *ds2,
+                              float *GM, uint64_t ldm, float *dH, uint64_t lddh, float *dS,
+                              float p_attn, float p_out, uint64_t seed, uint64_t off_attn);
+int nts_hip_gat_forward_heads_drop(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                                   const uint32_t *row_indices, const uint32_t *dst_local_id,
+                                   uint32_t v_size, const float *H, uint64_t ldh, uint32_t heads,
+                                   uint32_t D, const float *att, float *m_out, float *a_out,
+                                   float *Y, uint64_t ldy, int mean, float p_attn, float p_out,
+                                   uint64_t seed, uint64_t off_attn, uint64_t off_out);
+int nts_hip_gat_backward_heads_drop(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                                    const uint32_t *row_indices, const uint32_t *dst_local_id,
+                                    uint32_t v_size, const uint32_t *row_offset,
+                                    const uint32_t *column_indices, const uint32_t *csr_edge_id,
+                                    uint32_t src_size, const float *H, uint64_t ldh, uint32_t heads,
+                                    uint32_t D, const float *att, const float *a, const float *m,
+                                    const float *Y, uint64_t ldy, const float *GY, uint64_t ldg,
+                                    float *du, float *ds2, float *GM, uint64_t ldm, float *dH,
+                                    uint64_t lddh, float *dS, int mean, float p_attn, float p_out,
+                                    uint64_t seed, uint64_t off_attn);
+/* Plain inverted dropout with the same keep bits (no relu: the input pass of
+ * gat_feat_drop, whose features may be negative): y = keep(row, col) ?
+ * x / (1 - p) : 0 over [rows x feature_size]; y == x is allowed. */
+int nts_hip_dropout_f32(nts_hip_ctx *ctx, uint32_t rows, uint32_t feature_size, const float *x,
+                        uint64_t ldx, float p, uint64_t seed, uint64_t offset, float *y,
+                        uint64_t ldy);
 
 /* ---- dense layer update (MFMA fp32) -------------------------------------- */
 /* Row-major fp32 GEMM on the matrix cores (v_mfma_f32_16x16x4_f32 /

@@ -65,13 +65,102 @@ struct GV<4> {
 
 __device__ __forceinline__ float leaky(float u) { return u > 0.f ? u : 0.2f * u; }
 
+// ---- dropout forms ------------------------------------------------
+// Every kernel below has a `DROP` flag and an optional trailing GatDrop
+// argument (the pack DR: empty or GatDrop).  KERNEL<VEC, NCH[, MODE]> is the
+// plain kernel, signature and code as without the flag (the dropout code is
+// compiled out); KERNEL<..., true, GatDrop> adds the two dropouts of a GAT
+// recipe, both from the shared keep bits of common.hpp:
+//   attention  edge e of head h is kept iff the bit of element (row = CSC edge
+//              position e, col = h) at off_attn is set; the softmax still sums
+//              over all edges (a stays the undropped softmax), the aggregate
+//              takes the kept ones, scaled by 1 / (1 - p_attn);
+//   output     element (d, col) of the written Y at off_out, after the relu.
+// The backward regenerates the attention bits (no mask is stored); the output
+// mask is Y > 0 itself.  A threshold of 0 draws nothing.
+struct GatDrop {
+  uint32_t thr_attn = 0, thr_out = 0;  // dropout_threshold of the two rates
+  float scale_attn = 1.f, scale_out = 1.f;
+  uint64_t seed = 0, off_attn = 0, off_out = 0;
+};
+
+__device__ __forceinline__ GatDrop drop_of() { return GatDrop(); }
+__device__ __forceinline__ const GatDrop& drop_of(const GatDrop& dr) { return dr; }
+
+__device__ __forceinline__ uint32_t row_word(const uint4& r, uint32_t row) {
+  return (row & 2u) ? ((row & 1u) ? r.w : r.z) : ((row & 1u) ? r.y : r.x);
+}
+
+// single head: is CSC edge e kept
+__device__ __forceinline__ bool edge_kept(uint32_t e, const GatDrop& dr) {
+  if (!dr.thr_attn) return true;
+  return dropout_bits(row_word(dropout_words(e, 0u, dr.seed, dr.off_attn), e), 0u) >= dr.thr_attn;
+}
+
+// K heads: the keep bits of CSC edge e, bit h % 64 of kb[h / 64].  One generator
+// call gives heads 2 hp and 2 hp + 1 (word e % 4 of its 4-edge x 2-head block:
+// e is the global edge position).  The head of vector column col is at most
+// col, so NW = NCH words hold every head of the row.
+template <int NW>
+__device__ __forceinline__ void edge_keep_bits(uint64_t (&kb)[NW], uint32_t e, uint32_t heads,
+                                               const GatDrop& dr) {
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    kb[w] = ~0ull;
+    if (!dr.thr_attn) continue;
+    kb[w] = 0ull;
+    const uint32_t hp_end = min((heads + 1u) >> 1, 32u * (w + 1));
+    for (uint32_t hp = 32u * w; hp < hp_end; ++hp) {
+      const uint32_t wd = row_word(dropout_words(e, 2u * hp, dr.seed, dr.off_attn), e);
+      const uint64_t two = (uint64_t)((wd & 0xFFFFu) >= dr.thr_attn) |
+                           ((uint64_t)((wd >> 16) >= dr.thr_attn) << 1);
+      kb[w] |= two << (2u * (hp & 31u));
+    }
+  }
+}
+// the owner lane's bits in every lane (the words past the last head are not moved)
+template <int NW>
+__device__ __forceinline__ void keep_bits_from(uint64_t (&kj)[NW], const uint64_t (&kb)[NW],
+                                               int src_lane, uint32_t heads) {
+#pragma unroll
+  for (int w = 0; w < NW; ++w)
+    kj[w] = (uint32_t)(64 * w) < heads ? __shfl(kb[w], src_lane, 64) : 0ull;
+}
+// head h's bit; c: the chunk of the asking vector column (h / 64 <= c)
+template <int NW>
+__device__ __forceinline__ bool head_kept(const uint64_t (&kj)[NW], uint32_t h, int c) {
+  uint64_t w = kj[0];
+#pragma unroll
+  for (int i = 1; i < NW; ++i)
+    if (i <= c && (h >> 6) == (uint32_t)i) w = kj[i];
+  return (w >> (h & 63u)) & 1ull;
+}
+
+// output dropout of the vector at (row d, vector column col) of the written Y
+template <int VEC>
+__device__ __forceinline__ typename GV<VEC>::T out_drop(typename GV<VEC>::T v, uint32_t d,
+                                                        uint32_t col, const GatDrop& dr) {
+  if constexpr (VEC == 1) {
+    const uint32_t wd = row_word(dropout_words(d, col, dr.seed, dr.off_out), d);
+    return dropout_bits(wd, col) >= dr.thr_out ? v * dr.scale_out : 0.f;
+  } else {  // scalar columns 4 col ... 4 col + 3: two column pairs
+    const uint32_t w0 = row_word(dropout_words(d, 4u * col, dr.seed, dr.off_out), d);
+    const uint32_t w1 = row_word(dropout_words(d, 4u * col + 2u, dr.seed, dr.off_out), d);
+    return make_float4((w0 & 0xFFFFu) >= dr.thr_out ? v.x * dr.scale_out : 0.f,
+                       (w0 >> 16) >= dr.thr_out ? v.y * dr.scale_out : 0.f,
+                       (w1 & 0xFFFFu) >= dr.thr_out ? v.z * dr.scale_out : 0.f,
+                       (w1 >> 16) >= dr.thr_out ? v.w * dr.scale_out : 0.f);
+  }
+}
+
 // ---- forward -----------------------------------------------------------------
-template <int VEC, int NCH>
+template <int VEC, int NCH, bool DROP = false, class... DR>
 __global__ __launch_bounds__(kGatThreads) void k_gat_fwd(
     const uint32_t* __restrict__ co, const uint32_t* __restrict__ ri,
     const uint32_t* __restrict__ dl, uint32_t nv_dst, const float* __restrict__ H, uint64_t ldh,
     uint32_t nvec, const float* __restrict__ att, float* __restrict__ m_out,
-    float* __restrict__ a_out, float* __restrict__ Y, uint64_t ldy) {
+    float* __restrict__ a_out, float* __restrict__ Y, uint64_t ldy, DR... drs) {
+  [[maybe_unused]] const GatDrop& dr = drop_of(drs...);
   using G = GV<VEC>;
   using T = typename G::T;
   const int lane = threadIdx.x & 63;
@@ -104,6 +193,9 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd(
     const uint32_t ne = min(end - cb, 64u);
     const uint32_t my_r = lane < (int)ne ? ri[cb + lane] : 0u;
     float my_m = 0.f;
+    // DROP: bit j = edge cb + j kept, drawn by the lane that owns the edge
+    [[maybe_unused]] uint64_t kept = ~0ull;
+    if constexpr (DROP) kept = __ballot(edge_kept(cb + lane, dr));
     for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {  // kGatU neighbour rows in flight
       T x[kGatU][NCH];
       float p1[kGatU];
@@ -132,33 +224,47 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd(
         const float Mn = fmaxf(M, m);
         const float sc = expf(M - Mn);  // 0 for the first edge (M = -inf)
         const float p = expf(m - Mn);
-        S = S * sc + p;
+        S = S * sc + p;  // over all edges
+        float pk = p;    // DROP: the accumulator takes the kept edges only
+        if constexpr (DROP) pk = ((kept >> (j0 + u)) & 1ull) ? p : 0.f;
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) acc[c] = G::axpy(G::scale(acc[c], sc), p, x[u][c]);
+        for (int c = 0; c < NCH; ++c) acc[c] = G::axpy(G::scale(acc[c], sc), pk, x[u][c]);
         M = Mn;
       }
     }
     if (lane < (int)ne) m_out[cb + lane] = my_m;
   }
   const float inv = S > 0.f ? 1.f / S : 0.f;
+  float invy = inv;  // DROP: 1 / (1 - p_attn) folded in
+  if constexpr (DROP) invy = inv * dr.scale_attn;
   T* y = reinterpret_cast<T*>(Y + (uint64_t)d * ldy);
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const uint32_t col = lane + 64 * c;
-    if (col < nvec) y[col] = G::relu(G::scale(acc[c], inv));
+    if (col < nvec) {
+      T o = G::relu(G::scale(acc[c], invy));
+      if constexpr (DROP)
+        if (dr.thr_out) o = out_drop<VEC>(o, d, col, dr);
+      y[col] = o;
+    }
   }
   // attention coefficients (needed by the backward)
   for (uint32_t e = beg + lane; e < end; e += 64) a_out[e] = expf(m_out[e] - M) * inv;
 }
 
+
 // ---- backward, per destination ------------------------------------------------
-template <int VEC, int NCH>
+// DROP: GM = GY (.) [Y > 0] / (1 - p_out) (Y > 0 exactly where the row was
+// relu-active and kept); the parked ga_e = (GM . H[src_e]) keep_e / (1 - p_attn)
+// is dL/da_e, and du = a (ga - sum a ga) leaky' as without dropout.
+template <int VEC, int NCH, bool DROP = false, class... DR>
 __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst(
     const uint32_t* __restrict__ co, const uint32_t* __restrict__ ri,
     const uint32_t* __restrict__ dl, uint32_t nv_dst, const float* __restrict__ H, uint64_t ldh,
     uint32_t nvec, const float* __restrict__ a, const float* __restrict__ m,
     const float* __restrict__ Y, uint64_t ldy, const float* __restrict__ GY, uint64_t ldg,
-    float* __restrict__ du, float* __restrict__ ds2, float* __restrict__ GM, uint64_t ldm) {
+    float* __restrict__ du, float* __restrict__ ds2, float* __restrict__ GM, uint64_t ldm, DR... drs) {
+  [[maybe_unused]] const GatDrop& dr = drop_of(drs...);
   using G = GV<VEC>;
   using T = typename G::T;
   const int lane = threadIdx.x & 63;
@@ -172,6 +278,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst(
   for (int c = 0; c < NCH; ++c) {
     const uint32_t col = lane + 64 * c;
     g[c] = col < nvec ? G::mask(gy[col], yy[col]) : G::zero();
+    if constexpr (DROP) g[c] = G::scale(g[c], dr.scale_out);
     if (col < nvec) gm[col] = g[c];  // relu-masked gradient, read per edge by k_gat_bwd_src
   }
   const uint32_t beg = co[d], end = co[d + 1];
@@ -205,6 +312,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst(
         if (lane == (int)(j0 + u)) my_ga = p[u];
     }
     if (lane < (int)ne) {
+      if constexpr (DROP) my_ga = edge_kept(cb + lane, dr) ? my_ga * dr.scale_attn : 0.f;
       du[cb + lane] = my_ga;
       sag += a[cb + lane] * my_ga;
     }
@@ -222,14 +330,18 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst(
   if (lane == 0) ds2[dl[d]] = s;
 }
 
+
 // ---- backward, per source (CSR) ------------------------------------------------
-template <int VEC, int NCH>
+// DROP: the weight of GM[d_e] is the dropped attention keep_e a_e / (1 - p_attn),
+// the keep bit regenerated from the slot's CSC edge position
+template <int VEC, int NCH, bool DROP = false, class... DR>
 __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src(
     const uint32_t* __restrict__ ro, const uint32_t* __restrict__ ci,
     const uint32_t* __restrict__ ceid, uint32_t nv_src, uint32_t nvec,
     const float* __restrict__ a, const float* __restrict__ du, const float* __restrict__ ds2,
     const float* __restrict__ att, const float* __restrict__ GM, uint64_t ldm,
-    float* __restrict__ dH, uint64_t lddh, float* __restrict__ dS) {
+    float* __restrict__ dH, uint64_t lddh, float* __restrict__ dS, DR... drs) {
+  [[maybe_unused]] const GatDrop& dr = drop_of(drs...);
   using G = GV<VEC>;
   using T = typename G::T;
   const int lane = threadIdx.x & 63;
@@ -249,6 +361,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src(
       my_d = ci[cb + lane];
       my_a = a[eid];
       my_u = du[eid];
+      if constexpr (DROP) my_a = edge_kept(eid, dr) ? my_a * dr.scale_attn : 0.f;
     }
     s1 += my_u;
     for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {
@@ -290,6 +403,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src(
     dS[2 * (uint64_t)v + 1] = s2;
   }
 }
+
 
 // ---- multi-head layer -----------------------------------------------------------
 // K heads of D columns, F = K D: head h owns columns [hD, (h+1)D) of H, a1 and
@@ -376,13 +490,17 @@ __device__ __forceinline__ void head_sums(float (&p)[U][NCH], const uint32_t (&h
   }
 }
 
-template <int VEC, int NCH, int MODE>
+// DROP: the lane that owns edge cb + lane of a chunk draws that edge's keep bits
+// for every head (edge_keep_bits); they reach the lanes of head h with the
+// edge's turn (keep_bits_from).
+template <int VEC, int NCH, int MODE, bool DROP = false, class... DR>
 __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
     const uint32_t* __restrict__ co, const uint32_t* __restrict__ ri,
     const uint32_t* __restrict__ dl, uint32_t nv_dst, const float* __restrict__ H, uint64_t ldh,
     uint32_t nvec, uint32_t g, uint32_t heads, const float* __restrict__ att,
     float* __restrict__ m_out, float* __restrict__ a_out, float* __restrict__ Y, uint64_t ldy,
-    int mean) {
+    int mean, DR... drs) {
+  [[maybe_unused]] const GatDrop& dr = drop_of(drs...);
   using G = GV<VEC>;
   using T = typename G::T;
   // mean mode only (dynamic LDS, none in concat mode): the wave's normalised
@@ -421,6 +539,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
   for (uint32_t cb = beg; cb < end; cb += 64) {
     const uint32_t ne = min(end - cb, 64u);
     const uint32_t my_r = lane < (int)ne ? ri[cb + lane] : 0u;
+    [[maybe_unused]] uint64_t kb[NCH];
+    if constexpr (DROP) edge_keep_bits<NCH>(kb, cb + lane, heads, dr);
     for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {  // kGatU neighbour rows in flight
       T x[kGatU][NCH];
       float p1[kGatU][NCH];
@@ -441,6 +561,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
       for (int u = 0; u < kGatU; ++u) {
         if (j0 + u >= ne) break;
         const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
+        [[maybe_unused]] uint64_t kj[NCH];
+        if constexpr (DROP) keep_bits_from<NCH>(kj, kb, (int)(j0 + u), heads);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const float m = leaky(p1[u][c] + s2[0][c]);
@@ -448,8 +570,10 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
           const float Mn = fmaxf(M[c], m);
           const float sc = expf(M[c] - Mn);  // 0 for the first edge (M = -inf)
           const float p = expf(m - Mn);
-          S[c] = S[c] * sc + p;
-          acc[c] = G::axpy(G::scale(acc[c], sc), p, x[u][c]);
+          S[c] = S[c] * sc + p;  // over all edges
+          float pk = p;          // DROP: the accumulator takes the kept edges only
+          if constexpr (DROP) pk = head_kept<NCH>(kj, hc[c], c) ? p : 0.f;
+          acc[c] = G::axpy(G::scale(acc[c], sc), pk, x[u][c]);
           M[c] = Mn;
         }
       }
@@ -459,14 +583,21 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     inv[c] = S[c] > 0.f ? 1.f / S[c] : 0.f;
-    acc[c] = G::scale(acc[c], inv[c]);
+    float invy = inv[c];  // DROP: 1 / (1 - p_attn) folded in
+    if constexpr (DROP) invy = inv[c] * dr.scale_attn;
+    acc[c] = G::scale(acc[c], invy);
   }
   T* y = reinterpret_cast<T*>(Y + (uint64_t)d * ldy);
   if (!mean) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const uint32_t col = lane + 64 * c;
-      if (col < nvec) y[col] = G::relu(acc[c]);
+      if (col < nvec) {
+        T o = G::relu(acc[c]);
+        if constexpr (DROP)
+          if (dr.thr_out) o = out_drop<VEC>(o, d, col, dr);
+        y[col] = o;
+      }
     }
   } else {  // Y[d] = relu(mean over heads), heads added in order
 #pragma unroll
@@ -485,7 +616,10 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
       if (col < g) {
         T t = zrow[col];
         for (uint32_t h = 1; h < heads; ++h) t = G::axpy(t, 1.f, zrow[h * g + col]);
-        y[col] = G::relu(G::scale(t, rk));
+        T o = G::relu(G::scale(t, rk));
+        if constexpr (DROP)
+          if (dr.thr_out) o = out_drop<VEC>(o, d, col, dr);
+        y[col] = o;
       }
     }
   }
@@ -502,14 +636,17 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_heads(
     }
 }
 
-template <int VEC, int NCH, int MODE>
+
+// DROP: as k_gat_bwd_dst, per head
+template <int VEC, int NCH, int MODE, bool DROP = false, class... DR>
 __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
     const uint32_t* __restrict__ co, const uint32_t* __restrict__ ri,
     const uint32_t* __restrict__ dl, uint32_t nv_dst, const float* __restrict__ H, uint64_t ldh,
     uint32_t nvec, uint32_t g, uint32_t heads, const float* __restrict__ a,
     const float* __restrict__ m, const float* __restrict__ Y, uint64_t ldy,
     const float* __restrict__ GY, uint64_t ldg, float* __restrict__ du, float* __restrict__ ds2,
-    float* __restrict__ GM, uint64_t ldm, int mean) {
+    float* __restrict__ GM, uint64_t ldm, int mean, DR... drs) {
+  [[maybe_unused]] const GatDrop& dr = drop_of(drs...);
   using G = GV<VEC>;
   using T = typename G::T;
   const int lane = threadIdx.x & 63;
@@ -532,6 +669,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
       // mean mode: every head gets GY / K under the mask of the D-wide Y
       const uint32_t q = mean ? col - hc[c] * g : col;
       gv[c] = G::mask(gy[q], yy[q]);
+      if constexpr (DROP) gv[c] = G::scale(gv[c], dr.scale_out);
       if (mean) gv[c] = G::scale(gv[c], rk);
       gm[col] = gv[c];  // read per edge by k_gat_bwd_src_heads
     }
@@ -545,6 +683,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
   for (uint32_t cb = beg; cb < end; cb += 64) {
     const uint32_t ne = min(end - cb, 64u);
     const uint32_t my_r = lane < (int)ne ? ri[cb + lane] : 0u;
+    [[maybe_unused]] uint64_t kb[NCH];
+    if constexpr (DROP) edge_keep_bits<NCH>(kb, cb + lane, heads, dr);
     for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {
       float p[kGatU][NCH], av[kGatU][NCH];
 #pragma unroll
@@ -565,12 +705,17 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
       for (int u = 0; u < kGatU; ++u) {
         if (j0 + u >= ne) break;
         const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
+        [[maybe_unused]] uint64_t kj[NCH];
+        if constexpr (DROP) keep_bits_from<NCH>(kj, kb, (int)(j0 + u), heads);
 #pragma unroll
-        for (int c = 0; c < NCH; ++c)
+        for (int c = 0; c < NCH; ++c) {
+          float ga = p[u][c];
+          if constexpr (DROP) ga = head_kept<NCH>(kj, hc[c], c) ? ga * dr.scale_attn : 0.f;
           if (lead[c]) {
-            du[eb + hc[c]] = p[u][c];
-            sag[c] += av[u][c] * p[u][c];
+            du[eb + hc[c]] = ga;
+            sag[c] += av[u][c] * ga;
           }
+        }
       }
     }
   }
@@ -592,13 +737,17 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
     }
 }
 
-template <int VEC, int NCH, int = 0>  // (no reduction here: one form for every g)
+
+// DROP: as k_gat_bwd_src, per head; the lane that owns CSR slot cb + lane
+// draws the bits of that slot's CSC edge
+template <int VEC, int NCH, int = 0, bool DROP = false, class... DR>  // (no reduction here: one form for every g)
 __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src_heads(
     const uint32_t* __restrict__ ro, const uint32_t* __restrict__ ci,
     const uint32_t* __restrict__ ceid, uint32_t nv_src, uint32_t nvec, uint32_t g, uint32_t heads,
     const float* __restrict__ a, const float* __restrict__ du, const float* __restrict__ ds2,
     const float* __restrict__ att, const float* __restrict__ GM, uint64_t ldm,
-    float* __restrict__ dH, uint64_t lddh, float* __restrict__ dS) {
+    float* __restrict__ dH, uint64_t lddh, float* __restrict__ dS, DR... drs) {
+  [[maybe_unused]] const GatDrop& dr = drop_of(drs...);
   using G = GV<VEC>;
   using T = typename G::T;
   const int lane = threadIdx.x & 63;
@@ -622,6 +771,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src_heads(
       my_e = ceid[cb + lane];
       my_d = ci[cb + lane];
     }
+    [[maybe_unused]] uint64_t kb[NCH];
+    if constexpr (DROP) edge_keep_bits<NCH>(kb, my_e, heads, dr);
     for (uint32_t j0 = 0; j0 < ne; j0 += kGatU) {
       T x[kGatU][NCH];
       float w[kGatU][NCH], uu[kGatU][NCH];
@@ -632,12 +783,15 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src_heads(
         const uint32_t dd = (uint32_t)__shfl((int)my_d, jj, 64);
         const uint64_t eb = (uint64_t)(uint32_t)__shfl((int)my_e, jj, 64) * heads;
         const T* gm = reinterpret_cast<const T*>(GM + (uint64_t)dd * ldm);
+        [[maybe_unused]] uint64_t kj[NCH];
+        if constexpr (DROP) keep_bits_from<NCH>(kj, kb, jj, heads);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const uint32_t col = lane + 64 * c;
           const bool in = ok && col < nvec;
           x[u][c] = in ? gm[col] : G::zero();
           w[u][c] = in ? a[eb + hc[c]] : 0.f;
+          if constexpr (DROP) w[u][c] = head_kept<NCH>(kj, hc[c], c) ? w[u][c] * dr.scale_attn : 0.f;
           uu[u][c] = in ? du[eb + hc[c]] : 0.f;
         }
       }
@@ -670,6 +824,35 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src_heads(
   }
 }
 
+
+// plain inverted dropout with the shared keep bits (the input pass of
+// gat_feat_drop): thread = a 4-row x 2-column block, one generator call
+__global__ void k_dropout(const float* x, uint64_t ldx, uint32_t rows, uint32_t F,
+                          uint32_t keep_threshold, float scale, uint64_t seed, uint64_t offset,
+                          float* y, uint64_t ldy) {
+  const uint32_t cpairs = (F + 1) / 2;
+  const uint64_t blocks = (uint64_t)((rows + 3) / 4) * cpairs;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < blocks;
+       t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t r4 = (uint32_t)(t / cpairs) * 4, c2 = (uint32_t)(t % cpairs) * 2;
+    uint4 rnd = make_uint4(0u, 0u, 0u, 0u);
+    if (keep_threshold) rnd = dropout_words(r4, c2, seed, offset);
+    const uint32_t wd[4] = {rnd.x, rnd.y, rnd.z, rnd.w};
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const uint32_t r = r4 + v;
+      if (r >= rows) break;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const uint32_t c = c2 + h;
+        if (c >= F) break;
+        const float a = x[(uint64_t)r * ldx + c];  // (y may be x: read before the write)
+        y[(uint64_t)r * ldy + c] = dropout_bits(wd[v], c) >= keep_threshold ? a * scale : 0.f;
+      }
+    }
+  }
+}
+
 static bool gat_vec4(uint32_t F, uint64_t l1, uint64_t l2, const void* p1, const void* p2,
                      const void* att) {
   return F % 4 == 0 && l1 % 4 == 0 && l2 % 4 == 0 && ((uintptr_t)p1 % 16) == 0 &&
@@ -685,25 +868,58 @@ static const char kGatWidthMsg[] =
     "feature width too large (F <= 1024 on 16-byte aligned rows with pitches that are "
     "multiples of 4, F <= 256 otherwise)";
 
-#define NTS_GAT_DISPATCH(KERNEL, ARGS)                                                   \
+// The plain and the _drop entry points share one checked implementation each:
+// `fn` is the entry point's name for the error text, `dr` its dropout (none, or
+// both rates 0: the plain kernels, the same launches as without the options).
+#define GAT_CHECK(cond, msg)                                                \
+  do {                                                                      \
+    if (!(cond)) {                                                          \
+      ::nts_hip::set_error("%s: invalid argument: %s", fn, msg);            \
+      return NTS_ERR_INVALID;                                               \
+    }                                                                       \
+  } while (0)
+
+static const char kGatRateMsg[] = "dropout probability must be in [0, 1]";
+
+namespace {
+bool gat_rate_ok(float p) { return p >= 0.f && p <= 1.f; }  // (a NaN fails both)
+GatDrop gat_drop(float p_attn, float p_out, uint64_t seed, uint64_t off_attn, uint64_t off_out) {
+  GatDrop dr;
+  dr.thr_attn = dropout_threshold(p_attn);
+  dr.thr_out = dropout_threshold(p_out);
+  dr.scale_attn = p_attn >= 1.f ? 0.f : 1.0f / (1.0f - p_attn);
+  dr.scale_out = p_out >= 1.f ? 0.f : 1.0f / (1.0f - p_out);
+  dr.seed = seed;
+  dr.off_attn = off_attn;
+  dr.off_out = off_out;
+  return dr;
+}
+}  // namespace
+
+// The tail of a kernel's template arguments: none for the plain kernel,
+// GAT_T_DROP with `*dr` as the last argument.  The single-head dispatch takes
+// it as TAIL, the multi-head macros read GAT_T where they are used.
+#define GAT_T_NONE
+#define GAT_T_DROP , true, GatDrop
+#define NTS_GAT_DISPATCH(KERNEL, ARGS, TAIL)                                             \
   do {                                                                                   \
     const uint32_t nvec = v4 ? F / 4 : F;                                                \
     const int nch = (int)((nvec + 63) / 64);                                             \
-    NTS_CHECK_ARG(nch <= 4, kGatWidthMsg);                                               \
+    GAT_CHECK(nch <= 4, kGatWidthMsg);                                                   \
     const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));                        \
     if (v4) {                                                                            \
       switch (nch) {                                                                     \
-        case 1: hipLaunchKernelGGL((KERNEL<4, 1>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<4, 2>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<4, 3>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        default: hipLaunchKernelGGL((KERNEL<4, 4>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        case 1: hipLaunchKernelGGL((KERNEL<4, 1 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        case 2: hipLaunchKernelGGL((KERNEL<4, 2 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        case 3: hipLaunchKernelGGL((KERNEL<4, 3 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        default: hipLaunchKernelGGL((KERNEL<4, 4 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
       }                                                                                  \
     } else {                                                                             \
       switch (nch) {                                                                     \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<1, 2>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<1, 3>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        default: hipLaunchKernelGGL((KERNEL<1, 4>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        case 1: hipLaunchKernelGGL((KERNEL<1, 1 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        case 2: hipLaunchKernelGGL((KERNEL<1, 2 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        case 3: hipLaunchKernelGGL((KERNEL<1, 3 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
+        default: hipLaunchKernelGGL((KERNEL<1, 4 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
       }                                                                                  \
     }                                                                                    \
     NTS_LAUNCH_CHECK();                                                                  \
@@ -734,10 +950,10 @@ HeadsShape heads_shape(uint32_t heads, uint32_t D, bool v4) {
 
 #define NTS_GAT_HEADS_NCH(KERNEL, V, ...)                                                       \
   switch (hs.nch) {                                                                             \
-    case 1: hipLaunchKernelGGL((KERNEL<V, 1, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-    case 2: hipLaunchKernelGGL((KERNEL<V, 2, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-    case 3: hipLaunchKernelGGL((KERNEL<V, 3, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-    default: hipLaunchKernelGGL((KERNEL<V, 4, __VA_ARGS__>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    case 1: hipLaunchKernelGGL((KERNEL<V, 1, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    case 2: hipLaunchKernelGGL((KERNEL<V, 2, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    case 3: hipLaunchKernelGGL((KERNEL<V, 3, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
+    default: hipLaunchKernelGGL((KERNEL<V, 4, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
   }
 #define NTS_GAT_HEADS_MODE(KERNEL, V)                                     \
   switch (hs.mode) {                                                      \
@@ -757,6 +973,195 @@ HeadsShape heads_shape(uint32_t heads, uint32_t D, bool v4) {
     NTS_LAUNCH_CHECK();                                                   \
   } while (0)
 
+namespace {
+
+int gat_forward_heads_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
+                           const uint32_t* row_indices, const uint32_t* dst_local_id,
+                           uint32_t v_size, const float* H, uint64_t ldh, uint32_t heads,
+                           uint32_t D, const float* att, float* m_out, float* a_out, float* Y,
+                           uint64_t ldy, int mean, const GatDrop* dr) {
+  GAT_CHECK(ctx && column_offset && row_indices && dst_local_id && H && att && m_out && a_out && Y,
+            "NULL argument");
+  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
+  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  const uint32_t F = heads * D, FY = mean ? D : F;
+  GAT_CHECK(ldh >= F && ldy >= FY, "leading dimension");
+  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att);
+  const HeadsShape hs = heads_shape(heads, D, v4);
+  GAT_CHECK(hs.nch <= 4, kGatHeadsWidthMsg);
+  if (v_size == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const uint32_t n = v_size;
+  // mean mode: one row of nch * 64 vectors per wave (16 KiB a block at VEC 4, NCH 4)
+  const size_t lds = mean ? (size_t)(kGatThreads / 64) * hs.nch * 64 * (v4 ? 16 : 4) : 0;
+#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, att, \
+             m_out, a_out, Y, ldy, mean
+  if (!dr) {
+#define ARGS BASE
+#define GAT_T
+    NTS_GAT_HEADS_DISPATCH(k_gat_fwd_heads);
+#undef GAT_T
+#undef ARGS
+  } else {
+#define ARGS BASE, *dr
+#define GAT_T GAT_T_DROP
+    NTS_GAT_HEADS_DISPATCH(k_gat_fwd_heads);
+#undef GAT_T
+#undef ARGS
+  }
+#undef BASE
+  return NTS_OK;
+}
+
+int gat_backward_heads_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
+                            const uint32_t* row_indices, const uint32_t* dst_local_id,
+                            uint32_t v_size, const uint32_t* row_offset,
+                            const uint32_t* column_indices, const uint32_t* csr_edge_id,
+                            uint32_t src_size, const float* H, uint64_t ldh, uint32_t heads,
+                            uint32_t D, const float* att, const float* a, const float* m,
+                            const float* Y, uint64_t ldy, const float* GY, uint64_t ldg, float* du,
+                            float* ds2, float* GM, uint64_t ldm, float* dH, uint64_t lddh,
+                            float* dS, int mean, const GatDrop* dr) {
+  GAT_CHECK(ctx && column_offset && row_indices && dst_local_id && row_offset && column_indices &&
+                csr_edge_id && H && att && a && m && Y && GY && du && ds2 && GM && dH && dS,
+            "NULL argument");
+  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
+  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  const uint32_t F = heads * D, FY = mean ? D : F;
+  GAT_CHECK(ldm >= F, "leading dimension of GM");
+  GAT_CHECK(ldh >= F && ldy >= FY && ldg >= FY && lddh >= F, "leading dimension");
+  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 &&
+                  lddh % 4 == 0 && ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 &&
+                  ((uintptr_t)dH % 16) == 0 && ((uintptr_t)GM % 16) == 0;
+  const HeadsShape hs = heads_shape(heads, D, v4);
+  // a refused shape leaves every output as it was: checked before ds2 is cleared
+  GAT_CHECK(hs.nch <= 4, kGatHeadsWidthMsg);
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const size_t lds = 0;  // the backward kernels use no LDS
+  if (src_size)
+    NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * heads * sizeof(float), st));
+  if (v_size) {
+    const uint32_t n = v_size;
+#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, a, m, \
+             Y, ldy, GY, ldg, du, ds2, GM, ldm, mean
+    if (!dr) {
+#define ARGS BASE
+#define GAT_T
+      NTS_GAT_HEADS_DISPATCH(k_gat_bwd_dst_heads);
+#undef GAT_T
+#undef ARGS
+    } else {
+#define ARGS BASE, *dr
+#define GAT_T GAT_T_DROP
+      NTS_GAT_HEADS_DISPATCH(k_gat_bwd_dst_heads);
+#undef GAT_T
+#undef ARGS
+    }
+#undef BASE
+  }
+  if (src_size) {
+    const uint32_t n = src_size;
+    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));
+#define BASE row_offset, column_indices, csr_edge_id, src_size, hs.nvec, hs.g, heads, a, du, ds2, \
+             att, GM, ldm, dH, lddh, dS
+    if (!dr) {
+#define ARGS BASE
+#define GAT_T
+      if (v4) {
+        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 4, 0)
+      } else {
+        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 1, 0)
+      }
+#undef GAT_T
+#undef ARGS
+    } else {
+#define ARGS BASE, *dr
+#define GAT_T GAT_T_DROP
+      if (v4) {
+        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 4, 0)
+      } else {
+        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 1, 0)
+      }
+#undef GAT_T
+#undef ARGS
+    }
+#undef BASE
+    NTS_LAUNCH_CHECK();
+  }
+  return NTS_OK;
+}
+
+int gat_forward_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
+                     const uint32_t* row_indices, const uint32_t* dst_local_id, uint32_t v_size,
+                     const float* H, uint64_t ldh, uint32_t F, const float* att, float* m_out,
+                     float* a_out, float* Y, uint64_t ldy, const GatDrop* dr) {
+  GAT_CHECK(ctx && column_offset && row_indices && dst_local_id && H && att && m_out && a_out && Y,
+            "NULL argument");
+  GAT_CHECK(ldh >= F && ldy >= F, "leading dimension");
+  if (v_size == 0 || F == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att);
+  const uint32_t n = v_size;
+#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, att, m_out, a_out, Y, ldy
+#define ARGS BASE
+#define ARGS_DROP BASE, *dr
+  if (!dr)
+    NTS_GAT_DISPATCH(k_gat_fwd, ARGS, GAT_T_NONE);
+  else
+    NTS_GAT_DISPATCH(k_gat_fwd, ARGS_DROP, GAT_T_DROP);
+#undef BASE
+  return NTS_OK;
+}
+
+int gat_backward_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
+                      const uint32_t* row_indices, const uint32_t* dst_local_id, uint32_t v_size,
+                      const uint32_t* row_offset, const uint32_t* column_indices,
+                      const uint32_t* csr_edge_id, uint32_t src_size, const float* H, uint64_t ldh,
+                      uint32_t F, const float* att, const float* a, const float* m, const float* Y,
+                      uint64_t ldy, const float* GY, uint64_t ldg, float* du, float* ds2, float* GM,
+                      uint64_t ldm, float* dH, uint64_t lddh, float* dS, const GatDrop* dr) {
+  GAT_CHECK(ctx && column_offset && row_indices && dst_local_id && row_offset && column_indices &&
+                csr_edge_id && H && att && a && m && Y && GY && du && ds2 && GM && dH && dS,
+            "NULL argument");
+  GAT_CHECK(ldm >= F, "leading dimension of GM");
+  GAT_CHECK(ldh >= F && ldy >= F && ldg >= F && lddh >= F, "leading dimension");
+  if (F == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const hipStream_t st = ctx->stream;
+  const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 && lddh % 4 == 0 &&
+                  ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 && ((uintptr_t)dH % 16) == 0 &&
+                  ((uintptr_t)GM % 16) == 0;
+  // a refused width leaves every output as it was: checked before ds2 is cleared
+  GAT_CHECK((v4 ? F / 4 : F) <= 256, kGatWidthMsg);
+  if (src_size) NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * sizeof(float), st));
+  if (v_size) {
+    const uint32_t n = v_size;
+#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm
+    if (!dr)
+      NTS_GAT_DISPATCH(k_gat_bwd_dst, ARGS, GAT_T_NONE);
+    else
+      NTS_GAT_DISPATCH(k_gat_bwd_dst, ARGS_DROP, GAT_T_DROP);
+#undef BASE
+  }
+  if (src_size) {
+    const uint32_t n = src_size;
+#define BASE row_offset, column_indices, csr_edge_id, src_size, nvec, a, du, ds2, att, GM, ldm, dH, lddh, dS
+    if (!dr)
+      NTS_GAT_DISPATCH(k_gat_bwd_src, ARGS, GAT_T_NONE);
+    else
+      NTS_GAT_DISPATCH(k_gat_bwd_src, ARGS_DROP, GAT_T_DROP);
+#undef BASE
+  }
+#undef ARGS
+#undef ARGS_DROP
+  return NTS_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int nts_hip_gat_forward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -764,27 +1169,22 @@ int nts_hip_gat_forward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
                               uint32_t v_size, const float* H, uint64_t ldh, uint32_t heads,
                               uint32_t D, const float* att, float* m_out, float* a_out, float* Y,
                               uint64_t ldy, int mean) {
-  NTS_CHECK_ARG(ctx && column_offset && row_indices && dst_local_id && H && att && m_out &&
-                    a_out && Y,
-                "NULL argument");
-  NTS_CHECK_ARG(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
-  NTS_CHECK_ARG((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
-  const uint32_t F = heads * D, FY = mean ? D : F;
-  NTS_CHECK_ARG(ldh >= F && ldy >= FY, "leading dimension");
-  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att);
-  const HeadsShape hs = heads_shape(heads, D, v4);
-  NTS_CHECK_ARG(hs.nch <= 4, kGatHeadsWidthMsg);
-  if (v_size == 0) return NTS_OK;
-  NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const uint32_t n = v_size;
-  // mean mode: one row of nch * 64 vectors per wave (16 KiB a block at VEC 4, NCH 4)
-  const size_t lds = mean ? (size_t)(kGatThreads / 64) * hs.nch * 64 * (v4 ? 16 : 4) : 0;
-#define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, att, \
-             m_out, a_out, Y, ldy, mean
-  NTS_GAT_HEADS_DISPATCH(k_gat_fwd_heads);
-#undef ARGS
-  return NTS_OK;
+  return gat_forward_heads_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size, H,
+                                ldh, heads, D, att, m_out, a_out, Y, ldy, mean, nullptr);
+}
+
+int nts_hip_gat_forward_heads_drop(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                                   const uint32_t* row_indices, const uint32_t* dst_local_id,
+                                   uint32_t v_size, const float* H, uint64_t ldh, uint32_t heads,
+                                   uint32_t D, const float* att, float* m_out, float* a_out,
+                                   float* Y, uint64_t ldy, int mean, float p_attn, float p_out,
+                                   uint64_t seed, uint64_t off_attn, uint64_t off_out) {
+  const char* fn = __func__;
+  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
+  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, off_out);
+  return gat_forward_heads_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size, H, ldh,
+                                heads, D, att, m_out, a_out, Y, ldy, mean,
+                                p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
 }
 
 int nts_hip_gat_backward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -796,66 +1196,50 @@ int nts_hip_gat_backward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
                                const float* Y, uint64_t ldy, const float* GY, uint64_t ldg,
                                float* du, float* ds2, float* GM, uint64_t ldm, float* dH,
                                uint64_t lddh, float* dS, int mean) {
-  NTS_CHECK_ARG(ctx && column_offset && row_indices && dst_local_id && row_offset &&
-                    column_indices && csr_edge_id && H && att && a && m && Y && GY && du &&
-                    ds2 && GM && dH && dS,
-                "NULL argument");
-  NTS_CHECK_ARG(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
-  NTS_CHECK_ARG((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
-  const uint32_t F = heads * D, FY = mean ? D : F;
-  NTS_CHECK_ARG(ldm >= F, "leading dimension of GM");
-  NTS_CHECK_ARG(ldh >= F && ldy >= FY && ldg >= FY && lddh >= F, "leading dimension");
-  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 &&
-                  lddh % 4 == 0 && ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 &&
-                  ((uintptr_t)dH % 16) == 0 && ((uintptr_t)GM % 16) == 0;
-  const HeadsShape hs = heads_shape(heads, D, v4);
-  // a refused shape leaves every output as it was: checked before ds2 is cleared
-  NTS_CHECK_ARG(hs.nch <= 4, kGatHeadsWidthMsg);
-  NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const size_t lds = 0;  // the backward kernels use no LDS
-  if (src_size)
-    NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * heads * sizeof(float), st));
-  if (v_size) {
-    const uint32_t n = v_size;
-#define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, a, m, \
-             Y, ldy, GY, ldg, du, ds2, GM, ldm, mean
-    NTS_GAT_HEADS_DISPATCH(k_gat_bwd_dst_heads);
-#undef ARGS
-  }
-  if (src_size) {
-    const uint32_t n = src_size;
-    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));
-#define ARGS row_offset, column_indices, csr_edge_id, src_size, hs.nvec, hs.g, heads, a, du, ds2, \
-             att, GM, ldm, dH, lddh, dS
-    if (v4) {
-      NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 4, 0)
-    } else {
-      NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 1, 0)
-    }
-#undef ARGS
-    NTS_LAUNCH_CHECK();
-  }
-  return NTS_OK;
+  return gat_backward_heads_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size,
+                                 row_offset, column_indices, csr_edge_id, src_size, H, ldh, heads, D,
+                                 att, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm, dH, lddh, dS, mean,
+                                 nullptr);
+}
+
+int nts_hip_gat_backward_heads_drop(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                                    const uint32_t* row_indices, const uint32_t* dst_local_id,
+                                    uint32_t v_size, const uint32_t* row_offset,
+                                    const uint32_t* column_indices, const uint32_t* csr_edge_id,
+                                    uint32_t src_size, const float* H, uint64_t ldh, uint32_t heads,
+                                    uint32_t D, const float* att, const float* a, const float* m,
+                                    const float* Y, uint64_t ldy, const float* GY, uint64_t ldg,
+                                    float* du, float* ds2, float* GM, uint64_t ldm, float* dH,
+                                    uint64_t lddh, float* dS, int mean, float p_attn, float p_out,
+                                    uint64_t seed, uint64_t off_attn) {
+  const char* fn = __func__;
+  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
+  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, 0);
+  return gat_backward_heads_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size,
+                                 row_offset, column_indices, csr_edge_id, src_size, H, ldh, heads, D,
+                                 att, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm, dH, lddh, dS, mean,
+                                 p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
 }
 
 int nts_hip_gat_forward(nts_hip_ctx* ctx, const uint32_t* column_offset,
                         const uint32_t* row_indices, const uint32_t* dst_local_id,
                         uint32_t v_size, const float* H, uint64_t ldh, uint32_t F,
                         const float* att, float* m_out, float* a_out, float* Y, uint64_t ldy) {
-  NTS_CHECK_ARG(ctx && column_offset && row_indices && dst_local_id && H && att && m_out &&
-                    a_out && Y,
-                "NULL argument");
-  NTS_CHECK_ARG(ldh >= F && ldy >= F, "leading dimension");
-  if (v_size == 0 || F == 0) return NTS_OK;
-  NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att);
-  const uint32_t n = v_size;
-#define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, att, m_out, a_out, Y, ldy
-  NTS_GAT_DISPATCH(k_gat_fwd, ARGS);
-#undef ARGS
-  return NTS_OK;
+  return gat_forward_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size, H, ldh, F,
+                          att, m_out, a_out, Y, ldy, nullptr);
+}
+
+int nts_hip_gat_forward_drop(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                             const uint32_t* row_indices, const uint32_t* dst_local_id,
+                             uint32_t v_size, const float* H, uint64_t ldh, uint32_t F,
+                             const float* att, float* m_out, float* a_out, float* Y, uint64_t ldy,
+                             float p_attn, float p_out, uint64_t seed, uint64_t off_attn,
+                             uint64_t off_out) {
+  const char* fn = __func__;
+  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
+  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, off_out);
+  return gat_forward_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size, H, ldh, F, att,
+                          m_out, a_out, Y, ldy, p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
 }
 
 int nts_hip_gat_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -866,33 +1250,42 @@ int nts_hip_gat_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
                          const float* att, const float* a, const float* m, const float* Y,
                          uint64_t ldy, const float* GY, uint64_t ldg, float* du, float* ds2,
                          float* GM, uint64_t ldm, float* dH, uint64_t lddh, float* dS) {
-  NTS_CHECK_ARG(ctx && column_offset && row_indices && dst_local_id && row_offset &&
-                    column_indices && csr_edge_id && H && att && a && m && Y && GY && du &&
-                    ds2 && GM && dH && dS,
-                "NULL argument");
-  NTS_CHECK_ARG(ldm >= F, "leading dimension of GM");
-  NTS_CHECK_ARG(ldh >= F && ldy >= F && ldg >= F && lddh >= F, "leading dimension");
-  if (F == 0) return NTS_OK;
+  return gat_backward_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size,
+                           row_offset, column_indices, csr_edge_id, src_size, H, ldh, F, att, a, m, Y,
+                           ldy, GY, ldg, du, ds2, GM, ldm, dH, lddh, dS, nullptr);
+}
+
+int nts_hip_gat_backward_drop(nts_hip_ctx* ctx, const uint32_t* column_offset,
+                              const uint32_t* row_indices, const uint32_t* dst_local_id,
+                              uint32_t v_size, const uint32_t* row_offset,
+                              const uint32_t* column_indices, const uint32_t* csr_edge_id,
+                              uint32_t src_size, const float* H, uint64_t ldh, uint32_t F,
+                              const float* att, const float* a, const float* m, const float* Y,
+                              uint64_t ldy, const float* GY, uint64_t ldg, float* du, float* ds2,
+                              float* GM, uint64_t ldm, float* dH, uint64_t lddh, float* dS,
+                              float p_attn, float p_out, uint64_t seed, uint64_t off_attn) {
+  const char* fn = __func__;
+  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
+  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, 0);
+  return gat_backward_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size, row_offset,
+                           column_indices, csr_edge_id, src_size, H, ldh, F, att, a, m, Y, ldy, GY,
+                           ldg, du, ds2, GM, ldm, dH, lddh, dS,
+                           p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
+}
+
+int nts_hip_dropout_f32(nts_hip_ctx* ctx, uint32_t rows, uint32_t feature_size, const float* x,
+                        uint64_t ldx, float p, uint64_t seed, uint64_t offset, float* y,
+                        uint64_t ldy) {
+  NTS_CHECK_ARG(ctx && x && y, "NULL argument");
+  NTS_CHECK_ARG(ldx >= feature_size && ldy >= feature_size, "leading dimension");
+  NTS_CHECK_ARG(gat_rate_ok(p), kGatRateMsg);
+  if (rows == 0 || feature_size == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 && lddh % 4 == 0 &&
-                  ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 && ((uintptr_t)dH % 16) == 0 &&
-                  ((uintptr_t)GM % 16) == 0;
-  // a refused width leaves every output as it was: checked before ds2 is cleared
-  NTS_CHECK_ARG((v4 ? F / 4 : F) <= 256, kGatWidthMsg);
-  if (src_size) NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * sizeof(float), st));
-  if (v_size) {
-    const uint32_t n = v_size;
-#define ARGS column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm
-    NTS_GAT_DISPATCH(k_gat_bwd_dst, ARGS);
-#undef ARGS
-  }
-  if (src_size) {
-    const uint32_t n = src_size;
-#define ARGS row_offset, column_indices, csr_edge_id, src_size, nvec, a, du, ds2, att, GM, ldm, dH, lddh, dS
-    NTS_GAT_DISPATCH(k_gat_bwd_src, ARGS);
-#undef ARGS
-  }
+  const uint64_t blocks = (uint64_t)((rows + 3) / 4) * ((feature_size + 1) / 2);
+  const uint32_t gs = std::max(1u, std::min(ceil_div(blocks, 256), kMaxGrid));
+  hipLaunchKernelGGL(k_dropout, dim3(gs), dim3(256), 0, ctx->stream, x, ldx, rows, feature_size,
+                     dropout_threshold(p), p >= 1.f ? 0.f : 1.0f / (1.0f - p), seed, offset, y, ldy);
+  NTS_LAUNCH_CHECK();
   return NTS_OK;
 }
 

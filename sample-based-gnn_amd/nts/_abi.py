@@ -62,6 +62,8 @@ EXPORTED = (
     "nts_hip_gat_forward_heads", "nts_hip_gat_backward_heads",
     "nts_hip_gat_scores", "nts_hip_gat_graph_fwd",
     "nts_hip_ln_act_fwd", "nts_hip_ln_act_bwd",
+    "nts_hip_gat_forward_drop", "nts_hip_gat_backward_drop", "nts_hip_gat_forward_heads_drop",
+    "nts_hip_gat_backward_heads_drop", "nts_hip_dropout_f32",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -187,6 +189,16 @@ def lib() -> C.CDLL:
         "nts_hip_gat_forward_heads": ([P, P, P, P, U32, P, U64, U32, U32, P, P, P, P, U64, I], I),
         "nts_hip_gat_backward_heads": ([P, P, P, P, U32, P, P, P, U32, P, U64, U32, U32, P, P, P, P,
                                         U64, P, U64, P, P, P, U64, P, U64, P, I], I),
+        "nts_hip_gat_forward_drop": ([P, P, P, P, U32, P, U64, U32, P, P, P, P, U64,
+                                      F, F, U64, U64, U64], I),
+        "nts_hip_gat_backward_drop": ([P, P, P, P, U32, P, P, P, U32, P, U64, U32, P, P, P, P, U64,
+                                       P, U64, P, P, P, U64, P, U64, P, F, F, U64, U64], I),
+        "nts_hip_gat_forward_heads_drop": ([P, P, P, P, U32, P, U64, U32, U32, P, P, P, P, U64, I,
+                                            F, F, U64, U64, U64], I),
+        "nts_hip_gat_backward_heads_drop": ([P, P, P, P, U32, P, P, P, U32, P, U64, U32, U32, P, P,
+                                             P, P, U64, P, U64, P, P, P, U64, P, U64, P, I,
+                                             F, F, U64, U64], I),
+        "nts_hip_dropout_f32": ([P, U32, U32, P, U64, F, U64, U64, P, U64], I),
         "nts_hip_gat_scores": ([P, P, U64, U64, U32, U32, P, P], I),
         "nts_hip_gat_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, P, U64, U32, U32, P, P, U64, I], I),
         "nts_hip_ln_act_fwd": ([P, U64, U32, P, U64, P, P, F, F, U64, U64, P, U64, P, P], I),

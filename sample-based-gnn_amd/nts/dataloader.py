@@ -324,6 +324,11 @@ class InputInfo:
     # (LAYERS keeps the concatenated width), the last layer averages them.
     # GAT algorithms only; absent = single-head
     gat_heads: list = field(default_factory=list)
+    # GAT_ATTN_DROP / GAT_FEAT_DROP (this build's keys): dropout of the attention
+    # coefficients and of every layer's input, in [0, 1), training only.  GAT
+    # algorithms only; DROP_RATE stays unread by them (as in the reference)
+    gat_attn_drop: float = 0.0
+    gat_feat_drop: float = 0.0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -354,6 +359,8 @@ class InputInfo:
             "AGGREGATOR": ("aggregator", _aggregator),
             "LAYER_NORM": ("layer_norm", int),
             "GAT_HEADS": ("gat_heads", _gat_heads),
+            "GAT_ATTN_DROP": ("gat_attn_drop", float),
+            "GAT_FEAT_DROP": ("gat_feat_drop", float),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -156,6 +156,61 @@ class HipContext:
             heads, D, ptr(att), ptr(a), ptr(m), ptr(Y), Y.stride(0), ptr(GY), GY.stride(0), ptr(du),
             ptr(ds2), ptr(GM), GM.stride(0), ptr(dH), dH.stride(0), ptr(dS), int(bool(mean))))
 
+    # The dropout forms: p_attn on the attention coefficients, p_out
+    # on the written Y, both from the keep bits of relu_dropout under `seed` at
+    # off_attn (element (CSC edge position, head)) and off_out (element of Y).
+    def gat_forward_drop(self, co, ri, dl, v, H, att, m, a, Y, p_attn=0.0, p_out=0.0, seed=0,
+                         off_attn=0, off_out=0):
+        F = H.shape[1]
+        check(self.lib.nts_hip_gat_forward_drop(
+            self.h, ptr(co), ptr(ri), ptr(dl), v, ptr(H), H.stride(0), F, ptr(att), ptr(m), ptr(a),
+            ptr(Y), Y.stride(0), float(p_attn), float(p_out), int(seed), int(off_attn),
+            int(off_out)))
+
+    def gat_backward_drop(self, co, ri, dl, v, ro, ci, ceid, s, H, att, a, m, Y, GY, du, ds2, dH, dS,
+                          GM=None, p_attn=0.0, p_out=0.0, seed=0, off_attn=0):
+        F = H.shape[1]
+        if GM is None:
+            GM = torch.empty(max(v, 1), F, device=H.device)
+        check(self.lib.nts_hip_gat_backward_drop(
+            self.h, ptr(co), ptr(ri), ptr(dl), v, ptr(ro), ptr(ci), ptr(ceid), s, ptr(H), H.stride(0),
+            F, ptr(att), ptr(a), ptr(m), ptr(Y), Y.stride(0), ptr(GY), GY.stride(0), ptr(du), ptr(ds2),
+            ptr(GM), GM.stride(0), ptr(dH), dH.stride(0), ptr(dS), float(p_attn), float(p_out),
+            int(seed), int(off_attn)))
+
+    def gat_forward_heads_drop(self, co, ri, dl, v, H, heads, att, m, a, Y, mean=False, p_attn=0.0,
+                               p_out=0.0, seed=0, off_attn=0, off_out=0):
+        heads = int(heads)
+        D = H.shape[1] // heads if heads > 0 else H.shape[1]
+        if heads > 0 and D * heads != H.shape[1]:
+            raise ValueError(f"gat_forward_heads_drop: {heads} heads do not divide width {H.shape[1]}")
+        check(self.lib.nts_hip_gat_forward_heads_drop(
+            self.h, ptr(co), ptr(ri), ptr(dl), v, ptr(H), H.stride(0), heads, D, ptr(att), ptr(m),
+            ptr(a), ptr(Y), Y.stride(0), int(bool(mean)), float(p_attn), float(p_out), int(seed),
+            int(off_attn), int(off_out)))
+
+    def gat_backward_heads_drop(self, co, ri, dl, v, ro, ci, ceid, s, H, heads, att, a, m, Y, GY, du,
+                                ds2, dH, dS, GM=None, mean=False, p_attn=0.0, p_out=0.0, seed=0,
+                                off_attn=0):
+        heads = int(heads)
+        F = H.shape[1]
+        D = F // heads if heads > 0 else F
+        if heads > 0 and D * heads != F:
+            raise ValueError(f"gat_backward_heads_drop: {heads} heads do not divide width {F}")
+        if GM is None:
+            GM = torch.empty(max(v, 1), F, device=H.device)
+        check(self.lib.nts_hip_gat_backward_heads_drop(
+            self.h, ptr(co), ptr(ri), ptr(dl), v, ptr(ro), ptr(ci), ptr(ceid), s, ptr(H), H.stride(0),
+            heads, D, ptr(att), ptr(a), ptr(m), ptr(Y), Y.stride(0), ptr(GY), GY.stride(0), ptr(du),
+            ptr(ds2), ptr(GM), GM.stride(0), ptr(dH), dH.stride(0), ptr(dS), int(bool(mean)),
+            float(p_attn), float(p_out), int(seed), int(off_attn)))
+
+    def dropout(self, x, y, p=0.0, seed=0, offset=0):
+        """y = keep ? x / (1 - p) : 0 with relu_dropout's keep bits; y may be x."""
+        rows, F = x.shape
+        check(self.lib.nts_hip_dropout_f32(self.h, rows, F, ptr(x), x.stride(0), float(p), int(seed),
+                                           int(offset), ptr(y), y.stride(0)))
+
     def gather_labels(self, labels, index, n_dev, n_cap, out):
         check(self.lib.nts_hip_gather_labels(self.h, ptr(labels), ptr(index), ptr(n_dev),
                                              n_cap, ptr(out)))

@@ -61,6 +61,20 @@ def check_gat_heads(layers, gat, gat_heads):
     return heads
 
 
+def check_gat_drop(gat, **rates):
+    """gat_attn_drop / gat_feat_drop as floats, or a ValueError with the
+    driver's text: a rate in [0, 1), and none above 0 without gat."""
+    out = {}
+    for name, value in rates.items():
+        value = float(value)
+        if not 0.0 <= value < 1.0:
+            raise ValueError(f"{name} must be in [0, 1), got {value}")
+        if value != 0.0 and not gat:
+            raise ValueError(f"{name} is not supported without gat (attention layers only)")
+        out[name] = value
+    return out
+
+
 def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, drop_rate=0.5,
                rng_mode=_abi.NTS_RNG_PHILOX, weight="sum", fused_gather=True,
                bias_correction=False, deterministic_backward=True, shuffle=True, profile=False,
@@ -70,10 +84,12 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                up_degree=False, gat=False, pd_cache=False, pd_rate=0.2, pd_super_batch=4,
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
-               gat_heads=None, layer_norm=False, layer_norm_eps=1e-5):
+               gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
+               gat_feat_drop=0.0):
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
     gat_heads = check_gat_heads(layers, gat, gat_heads)
+    gat_drop = check_gat_drop(gat, gat_attn_drop=gat_attn_drop, gat_feat_drop=gat_feat_drop)
     E = ext()
     c = E.GCNConfig()
     c.layer_size = list(layers)
@@ -113,6 +129,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.up_degree = bool(up_degree)
     c.gat = bool(gat)
     c.gat_heads = gat_heads
+    c.gat_attn_drop = gat_drop["gat_attn_drop"]  # GAT's own dropouts (drop_rate is not read
+    c.gat_feat_drop = gat_drop["gat_feat_drop"]  # by a GAT driver)
     c.pd_cache = bool(pd_cache)
     c.pd_rate = float(pd_rate)
     c.pd_super_batch = int(pd_super_batch)

@@ -1375,10 +1375,15 @@ void KernelProfiler::reset() {
 // columns h and K + h (the other columns, products of one head's rows with
 // another head's dS, are dropped): the GEMM is the MFMA kernel that is there,
 // deterministic, and at K <= 8 its 2K columns still fill one 16-column tile.
+// p_attn / p_out > 0: the _drop entry points (attention and output dropout in
+// the same kernels; the backward regenerates the attention keep bits from
+// (seed, off_attn) and reads the output mask off Y > 0).
 struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
   static NtsVar forward(AutogradContext* ctx, NtsVar X, NtsVar W, NtsVar Watt, int64_t sg_ptr,
-                        int64_t cs_ptr, int64_t prof_ptr, int64_t heads, bool mean) {
+                        int64_t cs_ptr, int64_t prof_ptr, int64_t heads, bool mean, double p_attn,
+                        double p_out, int64_t seed, int64_t off_attn, int64_t off_out) {
     auto* sg = reinterpret_cast<sampCSC*>(sg_ptr);
+    const bool drop = p_attn > 0.0 || p_out > 0.0;  // else today's entry points
     auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
     auto* prof = reinterpret_cast<KernelProfiler*>(prof_ptr);
     TORCH_CHECK(sg->dst_local_id.defined() && sg->csr_edge_id.defined(),
@@ -1403,7 +1408,23 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     NtsVar Y = torch::empty({v, FY}, f32_opts(dev));
     hipStream_t st = (hipStream_t)cs->stream();
     if (prof) prof->begin(KernelProfiler::GAT_FWD, st);
-    if (K == 1)
+    if (drop && K == 1)
+      hip_check(nts_hip_gat_forward_drop(
+                    cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
+                    H.data_ptr<float>(), (uint64_t)F, (uint32_t)F, Ac.data_ptr<float>(),
+                    m.data_ptr<float>(), a.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)F,
+                    (float)p_attn, (float)p_out, (uint64_t)seed, (uint64_t)off_attn,
+                    (uint64_t)off_out),
+                "nts_hip_gat_forward_drop");
+    else if (drop)
+      hip_check(nts_hip_gat_forward_heads_drop(
+                    cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
+                    H.data_ptr<float>(), (uint64_t)F, (uint32_t)K, (uint32_t)D,
+                    Ac.data_ptr<float>(), m.data_ptr<float>(), a.data_ptr<float>(),
+                    Y.data_ptr<float>(), (uint64_t)FY, mean ? 1 : 0, (float)p_attn, (float)p_out,
+                    (uint64_t)seed, (uint64_t)off_attn, (uint64_t)off_out),
+                "nts_hip_gat_forward_heads_drop");
+    else if (K == 1)
       hip_check(nts_hip_gat_forward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
                                     (uint32_t)v, H.data_ptr<float>(), (uint64_t)F, (uint32_t)F,
                                     Ac.data_ptr<float>(), m.data_ptr<float>(), a.data_ptr<float>(),
@@ -1429,12 +1450,21 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     ctx->saved_data["sg"] = sg_ptr;
     ctx->saved_data["cs"] = cs_ptr;
     ctx->saved_data["x_grad"] = X.requires_grad();
+    ctx->saved_data["p_attn"] = p_attn;
+    ctx->saved_data["p_out"] = p_out;
+    ctx->saved_data["seed"] = seed;
+    ctx->saved_data["off_attn"] = off_attn;
     return Y;
   }
   static torch::autograd::variable_list backward(AutogradContext* ctx,
                                                  torch::autograd::variable_list grads) {
     auto v_ = ctx->get_saved_variables();
     NtsVar X = v_[0], W = v_[1], A = v_[2], H = v_[3], Y = v_[4], m = v_[5], a = v_[6];
+    const double p_attn = ctx->saved_data["p_attn"].toDouble();
+    const double p_out = ctx->saved_data["p_out"].toDouble();
+    const uint64_t seed = (uint64_t)ctx->saved_data["seed"].toInt();
+    const uint64_t off_attn = (uint64_t)ctx->saved_data["off_attn"].toInt();
+    const bool drop = p_attn > 0.0 || p_out > 0.0;
     auto* sg = reinterpret_cast<sampCSC*>(ctx->saved_data["sg"].toInt());
     auto* cs = reinterpret_cast<NtsStream*>(ctx->saved_data["cs"].toInt());
     NtsVar GY = grads[0].contiguous();
@@ -1450,7 +1480,27 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     NtsVar dH = torch::empty({s, F}, f32_opts(dev));
     NtsVar dS = torch::empty({s, 2 * K}, f32_opts(dev));
     NtsVar GM = torch::empty({std::max<int64_t>(v, 1), F}, f32_opts(dev));
-    if (K > 1)
+    if (drop && K > 1)
+      hip_check(nts_hip_gat_backward_heads_drop(
+                    cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
+                    sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
+                    H.data_ptr<float>(), (uint64_t)F, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(),
+                    a.data_ptr<float>(), m.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)FY,
+                    GY.data_ptr<float>(), (uint64_t)FY, du.data_ptr<float>(), ds2.data_ptr<float>(),
+                    GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(), (uint64_t)F,
+                    dS.data_ptr<float>(), mean ? 1 : 0, (float)p_attn, (float)p_out, seed, off_attn),
+                "nts_hip_gat_backward_heads_drop");
+    else if (drop)
+      hip_check(nts_hip_gat_backward_drop(
+                    cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
+                    sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
+                    H.data_ptr<float>(), (uint64_t)F, (uint32_t)F, A.data_ptr<float>(),
+                    a.data_ptr<float>(), m.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)F,
+                    GY.data_ptr<float>(), (uint64_t)F, du.data_ptr<float>(), ds2.data_ptr<float>(),
+                    GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(), (uint64_t)F,
+                    dS.data_ptr<float>(), (float)p_attn, (float)p_out, seed, off_attn),
+                "nts_hip_gat_backward_drop");
+    else if (K > 1)
       hip_check(nts_hip_gat_backward_heads(
                     cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
                     sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
@@ -1496,15 +1546,28 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                                  dX.data_ptr<float>(), (uint64_t)Fin),
                 "nts_hip_gemm_f32(dX)");
     }
-    return {dX, dW, dA.view(A.sizes()), NtsVar(), NtsVar(), NtsVar(), NtsVar(), NtsVar()};
+    return {dX,       dW,       dA.view(A.sizes()), NtsVar(), NtsVar(), NtsVar(), NtsVar(),
+            NtsVar(), NtsVar(), NtsVar(),           NtsVar(), NtsVar(), NtsVar()};
   }
 };
 
 NtsVar hip_gat_layer(const NtsVar& x, const NtsVar& W, const NtsVar& Watt, sampCSC* sg,
-                     NtsStream* cs, KernelProfiler* prof, int heads, bool mean) {
+                     NtsStream* cs, KernelProfiler* prof, int heads, bool mean,
+                     const GatDropout& drop) {
   return HipGATLayerFn::apply(x, W, Watt, reinterpret_cast<int64_t>(sg),
                               reinterpret_cast<int64_t>(cs), reinterpret_cast<int64_t>(prof),
-                              (int64_t)heads, mean);
+                              (int64_t)heads, mean, drop.p_attn, drop.p_out, (int64_t)drop.seed,
+                              (int64_t)drop.off_attn, (int64_t)drop.off_out);
+}
+
+NtsVar hip_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offset, NtsStream* cs) {
+  NtsVar xc = row_major(x);
+  NtsVar y = torch::empty({xc.size(0), xc.size(1)}, xc.options());
+  hip_check(nts_hip_dropout_f32(cs->ctx(), (uint32_t)xc.size(0), (uint32_t)xc.size(1),
+                                xc.data_ptr<float>(), (uint64_t)xc.stride(0), (float)p, seed, offset,
+                                y.data_ptr<float>(), (uint64_t)y.size(1)),
+            "nts_hip_dropout_f32");
+  return y;
 }
 
 NtsVar hip_linear(const NtsVar& x, const NtsVar& W, NtsStream* cs) {

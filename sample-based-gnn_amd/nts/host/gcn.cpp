@@ -92,6 +92,12 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
       TORCH_CHECK(cfg.layer_size[l] <= 1024, "layer_norm is not supported with a hidden width above "
                                              "1024 (layer ", l - 1, ": ", cfg.layer_size[l], ")");
   }
+  for (const auto& r : {std::make_pair("gat_attn_drop", cfg.gat_attn_drop),
+                        std::make_pair("gat_feat_drop", cfg.gat_feat_drop)}) {
+    TORCH_CHECK(r.second >= 0.0 && r.second < 1.0, r.first, " must be in [0, 1), got ", r.second);
+    TORCH_CHECK(r.second == 0.0 || cfg.gat, r.first,
+                " is not supported without gat (attention layers only)");
+  }
   if (cfg.sample_gpu) {
     TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
     TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
@@ -563,11 +569,28 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_gat(SampledSubgraph* sg) {
     sampler->load_feature_gpu_cache(*cs, sg, X, *fcache);
   else
     sampler->load_feature_gpu(*cs, sg, X, F);
+  // gat_attn_drop / gat_feat_drop (training mode only): every mask
+  // takes the next dropout_calls_ in order of use — the input pass, then per
+  // layer the attention draw and (hidden layers) the output draw.  With both
+  // rates 0 no offset is drawn and the layers run the plain entry points.
+  const double q = ctx.is_train() ? cfg.gat_attn_drop : 0.0;
+  const double p = ctx.is_train() ? cfg.gat_feat_drop : 0.0;
+  if (p > 0.0) X = hip_dropout(X, p, dropout_key(), dropout_calls_++, cs.get());
   std::vector<NtsVar> acts;
   for (int l = 0; l < L; ++l) {
     const int hop = L - 1 - l;  // X_{l+1} = relu(attention aggregate of X_l W_l)
+    GatDropout drop;
+    drop.seed = dropout_key();
+    if (q > 0.0) {
+      drop.p_attn = q;
+      drop.off_attn = dropout_calls_++;
+    }
+    if (p > 0.0 && l < L - 1) {
+      drop.p_out = p;
+      drop.off_out = dropout_calls_++;
+    }
     X = hip_gat_layer(X, P[2 * l]->W, P[2 * l + 1]->W, sg->sampled_sgs[hop], cs.get(),
-                      profiler(), gat_heads(l), l == L - 1 && gat_heads(l) > 1);
+                      profiler(), gat_heads(l), l == L - 1 && gat_heads(l) > 1, drop);
     acts.push_back(X);
   }
   return acts;

@@ -28,7 +28,17 @@ struct GCNConfig {
   // is [F_in, K C] and its W_att [2 K C, 1].  Every layer's K D must be within
   // the kernels' width limit (1024 when D % 4 == 0, else 256).
   std::vector<int> gat_heads;
-  bool fused_gather = true;           // gather features inside the bottom aggregation
+  // GAT dropout (gat only, training mode only; no reference counterpart: the
+  // reference's GAT stores drop_rate and never uses it, and drop_rate stays
+  // ignored by a GAT driver).  gat_attn_drop: the normalised attention
+  // coefficients of every layer, a~ = keep ? a / (1 - q) : 0, the softmax still
+  // over all edges.  gat_feat_drop: the input of every layer — the gathered
+  // feature rows of layer 0 (no relu) and the relu'd output of every hidden
+  // layer (DGL's feat_drop / attn_drop, PyG's GATConv(dropout=)).  Both in
+  // [0, 1), fused into the GAT kernels; 0 = off: no launch, Philox
+  // offset or output differs from a build without the options.
+  double gat_attn_drop = 0.0, gat_feat_drop = 0.0;
+  bool fused_gather = true;          // gather features inside the bottom aggregation
   bool bias_correction = false;       // false: learn_local_with_decay_Adam (GPU drivers)
   bool deterministic_backward = true; // CSR transpose gather instead of atomics
   bool hip_gemm = true;               // layer GEMMs on the hand-written MFMA kernels

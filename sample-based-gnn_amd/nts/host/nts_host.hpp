@@ -457,10 +457,21 @@ NtsVar hip_linear(const NtsVar& x, const NtsVar& W, NtsStream* cs);
 // heads > 1: W's F columns are `heads` heads of F / heads columns, each with
 // its own softmax; the output is their concatenation [v_size, F], or with
 // `mean` the mean over the heads [v_size, F / heads] (relu in both).
+// GatDropout: p_attn drops the attention coefficients, p_out the
+// layer's output, with the shared keep bits under key `seed` at the two
+// offsets; both rates 0 (the default) run the plain entry points.
 class KernelProfiler;
+struct GatDropout {
+  double p_attn = 0.0, p_out = 0.0;
+  uint64_t seed = 0, off_attn = 0, off_out = 0;
+  bool on() const { return p_attn > 0.0 || p_out > 0.0; }
+};
 NtsVar hip_gat_layer(const NtsVar& x, const NtsVar& W, const NtsVar& Watt, sampCSC* sg,
                      NtsStream* cs, KernelProfiler* prof = nullptr, int heads = 1,
-                     bool mean = false);
+                     bool mean = false, const GatDropout& drop = GatDropout());
+// plain inverted dropout with the shared keep bits (nts_hip_dropout_f32), no
+// backward: the input pass of gat_feat_drop over untrained features
+NtsVar hip_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offset, NtsStream* cs);
 // CU masks splitting the device: `n` CUs spread evenly over the chip
 // (every (total/n)-th CU) and the complement
 std::vector<uint32_t> cu_mask_spread(int device, int n, bool complement);

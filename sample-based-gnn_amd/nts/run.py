@@ -37,6 +37,10 @@ LAYER_NORM:1 (GCN / GraphSAGE algorithms without PD cache): every hidden layer
 is dropout(relu(LayerNorm(.))) in one fused pass, with a gamma and a beta per
 hidden layer that are trained without weight decay.
 
+GAT_ATTN_DROP:0.6 / GAT_FEAT_DROP:0.6 (GAT algorithms): dropout of the attention
+coefficients and of every layer's input while training, fused into the GAT
+kernels.  DROP_RATE is not read by a GAT job (as in the reference).
+
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
 """
@@ -115,6 +119,10 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.gat_heads and model != "gat":
         raise SystemExit(f"ALGORITHM {info.algorithm}: GAT_HEADS is not supported with GCN / "
                          "GraphSAGE algorithms (GAT only)")
+    for key, rate in (("GAT_ATTN_DROP", info.gat_attn_drop), ("GAT_FEAT_DROP", info.gat_feat_drop)):
+        if rate and model != "gat":
+            raise SystemExit(f"ALGORITHM {info.algorithm}: {key} is not supported with GCN / "
+                             "GraphSAGE algorithms (GAT only; they read DROP_RATE)")
     if info.aggregator == "max" and (model == "gat" or place is not None):
         raise SystemExit(f"ALGORITHM {info.algorithm}: AGGREGATOR:max is not supported with GAT, "
                          "PD-cache or GCN_SAMPLE_GPU algorithms")
@@ -137,7 +145,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         pd_super_batch=max(info.pipeline_num, 1), sample_gpu=place == "sample_gpu",
         multi_label=bool(info.multi_label), root_weight=bool(info.root_weight),
         aggregator=info.aggregator, gat_heads=info.gat_heads or None,
-        layer_norm=bool(info.layer_norm))
+        layer_norm=bool(info.layer_norm), gat_attn_drop=info.gat_attn_drop,
+        gat_feat_drop=info.gat_feat_drop)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
