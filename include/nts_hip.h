@@ -627,6 +627,56 @@ int nts_hip_gat_backward_heads_drop(nts_hip_ctx *ctx, const uint32_t *column_off
 int nts_hip_dropout_f32(nts_hip_ctx *ctx, uint32_t rows, uint32_t feature_size, const float *x,
                         uint64_t ldx, float p, uint64_t seed, uint64_t offset, float *y,
                         uint64_t ldy);
+/* The GATv2 layer (Brody et al., ICLR 2022: "dynamic" attention; no reference
+ * counterpart), K = heads heads of D columns, F = K D.  Hs [src_size, F] holds
+ * the source rows X W_s (also the aggregated values), Hd [v_size, F] one row
+ * X[dst] W_d per destination, in destination order (no dst_local_id), att [F]
+ * the score vectors of the K heads:
+ *   t[e]   = leaky_relu(Hs[src_e] + Hd[d_e], 0.2)        (F wide, never stored)
+ *   u[e,h] = t[e]_h . att_h                               (u_out, edge-major [e, K])
+ *   a[e,h] = softmax over the edges of d of u[., h]       (a_out, [e, K], undropped)
+ *   a~[e,h] = keepA(e,h) ? a[e,h] / (1 - p_attn) : 0      (a itself when p_attn == 0)
+ *   Z_h[d] = sum_e a~[e,h] Hs[src_e]_h
+ *   mean == 0: Y[d] = relu([Z_0 | ... | Z_{K-1}]) (F wide);  mean != 0: relu((1/K) sum_h Z_h) (D wide)
+ *   Y[d,c] <- keepF(d,c) ? Y[d,c] / (1 - p_out) : 0.
+ * Empty columns give a zero row; edge order, the keep bits (element (e, h) at
+ * off_attn, element (d, c) of Y at off_out, key `seed`), the 1 / (1 - p) float
+ * scales and the p >= 1 rule are those of nts_hip_gat_forward_heads_drop; with
+ * both rates 0 the plain kernels run.  Backward, for GY = dL/dY (Y / GY F or D
+ * wide as in the forward; du [e, K]; GM, dHs, dHd F wide; datt [F]):
+ *   GM[d]   = GY[d] [Y > 0] / (1 - p_out)                 (mean: / K, for every head)
+ *   ga[e,h] = (GM[d]_h . Hs[src_e]_h) keepA(e,h) / (1 - p_attn)
+ *   du[e,h] = a[e,h] (ga[e,h] - sum_e a ga)               (dL/du)
+ *   q[e][c] = du[e, head(c)] att[c] leaky'(Hs[src_e][c] + Hd[d_e][c])
+ *   dHd[d]  = sum_{e of d} q[e]                           (CSC order)
+ *   dHs[v]  = sum_{e: src_e = v} (a~[e] GM[d_e] + q[e])   (CSR order, via csr_edge_id)
+ *   datt[c] = sum_e du[e, head(c)] t[e][c]
+ * with leaky' = 1 for a positive sum and 0.2 otherwise, recomputed from Hs and
+ * Hd.  Nothing F wide per edge is written.  No float atomics: datt is summed
+ * over fixed runs of destinations (their length a function of v_size alone),
+ * the partial rows (in the context's scratch) then added in order, so two
+ * calls give the same bytes for every output.  Width limit: F <= 1024 on the
+ * float4 path (D % 4 == 0, every row pointer and att 16-byte aligned, every
+ * pitch a multiple of 4, over all row operands of the call), F <= 256
+ * otherwise.  A wider F, heads == 0, D == 0 or a rate that is negative, above
+ * 1 or NaN return NTS_ERR_INVALID with a message that states the limits,
+ * before any write. */
+int nts_hip_gatv2_forward(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                          const uint32_t *row_indices, uint32_t v_size, const float *Hs,
+                          uint64_t ldhs, const float *Hd, uint64_t ldhd, uint32_t heads,
+                          uint32_t D, const float *att, float *u_out, float *a_out, float *Y,
+                          uint64_t ldy, int mean, float p_attn, float p_out, uint64_t seed,
+                          uint64_t off_attn, uint64_t off_out);
+int nts_hip_gatv2_backward(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                           const uint32_t *row_indices, uint32_t v_size,
+                           const uint32_t *row_offset, const uint32_t *column_indices,
+                           const uint32_t *csr_edge_id, uint32_t src_size, const float *Hs,
+                           uint64_t ldhs, const float *Hd, uint64_t ldhd, uint32_t heads,
+                           uint32_t D, const float *att, const float *a, const float *Y,
+                           uint64_t ldy, const float *GY, uint64_t ldg, float *du, float *GM,
+                           uint64_t ldm, float *dHs, uint64_t lddhs, float *dHd, uint64_t lddhd,
+                           float *datt, int mean, float p_attn, float p_out, uint64_t seed,
+                           uint64_t off_attn);
 
 /* ---- dense layer update (MFMA fp32) -------------------------------------- */
 /* Row-major fp32 GEMM on the matrix cores (v_mfma_f32_16x16x4_f32 /

@@ -64,6 +64,7 @@ EXPORTED = (
     "nts_hip_ln_act_fwd", "nts_hip_ln_act_bwd",
     "nts_hip_gat_forward_drop", "nts_hip_gat_backward_drop", "nts_hip_gat_forward_heads_drop",
     "nts_hip_gat_backward_heads_drop", "nts_hip_dropout_f32",
+    "nts_hip_gatv2_forward", "nts_hip_gatv2_backward",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -199,6 +200,11 @@ def lib() -> C.CDLL:
                                              P, P, U64, P, U64, P, P, P, U64, P, U64, P, I,
                                              F, F, U64, U64], I),
         "nts_hip_dropout_f32": ([P, U32, U32, P, U64, F, U64, U64, P, U64], I),
+        "nts_hip_gatv2_forward": ([P, P, P, U32, P, U64, P, U64, U32, U32, P, P, P, P, U64, I,
+                                   F, F, U64, U64, U64], I),
+        "nts_hip_gatv2_backward": ([P, P, P, U32, P, P, P, U32, P, U64, P, U64, U32, U32, P, P, P,
+                                    U64, P, U64, P, P, U64, P, U64, P, U64, P, I,
+                                    F, F, U64, U64], I),
         "nts_hip_gat_scores": ([P, P, U64, U64, U32, U32, P, P], I),
         "nts_hip_gat_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, P, U64, U32, U32, P, P, U64, I], I),
         "nts_hip_ln_act_fwd": ([P, U64, U32, P, U64, P, P, F, F, U64, U64, P, U64, P, P], I),

@@ -329,6 +329,10 @@ class InputInfo:
     # algorithms only; DROP_RATE stays unread by them (as in the reference)
     gat_attn_drop: float = 0.0
     gat_feat_drop: float = 0.0
+    # GAT_V2 (this build's key): 1 = GATv2 scores, att . leaky_relu(W_s x_src +
+    # W_d x_dst), in every attention layer (GAT algorithms only; not with
+    # FULL_INFERENCE)
+    gat_v2: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -361,6 +365,7 @@ class InputInfo:
             "GAT_HEADS": ("gat_heads", _gat_heads),
             "GAT_ATTN_DROP": ("gat_attn_drop", float),
             "GAT_FEAT_DROP": ("gat_feat_drop", float),
+            "GAT_V2": ("gat_v2", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -205,6 +205,42 @@ class HipContext:
             ptr(ds2), ptr(GM), GM.stride(0), ptr(dH), dH.stride(0), ptr(dS), int(bool(mean)),
             float(p_attn), float(p_out), int(seed), int(off_attn)))
 
+    # GATv2: Hs [s, heads * D] the source rows, Hd [v, heads * D] one
+    # row per destination, att [heads * D]; u / a / du [e, heads] (edge-major);
+    # Y and GY [v, heads * D] (concat) or [v, D] (mean).  One pair of entry
+    # points carries heads and both dropouts.
+    def gatv2_forward(self, co, ri, v, Hs, Hd, heads, att, u, a, Y, mean=False, p_attn=0.0,
+                      p_out=0.0, seed=0, off_attn=0, off_out=0):
+        heads = int(heads)
+        F = Hs.shape[1]
+        D = F // heads if heads > 0 else F
+        if (heads > 0 and D * heads != F) or Hd.shape[1] != F:
+            raise ValueError(f"gatv2_forward: {heads} heads do not divide width {F}, or Hd is "
+                             f"{Hd.shape[1]} wide")
+        check(self.lib.nts_hip_gatv2_forward(
+            self.h, ptr(co), ptr(ri), v, ptr(Hs), Hs.stride(0), ptr(Hd), Hd.stride(0), heads, D,
+            ptr(att), ptr(u), ptr(a), ptr(Y), Y.stride(0), int(bool(mean)), float(p_attn),
+            float(p_out), int(seed), int(off_attn), int(off_out)))
+
+    def gatv2_backward(self, co, ri, v, ro, ci, ceid, s, Hs, Hd, heads, att, a, Y, GY, du, dHs, dHd,
+                       datt, GM=None, mean=False, p_attn=0.0, p_out=0.0, seed=0, off_attn=0):
+        """Its backward: dHs [s, heads * D], dHd [v, heads * D], datt [heads * D],
+        GM [v, heads * D] (the masked, scaled GY)."""
+        heads = int(heads)
+        F = Hs.shape[1]
+        D = F // heads if heads > 0 else F
+        if (heads > 0 and D * heads != F) or Hd.shape[1] != F:
+            raise ValueError(f"gatv2_backward: {heads} heads do not divide width {F}, or Hd is "
+                             f"{Hd.shape[1]} wide")
+        if GM is None:
+            GM = torch.empty(max(v, 1), F, device=Hs.device)
+        check(self.lib.nts_hip_gatv2_backward(
+            self.h, ptr(co), ptr(ri), v, ptr(ro), ptr(ci), ptr(ceid), s, ptr(Hs), Hs.stride(0),
+            ptr(Hd), Hd.stride(0), heads, D, ptr(att), ptr(a), ptr(Y), Y.stride(0), ptr(GY),
+            GY.stride(0), ptr(du), ptr(GM), GM.stride(0), ptr(dHs), dHs.stride(0), ptr(dHd),
+            dHd.stride(0), ptr(datt), int(bool(mean)), float(p_attn), float(p_out), int(seed),
+            int(off_attn)))
+
     def dropout(self, x, y, p=0.0, seed=0, offset=0):
         """y = keep ? x / (1 - p) : 0 with relu_dropout's keep bits; y may be x."""
         rows, F = x.shape

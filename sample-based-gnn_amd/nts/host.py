@@ -85,11 +85,13 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
-               gat_feat_drop=0.0):
+               gat_feat_drop=0.0, gat_v2=False):
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
     gat_heads = check_gat_heads(layers, gat, gat_heads)
     gat_drop = check_gat_drop(gat, gat_attn_drop=gat_attn_drop, gat_feat_drop=gat_feat_drop)
+    if gat_v2 and not gat:
+        raise ValueError("gat_v2 is not supported without gat (attention layers only)")
     E = ext()
     c = E.GCNConfig()
     c.layer_size = list(layers)
@@ -131,6 +133,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.gat_heads = gat_heads
     c.gat_attn_drop = gat_drop["gat_attn_drop"]  # GAT's own dropouts (drop_rate is not read
     c.gat_feat_drop = gat_drop["gat_feat_drop"]  # by a GAT driver)
+    if gat_v2:  # GATv2 scores; the default leaves the field as constructed
+        c.gat_v2 = True
     c.pd_cache = bool(pd_cache)
     c.pd_rate = float(pd_rate)
     c.pd_super_batch = int(pd_super_batch)

@@ -242,6 +242,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("up_degree", &GCNConfig::up_degree)
       .def_readwrite("gat", &GCNConfig::gat)
       .def_readwrite("gat_heads", &GCNConfig::gat_heads)
+      .def_readwrite("gat_v2", &GCNConfig::gat_v2)
       .def_readwrite("gat_attn_drop", &GCNConfig::gat_attn_drop)
       .def_readwrite("gat_feat_drop", &GCNConfig::gat_feat_drop)
       .def_readwrite("fuse_activation", &GCNConfig::fuse_activation)

@@ -1560,6 +1560,155 @@ NtsVar hip_gat_layer(const NtsVar& x, const NtsVar& W, const NtsVar& Watt, sampC
                               (int64_t)drop.off_attn, (int64_t)drop.off_out);
 }
 
+// GATv2 layer (no reference counterpart) on a merged src/dst
+// sampled block.  W is the stacked parameter [F_in, 2F] = [W_s | W_d]:
+// Hs = X W_s over all source rows, Hd = X[dst_local_id] W_d over the v
+// destination rows only (s is several times v), both on the MFMA GEMM, then
+// the fused score / softmax / aggregation / relu kernel.  The backward runs the
+// two deterministic kernels (datt comes straight from them) and four GEMMs:
+// dW = [X^T dHs | X[dst]^T dHd], dX = dHs W_s^T, plus dHd W_d^T added at the
+// rows dst_local_id (the map is injective: no two rows meet).
+struct HipGATv2LayerFn : public torch::autograd::Function<HipGATv2LayerFn> {
+  static NtsVar forward(AutogradContext* ctx, NtsVar X, NtsVar W, NtsVar Watt, int64_t sg_ptr,
+                        int64_t cs_ptr, int64_t prof_ptr, int64_t heads, bool mean, double p_attn,
+                        double p_out, int64_t seed, int64_t off_attn, int64_t off_out) {
+    auto* sg = reinterpret_cast<sampCSC*>(sg_ptr);
+    auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
+    auto* prof = reinterpret_cast<KernelProfiler*>(prof_ptr);
+    TORCH_CHECK(sg->dst_local_id.defined() && sg->csr_edge_id.defined(),
+                "GATv2 needs a merged src/dst layer with its CSR (set_merge_src_dst)");
+    TORCH_CHECK(W.size(1) % 2 == 0, "GATv2 layer: W must be [F_in, 2 F] = [W_s | W_d]");
+    const int64_t F = W.size(1) / 2;
+    TORCH_CHECK(heads >= 1 && F % heads == 0, "GATv2 layer: ", heads, " heads do not divide width ",
+                F);
+    const int64_t K = heads, D = F / heads;
+    if (K == 1) mean = false;  // one head: both modes are the single-head layer
+    NtsVar Xc = row_major(X), Ac = Watt.contiguous();
+    NtsVar Ws = W.narrow(1, 0, F).contiguous(), Wd = W.narrow(1, F, F).contiguous();
+    const int64_t s = sg->src_size, v = sg->v_size, e = sg->e_size;
+    const int64_t Fin = Xc.size(1);
+    TORCH_CHECK(Xc.size(0) == s && W.size(0) == Fin && Ac.numel() == F, "GATv2 layer shapes");
+    const int dev = cs->device();
+    NtsVar idx = sg->dst_local_id.narrow(0, 0, v).to(torch::kInt64);
+    NtsVar Xd = Xc.index_select(0, idx);
+    NtsVar Hs = torch::empty({s, F}, f32_opts(dev));
+    NtsVar Hd = torch::empty({std::max<int64_t>(v, 1), F}, f32_opts(dev));
+    hip_check(nts_hip_gemm_f32(cs->ctx(), 0, (int)s, (int)F, (int)Fin, Xc.data_ptr<float>(),
+                               (uint64_t)Xc.stride(0), Ws.data_ptr<float>(), (uint64_t)F,
+                               Hs.data_ptr<float>(), (uint64_t)F),
+              "nts_hip_gemm_f32(Hs)");
+    if (v)
+      hip_check(nts_hip_gemm_f32(cs->ctx(), 0, (int)v, (int)F, (int)Fin, Xd.data_ptr<float>(),
+                                 (uint64_t)Xd.stride(0), Wd.data_ptr<float>(), (uint64_t)F,
+                                 Hd.data_ptr<float>(), (uint64_t)F),
+                "nts_hip_gemm_f32(Hd)");
+    NtsVar u = torch::empty({std::max<int64_t>(e, 1) * K}, f32_opts(dev));
+    NtsVar a = torch::empty({std::max<int64_t>(e, 1) * K}, f32_opts(dev));
+    const int64_t FY = mean ? D : F;
+    NtsVar Y = torch::empty({v, FY}, f32_opts(dev));
+    hipStream_t st = (hipStream_t)cs->stream();
+    if (prof) prof->begin(KernelProfiler::GAT_FWD, st);
+    hip_check(nts_hip_gatv2_forward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), (uint32_t)v,
+                                    Hs.data_ptr<float>(), (uint64_t)F, Hd.data_ptr<float>(),
+                                    (uint64_t)F, (uint32_t)K, (uint32_t)D, Ac.data_ptr<float>(),
+                                    u.data_ptr<float>(), a.data_ptr<float>(), Y.data_ptr<float>(),
+                                    (uint64_t)FY, mean ? 1 : 0, (float)p_attn, (float)p_out,
+                                    (uint64_t)seed, (uint64_t)off_attn, (uint64_t)off_out),
+              "nts_hip_gatv2_forward");
+    // compulsory bytes: Hs and Hd rows once, offsets, row index + score + weight
+    // per edge, att, output rows
+    if (prof)
+      prof->end(KernelProfiler::GAT_FWD, st,
+                4.0 * F * s + 4.0 * F * v + 4.0 * (v + 1) + (4.0 + 8.0 * K) * e + 4.0 * F +
+                    4.0 * FY * v);
+    ctx->save_for_backward({Xc, Xd, Ws, Wd, Ac, Hs, Hd, Y, a, idx});
+    ctx->saved_data["heads"] = K;
+    ctx->saved_data["mean"] = mean;
+    ctx->saved_data["sg"] = sg_ptr;
+    ctx->saved_data["cs"] = cs_ptr;
+    ctx->saved_data["x_grad"] = X.requires_grad();
+    ctx->saved_data["p_attn"] = p_attn;
+    ctx->saved_data["p_out"] = p_out;
+    ctx->saved_data["seed"] = seed;
+    ctx->saved_data["off_attn"] = off_attn;
+    return Y;
+  }
+  static torch::autograd::variable_list backward(AutogradContext* ctx,
+                                                 torch::autograd::variable_list grads) {
+    auto v_ = ctx->get_saved_variables();
+    NtsVar X = v_[0], Xd = v_[1], Ws = v_[2], Wd = v_[3], A = v_[4], Hs = v_[5], Hd = v_[6],
+           Y = v_[7], a = v_[8], idx = v_[9];
+    const double p_attn = ctx->saved_data["p_attn"].toDouble();
+    const double p_out = ctx->saved_data["p_out"].toDouble();
+    const uint64_t seed = (uint64_t)ctx->saved_data["seed"].toInt();
+    const uint64_t off_attn = (uint64_t)ctx->saved_data["off_attn"].toInt();
+    auto* sg = reinterpret_cast<sampCSC*>(ctx->saved_data["sg"].toInt());
+    auto* cs = reinterpret_cast<NtsStream*>(ctx->saved_data["cs"].toInt());
+    NtsVar GY = grads[0].contiguous();
+    const int64_t s = Hs.size(0), F = Hs.size(1), Fin = X.size(1), v = Y.size(0);
+    const int64_t e = sg->e_size;
+    const int64_t K = ctx->saved_data["heads"].toInt(), D = F / K;
+    const bool mean = ctx->saved_data["mean"].toBool();
+    const int64_t FY = mean ? D : F;
+    const int dev = cs->device();
+    auto guard = cs->guard();
+    NtsVar du = torch::empty({std::max<int64_t>(e, 1) * K}, f32_opts(dev));
+    NtsVar GM = torch::empty({std::max<int64_t>(v, 1), F}, f32_opts(dev));
+    NtsVar dHs = torch::empty({s, F}, f32_opts(dev));
+    NtsVar dHd = torch::empty({std::max<int64_t>(v, 1), F}, f32_opts(dev));
+    NtsVar dA = torch::empty({F}, f32_opts(dev));
+    hip_check(nts_hip_gatv2_backward(
+                  cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), (uint32_t)v, sg->dev_r_o(), sg->dev_c_i(),
+                  dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s, Hs.data_ptr<float>(), (uint64_t)F,
+                  Hd.data_ptr<float>(), (uint64_t)F, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(),
+                  a.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)FY, GY.data_ptr<float>(),
+                  (uint64_t)FY, du.data_ptr<float>(), GM.data_ptr<float>(), (uint64_t)F,
+                  dHs.data_ptr<float>(), (uint64_t)F, dHd.data_ptr<float>(), (uint64_t)F,
+                  dA.data_ptr<float>(), mean ? 1 : 0, (float)p_attn, (float)p_out, seed, off_attn),
+              "nts_hip_gatv2_backward");
+    NtsVar dWs = torch::empty({Fin, F}, f32_opts(dev));
+    NtsVar dWd = torch::zeros({Fin, F}, f32_opts(dev));
+    hip_check(nts_hip_gemm_f32(cs->ctx(), 1, (int)Fin, (int)F, (int)s, X.data_ptr<float>(),
+                               (uint64_t)X.stride(0), dHs.data_ptr<float>(), (uint64_t)F,
+                               dWs.data_ptr<float>(), (uint64_t)F),
+              "nts_hip_gemm_f32(dW_s)");
+    if (v)
+      hip_check(nts_hip_gemm_f32(cs->ctx(), 1, (int)Fin, (int)F, (int)v, Xd.data_ptr<float>(),
+                                 (uint64_t)Xd.stride(0), dHd.data_ptr<float>(), (uint64_t)F,
+                                 dWd.data_ptr<float>(), (uint64_t)F),
+                "nts_hip_gemm_f32(dW_d)");
+    NtsVar dW = torch::cat({dWs, dWd}, 1);
+    NtsVar dX;
+    if (ctx->saved_data["x_grad"].toBool()) {
+      NtsVar Wst = Ws.t().contiguous(), Wdt = Wd.t().contiguous();
+      dX = torch::empty({s, Fin}, f32_opts(dev));
+      hip_check(nts_hip_gemm_f32(cs->ctx(), 0, (int)s, (int)Fin, (int)F, dHs.data_ptr<float>(),
+                                 (uint64_t)F, Wst.data_ptr<float>(), (uint64_t)Fin,
+                                 dX.data_ptr<float>(), (uint64_t)Fin),
+                "nts_hip_gemm_f32(dX)");
+      if (v) {
+        NtsVar dXd = torch::empty({v, Fin}, f32_opts(dev));
+        hip_check(nts_hip_gemm_f32(cs->ctx(), 0, (int)v, (int)Fin, (int)F, dHd.data_ptr<float>(),
+                                   (uint64_t)F, Wdt.data_ptr<float>(), (uint64_t)Fin,
+                                   dXd.data_ptr<float>(), (uint64_t)Fin),
+                  "nts_hip_gemm_f32(dX_d)");
+        dX.index_add_(0, idx, dXd);  // injective: one addend per row
+      }
+    }
+    return {dX,       dW,       dA.view(A.sizes()), NtsVar(), NtsVar(), NtsVar(), NtsVar(),
+            NtsVar(), NtsVar(), NtsVar(),           NtsVar(), NtsVar(), NtsVar()};
+  }
+};
+
+NtsVar hip_gatv2_layer(const NtsVar& x, const NtsVar& W, const NtsVar& att, sampCSC* sg,
+                       NtsStream* cs, KernelProfiler* prof, int heads, bool mean,
+                       const GatDropout& drop) {
+  return HipGATv2LayerFn::apply(x, W, att, reinterpret_cast<int64_t>(sg),
+                                reinterpret_cast<int64_t>(cs), reinterpret_cast<int64_t>(prof),
+                                (int64_t)heads, mean, drop.p_attn, drop.p_out, (int64_t)drop.seed,
+                                (int64_t)drop.off_attn, (int64_t)drop.off_out);
+}
+
 NtsVar hip_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offset, NtsStream* cs) {
   NtsVar xc = row_major(x);
   NtsVar y = torch::empty({xc.size(0), xc.size(1)}, xc.options());

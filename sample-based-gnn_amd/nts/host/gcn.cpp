@@ -82,6 +82,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                   "multiple of 4, else 256)");
     }
   }
+  TORCH_CHECK(!cfg.gat_v2 || cfg.gat, "gat_v2 is not supported without gat (attention layers only)");
   if (cfg.layer_norm) {
     TORCH_CHECK(!cfg.gat, "layer_norm is not supported with gat (GCN / GraphSAGE layers only)");
     TORCH_CHECK(!cfg.pd_cache, "layer_norm is not supported with pd_cache");
@@ -370,13 +371,14 @@ void GCN_SAMPLE_ALLGPU_impl::init_nn() {
   for (size_t i = 0; i + 1 < cfg.layer_size.size(); ++i) {
     // root_weight: the stacked [W_n; W_s]
     // gat_heads: the last layer's K heads of layer_size.back() columns each
+    // gat_v2: the stacked [W_s | W_d] and the score vector att [F_{l+1}, 1]
     const int64_t out = gat_width((int)i);
-    P.push_back(new Parameter((cfg.root_weight ? 2 : 1) * cfg.layer_size[i], out,
-                              cfg.learn_rate, cfg.beta1,
+    P.push_back(new Parameter((cfg.root_weight ? 2 : 1) * cfg.layer_size[i],
+                              (cfg.gat_v2 ? 2 : 1) * out, cfg.learn_rate, cfg.beta1,
                               cfg.beta2, cfg.epsilon, cfg.weight_decay, graph->device,
                               cfg.seed + (int64_t)i));
     if (cfg.gat)  // attention vector W_att [2 F_{l+1}, 1] (GAT_SAMPLE_ALL_GPU.hpp:141-147)
-      P.push_back(new Parameter(2 * out, 1, cfg.learn_rate, cfg.beta1,
+      P.push_back(new Parameter((cfg.gat_v2 ? 1 : 2) * out, 1, cfg.learn_rate, cfg.beta1,
                                 cfg.beta2, cfg.epsilon, cfg.weight_decay, graph->device,
                                 cfg.seed + 1000 + (int64_t)i));
   }
@@ -589,8 +591,9 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward_gat(SampledSubgraph* sg) {
       drop.p_out = p;
       drop.off_out = dropout_calls_++;
     }
-    X = hip_gat_layer(X, P[2 * l]->W, P[2 * l + 1]->W, sg->sampled_sgs[hop], cs.get(),
-                      profiler(), gat_heads(l), l == L - 1 && gat_heads(l) > 1, drop);
+    const auto layer = cfg.gat_v2 ? hip_gatv2_layer : hip_gat_layer;
+    X = layer(X, P[2 * l]->W, P[2 * l + 1]->W, sg->sampled_sgs[hop], cs.get(), profiler(),
+              gat_heads(l), l == L - 1 && gat_heads(l) > 1, drop);
     acts.push_back(X);
   }
   return acts;
@@ -1098,6 +1101,8 @@ double GCN_SAMPLE_ALLGPU_impl::evaluate_full(const std::vector<VertexId>& nids) 
 NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full_gat() {
   TORCH_CHECK(cfg.gat, "infer_full_gat: attention layers only; a GCN / GraphSAGE driver has "
                        "infer_full() / evaluate_full()");
+  TORCH_CHECK(!cfg.gat_v2, "infer_full_gat: full-neighbour inference for GATv2 (gat_v2) is not "
+                           "built; use evaluate() on sampled neighbourhoods");
   TORCH_CHECK(!fcache, "infer_full_gat: needs the whole feature table in HBM (cache_rate < 0)");
   flush_update();
   auto guard = cs->guard();

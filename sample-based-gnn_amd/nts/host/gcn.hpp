@@ -28,6 +28,15 @@ struct GCNConfig {
   // is [F_in, K C] and its W_att [2 K C, 1].  Every layer's K D must be within
   // the kernels' width limit (1024 when D % 4 == 0, else 256).
   std::vector<int> gat_heads;
+  // GATv2 attention (gat only; no reference counterpart; Brody et al., ICLR
+  // 2022): every layer scores an edge with
+  //   att_h . leaky_relu(W_s x_src + W_d x_dst, 0.2)_h
+  // instead of GAT's leaky_relu(a1 . W x_src + a2 . W x_dst), so the ranking of
+  // a destination's neighbours depends on the destination.  P[2l] is then the
+  // stacked [F_in, 2 gat_width(l)] = [W_s | W_d] and P[2l+1] the score vector
+  // [gat_width(l), 1]; gat_heads, gat_attn_drop and gat_feat_drop keep their
+  // meaning.  infer_full_gat() / evaluate_full_gat() are not built for it.
+  bool gat_v2 = false;
   // GAT dropout (gat only, training mode only; no reference counterpart: the
   // reference's GAT stores drop_rate and never uses it, and drop_rate stays
   // ignored by a GAT driver).  gat_attn_drop: the normalised attention

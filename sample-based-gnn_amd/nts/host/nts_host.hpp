@@ -469,6 +469,14 @@ struct GatDropout {
 NtsVar hip_gat_layer(const NtsVar& x, const NtsVar& W, const NtsVar& Watt, sampCSC* sg,
                      NtsStream* cs, KernelProfiler* prof = nullptr, int heads = 1,
                      bool mean = false, const GatDropout& drop = GatDropout());
+// one GATv2 layer: W [F_in, 2F] = [W_s | W_d] stacked, att [F, 1];
+// Hs = X W_s over the source rows, Hd = X[dst_local_id] W_d over the
+// destination rows, score att_h . leaky_relu(Hs[src] + Hd[dst])_h per head,
+// softmax over each dst's sampled edges, relu(sum a Hs[src]).  heads, mean and
+// GatDropout as hip_gat_layer.
+NtsVar hip_gatv2_layer(const NtsVar& x, const NtsVar& W, const NtsVar& att, sampCSC* sg,
+                       NtsStream* cs, KernelProfiler* prof = nullptr, int heads = 1,
+                       bool mean = false, const GatDropout& drop = GatDropout());
 // plain inverted dropout with the shared keep bits (nts_hip_dropout_f32), no
 // backward: the input pass of gat_feat_drop over untrained features
 NtsVar hip_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offset, NtsStream* cs);

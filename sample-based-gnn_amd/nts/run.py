@@ -119,6 +119,12 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.gat_heads and model != "gat":
         raise SystemExit(f"ALGORITHM {info.algorithm}: GAT_HEADS is not supported with GCN / "
                          "GraphSAGE algorithms (GAT only)")
+    if info.gat_v2 and model != "gat":
+        raise SystemExit(f"ALGORITHM {info.algorithm}: GAT_V2 is not supported with GCN / "
+                         "GraphSAGE algorithms (GAT only)")
+    if info.gat_v2 and info.full_inference:
+        raise SystemExit(f"ALGORITHM {info.algorithm}: FULL_INFERENCE is not supported with GAT_V2 "
+                         "(full-neighbour inference for GATv2 is not built)")
     for key, rate in (("GAT_ATTN_DROP", info.gat_attn_drop), ("GAT_FEAT_DROP", info.gat_feat_drop)):
         if rate and model != "gat":
             raise SystemExit(f"ALGORITHM {info.algorithm}: {key} is not supported with GCN / "
@@ -146,7 +152,7 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         multi_label=bool(info.multi_label), root_weight=bool(info.root_weight),
         aggregator=info.aggregator, gat_heads=info.gat_heads or None,
         layer_norm=bool(info.layer_norm), gat_attn_drop=info.gat_attn_drop,
-        gat_feat_drop=info.gat_feat_drop)
+        gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2))
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
