@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd(
 #pragma unroll
       for (int u = 0; u < kGatU; ++u) {
         const bool ok = j0 + u < ne;
-        const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+        const uint32_t r = chunk_get(my_r, j0 + u, ne);
         const T* hr = reinterpret_cast<const T*>(H + (uint64_t)r * ldh);
         p1[u] = 0.f;
 #pragma unroll
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst(
 #pragma unroll
       for (int u = 0; u < kGatU; ++u) {
         const bool ok = j0 + u < ne;
-        const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+        const uint32_t r = chunk_get(my_r, j0 + u, ne);
         const T* hr = reinterpret_cast<const T*>(H + (uint64_t)r * ldh);
         p[u] = 0.f;
 #pragma unroll
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src(
       for (int u = 0; u < kGatU; ++u) {
         const bool ok = j0 + u < ne;
         const int jj = (int)min(j0 + u, ne - 1);
-        const uint32_t dd = (uint32_t)__shfl((int)my_d, jj, 64);
+        const uint32_t dd = chunk_get(my_d, j0 + u, ne);
         w[u] = ok ? __shfl(my_a, jj, 64) : 0.f;
         const T* gm = reinterpret_cast<const T*>(GM + (uint64_t)dd * ldm);
 #pragma unroll
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_dst_heads(
 #pragma unroll
       for (int u = 0; u < kGatU; ++u) {
         const bool ok = j0 + u < ne;
-        const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+        const uint32_t r = chunk_get(my_r, j0 + u, ne);
         const T* hr = reinterpret_cast<const T*>(H + (uint64_t)r * ldh);
         const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
 #pragma unroll
@@ -582,8 +582,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_src_heads(
       for (int u = 0; u < kGatU; ++u) {
         const bool ok = j0 + u < ne;
         const int jj = (int)min(j0 + u, ne - 1);
-        const uint32_t dd = (uint32_t)__shfl((int)my_d, jj, 64);
-        const uint64_t eb = (uint64_t)(uint32_t)__shfl((int)my_e, jj, 64) * heads;
+        const uint32_t dd = chunk_get(my_d, j0 + u, ne);
+        const uint64_t eb = (uint64_t)chunk_get(my_e, j0 + u, ne) * heads;
         const T* gm = reinterpret_cast<const T*>(GM + (uint64_t)dd * ldm);
         [[maybe_unused]] uint64_t kj[NCH];
         if constexpr (DROP) keep_bits_from<NCH>(kj, kb, jj, heads);
@@ -664,34 +664,10 @@ static const char kGatWidthMsg[] =
     "feature width too large (F <= 1024 on 16-byte aligned rows with pitches that are "
     "multiples of 4, F <= 256 otherwise)";
 
+// ---- entry points: checks and dispatch ---------------------------------------------
 // The plain and the _drop entry points share one checked implementation each:
 // `fn` is the entry point's name for the error text, `dr` its dropout (none, or
 // both rates 0: the plain kernels, the same launches as without the options).
-#define NTS_GAT_DISPATCH(KERNEL, ARGS, TAIL)                                             \
-  do {                                                                                   \
-    const uint32_t nvec = v4 ? F / 4 : F;                                                \
-    const int nch = (int)((nvec + 63) / 64);                                             \
-    GAT_CHECK(nch <= 4, kGatWidthMsg);                                                   \
-    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));                        \
-    if (v4) {                                                                            \
-      switch (nch) {                                                                     \
-        case 1: hipLaunchKernelGGL((KERNEL<4, 1 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<4, 2 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<4, 3 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        default: hipLaunchKernelGGL((KERNEL<4, 4 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-      }                                                                                  \
-    } else {                                                                             \
-      switch (nch) {                                                                     \
-        case 1: hipLaunchKernelGGL((KERNEL<1, 1 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 2: hipLaunchKernelGGL((KERNEL<1, 2 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        case 3: hipLaunchKernelGGL((KERNEL<1, 3 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-        default: hipLaunchKernelGGL((KERNEL<1, 4 TAIL>), grid, dim3(kGatThreads), 0, st, ARGS); break; \
-      }                                                                                  \
-    }                                                                                    \
-    NTS_LAUNCH_CHECK();                                                                  \
-  } while (0)
-
-// ---- multi-head entry points: checks and dispatch ---------------------------------
 namespace {
 
 int gat_forward_heads_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -701,36 +677,20 @@ int gat_forward_heads_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* col
                            uint64_t ldy, int mean, const GatDrop* dr) {
   GAT_CHECK(ctx && column_offset && row_indices && dst_local_id && H && att && m_out && a_out && Y,
             "NULL argument");
-  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
-  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  NTS_RET(gat_heads_check(fn, heads, D));
   const uint32_t F = heads * D, FY = mean ? D : F;
   GAT_CHECK(ldh >= F && ldy >= FY, "leading dimension");
-  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att);
-  const HeadsShape hs = heads_shape(heads, D, v4);
-  GAT_CHECK(hs.nch <= 4, kGatHeadsWidthMsg);
+  const bool v4 = gat_vec4(D, {{H, ldh}, {Y, ldy}, {att, 0}});
+  HeadsShape hs;
+  NTS_RET(gat_heads_shape(fn, heads, D, v4, &hs));
   if (v_size == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const uint32_t n = v_size;
-  // mean mode: one row of nch * 64 vectors per wave (16 KiB a block at VEC 4, NCH 4)
-  const size_t lds = mean ? (size_t)(kGatThreads / 64) * hs.nch * 64 * (v4 ? 16 : 4) : 0;
-#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, att, \
-             m_out, a_out, Y, ldy, mean
-  if (!dr) {
-#define ARGS BASE
-#define GAT_T
-    NTS_GAT_HEADS_DISPATCH(k_gat_fwd_heads);
-#undef GAT_T
-#undef ARGS
-  } else {
-#define ARGS BASE, *dr
-#define GAT_T GAT_T_DROP
-    NTS_GAT_HEADS_DISPATCH(k_gat_fwd_heads);
-#undef GAT_T
-#undef ARGS
-  }
-#undef BASE
-  return NTS_OK;
+  return gat_dispatch(v4, hs.nch, hs.mode, [&](auto V, auto N, auto M) {
+    return gat_launch(k_gat_fwd_heads<V(), N(), M()>, k_gat_fwd_heads<V(), N(), M(), true, GatDrop>,
+                      gat_grid(v_size), gat_mean_lds(mean, hs.nch, v4), ctx->stream, dr,
+                      column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads,
+                      att, m_out, a_out, Y, ldy, mean);
+  });
 }
 
 int gat_backward_heads_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -745,70 +705,33 @@ int gat_backward_heads_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* co
   GAT_CHECK(ctx && column_offset && row_indices && dst_local_id && row_offset && column_indices &&
                 csr_edge_id && H && att && a && m && Y && GY && du && ds2 && GM && dH && dS,
             "NULL argument");
-  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
-  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  NTS_RET(gat_heads_check(fn, heads, D));
   const uint32_t F = heads * D, FY = mean ? D : F;
   GAT_CHECK(ldm >= F, "leading dimension of GM");
   GAT_CHECK(ldh >= F && ldy >= FY && ldg >= FY && lddh >= F, "leading dimension");
-  const bool v4 = D % 4 == 0 && gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 &&
-                  lddh % 4 == 0 && ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 &&
-                  ((uintptr_t)dH % 16) == 0 && ((uintptr_t)GM % 16) == 0;
-  const HeadsShape hs = heads_shape(heads, D, v4);
+  const bool v4 =
+      gat_vec4(D, {{H, ldh}, {Y, ldy}, {att, 0}, {GY, ldg}, {dH, lddh}, {GM, ldm}});
   // a refused shape leaves every output as it was: checked before ds2 is cleared
-  GAT_CHECK(hs.nch <= 4, kGatHeadsWidthMsg);
+  HeadsShape hs;
+  NTS_RET(gat_heads_shape(fn, heads, D, v4, &hs));
   NTS_HIP_TRY(hipSetDevice(ctx->device));
   const hipStream_t st = ctx->stream;
-  const size_t lds = 0;  // the backward kernels use no LDS
   if (src_size)
     NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * heads * sizeof(float), st));
-  if (v_size) {
-    const uint32_t n = v_size;
-#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g, heads, a, m, \
-             Y, ldy, GY, ldg, du, ds2, GM, ldm, mean
-    if (!dr) {
-#define ARGS BASE
-#define GAT_T
-      NTS_GAT_HEADS_DISPATCH(k_gat_bwd_dst_heads);
-#undef GAT_T
-#undef ARGS
-    } else {
-#define ARGS BASE, *dr
-#define GAT_T GAT_T_DROP
-      NTS_GAT_HEADS_DISPATCH(k_gat_bwd_dst_heads);
-#undef GAT_T
-#undef ARGS
-    }
-#undef BASE
-  }
-  if (src_size) {
-    const uint32_t n = src_size;
-    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));
-#define BASE row_offset, column_indices, csr_edge_id, src_size, hs.nvec, hs.g, heads, a, du, ds2, \
-             att, GM, ldm, dH, lddh, dS
-    if (!dr) {
-#define ARGS BASE
-#define GAT_T
-      if (v4) {
-        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 4, 0)
-      } else {
-        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 1, 0)
-      }
-#undef GAT_T
-#undef ARGS
-    } else {
-#define ARGS BASE, *dr
-#define GAT_T GAT_T_DROP
-      if (v4) {
-        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 4, 0)
-      } else {
-        NTS_GAT_HEADS_NCH(k_gat_bwd_src_heads, 1, 0)
-      }
-#undef GAT_T
-#undef ARGS
-    }
-#undef BASE
-    NTS_LAUNCH_CHECK();
-  }
+  if (v_size)
+    NTS_RET(gat_dispatch(v4, hs.nch, hs.mode, [&](auto V, auto N, auto M) {
+      return gat_launch(k_gat_bwd_dst_heads<V(), N(), M()>,
+                        k_gat_bwd_dst_heads<V(), N(), M(), true, GatDrop>, gat_grid(v_size), 0, st,
+                        dr, column_offset, row_indices, dst_local_id, v_size, H, ldh, hs.nvec, hs.g,
+                        heads, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm, mean);
+    }));
+  if (src_size)
+    NTS_RET(gat_dispatch(v4, hs.nch, [&](auto V, auto N) {
+      return gat_launch(k_gat_bwd_src_heads<V(), N(), 0>,
+                        k_gat_bwd_src_heads<V(), N(), 0, true, GatDrop>, gat_grid(src_size), 0, st,
+                        dr, row_offset, column_indices, csr_edge_id, src_size, hs.nvec, hs.g, heads,
+                        a, du, ds2, att, GM, ldm, dH, lddh, dS);
+    }));
   return NTS_OK;
 }
 
@@ -821,18 +744,15 @@ int gat_forward_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_of
   GAT_CHECK(ldh >= F && ldy >= F, "leading dimension");
   if (v_size == 0 || F == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att);
-  const uint32_t n = v_size;
-#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, att, m_out, a_out, Y, ldy
-#define ARGS BASE
-#define ARGS_DROP BASE, *dr
-  if (!dr)
-    NTS_GAT_DISPATCH(k_gat_fwd, ARGS, GAT_T_NONE);
-  else
-    NTS_GAT_DISPATCH(k_gat_fwd, ARGS_DROP, GAT_T_DROP);
-#undef BASE
-  return NTS_OK;
+  const bool v4 = gat_vec4(F, {{H, ldh}, {Y, ldy}, {att, 0}});
+  const uint32_t nvec = v4 ? F / 4 : F;
+  const int nch = (int)((nvec + 63) / 64);
+  GAT_CHECK(nch <= 4, kGatWidthMsg);
+  return gat_dispatch(v4, nch, [&](auto V, auto N) {
+    return gat_launch(k_gat_fwd<V(), N()>, k_gat_fwd<V(), N(), true, GatDrop>, gat_grid(v_size), 0,
+                      ctx->stream, dr, column_offset, row_indices, dst_local_id, v_size, H, ldh,
+                      nvec, att, m_out, a_out, Y, ldy);
+  });
 }
 
 int gat_backward_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -850,32 +770,25 @@ int gat_backward_impl(const char* fn, nts_hip_ctx* ctx, const uint32_t* column_o
   if (F == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
   const hipStream_t st = ctx->stream;
-  const bool v4 = gat_vec4(F, ldh, ldy, H, Y, att) && ldg % 4 == 0 && lddh % 4 == 0 &&
-                  ldm % 4 == 0 && ((uintptr_t)GY % 16) == 0 && ((uintptr_t)dH % 16) == 0 &&
-                  ((uintptr_t)GM % 16) == 0;
+  const bool v4 =
+      gat_vec4(F, {{H, ldh}, {Y, ldy}, {att, 0}, {GY, ldg}, {dH, lddh}, {GM, ldm}});
+  const uint32_t nvec = v4 ? F / 4 : F;
+  const int nch = (int)((nvec + 63) / 64);
   // a refused width leaves every output as it was: checked before ds2 is cleared
-  GAT_CHECK((v4 ? F / 4 : F) <= 256, kGatWidthMsg);
+  GAT_CHECK(nvec <= 256, kGatWidthMsg);
   if (src_size) NTS_HIP_TRY(hipMemsetAsync(ds2, 0, (size_t)src_size * sizeof(float), st));
-  if (v_size) {
-    const uint32_t n = v_size;
-#define BASE column_offset, row_indices, dst_local_id, v_size, H, ldh, nvec, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm
-    if (!dr)
-      NTS_GAT_DISPATCH(k_gat_bwd_dst, ARGS, GAT_T_NONE);
-    else
-      NTS_GAT_DISPATCH(k_gat_bwd_dst, ARGS_DROP, GAT_T_DROP);
-#undef BASE
-  }
-  if (src_size) {
-    const uint32_t n = src_size;
-#define BASE row_offset, column_indices, csr_edge_id, src_size, nvec, a, du, ds2, att, GM, ldm, dH, lddh, dS
-    if (!dr)
-      NTS_GAT_DISPATCH(k_gat_bwd_src, ARGS, GAT_T_NONE);
-    else
-      NTS_GAT_DISPATCH(k_gat_bwd_src, ARGS_DROP, GAT_T_DROP);
-#undef BASE
-  }
-#undef ARGS
-#undef ARGS_DROP
+  if (v_size)
+    NTS_RET(gat_dispatch(v4, nch, [&](auto V, auto N) {
+      return gat_launch(k_gat_bwd_dst<V(), N()>, k_gat_bwd_dst<V(), N(), true, GatDrop>,
+                        gat_grid(v_size), 0, st, dr, column_offset, row_indices, dst_local_id,
+                        v_size, H, ldh, nvec, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm);
+    }));
+  if (src_size)
+    NTS_RET(gat_dispatch(v4, nch, [&](auto V, auto N) {
+      return gat_launch(k_gat_bwd_src<V(), N()>, k_gat_bwd_src<V(), N(), true, GatDrop>,
+                        gat_grid(src_size), 0, st, dr, row_offset, column_indices, csr_edge_id,
+                        src_size, nvec, a, du, ds2, att, GM, ldm, dH, lddh, dS);
+    }));
   return NTS_OK;
 }
 
@@ -898,12 +811,10 @@ int nts_hip_gat_forward_heads_drop(nts_hip_ctx* ctx, const uint32_t* column_offs
                                    uint32_t D, const float* att, float* m_out, float* a_out,
                                    float* Y, uint64_t ldy, int mean, float p_attn, float p_out,
                                    uint64_t seed, uint64_t off_attn, uint64_t off_out) {
-  const char* fn = __func__;
-  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
-  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, off_out);
-  return gat_forward_heads_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size, H, ldh,
-                                heads, D, att, m_out, a_out, Y, ldy, mean,
-                                p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
+  std::optional<GatDrop> dr;
+  NTS_RET(gat_drop(__func__, p_attn, p_out, seed, off_attn, off_out, &dr));
+  return gat_forward_heads_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size, H,
+                                ldh, heads, D, att, m_out, a_out, Y, ldy, mean, gat_drop_ptr(dr));
 }
 
 int nts_hip_gat_backward_heads(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -931,13 +842,12 @@ int nts_hip_gat_backward_heads_drop(nts_hip_ctx* ctx, const uint32_t* column_off
                                     float* du, float* ds2, float* GM, uint64_t ldm, float* dH,
                                     uint64_t lddh, float* dS, int mean, float p_attn, float p_out,
                                     uint64_t seed, uint64_t off_attn) {
-  const char* fn = __func__;
-  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
-  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, 0);
-  return gat_backward_heads_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size,
+  std::optional<GatDrop> dr;
+  NTS_RET(gat_drop(__func__, p_attn, p_out, seed, off_attn, 0, &dr));
+  return gat_backward_heads_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size,
                                  row_offset, column_indices, csr_edge_id, src_size, H, ldh, heads, D,
                                  att, a, m, Y, ldy, GY, ldg, du, ds2, GM, ldm, dH, lddh, dS, mean,
-                                 p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
+                                 gat_drop_ptr(dr));
 }
 
 int nts_hip_gat_forward(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -954,11 +864,10 @@ int nts_hip_gat_forward_drop(nts_hip_ctx* ctx, const uint32_t* column_offset,
                              const float* att, float* m_out, float* a_out, float* Y, uint64_t ldy,
                              float p_attn, float p_out, uint64_t seed, uint64_t off_attn,
                              uint64_t off_out) {
-  const char* fn = __func__;
-  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
-  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, off_out);
-  return gat_forward_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size, H, ldh, F, att,
-                          m_out, a_out, Y, ldy, p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
+  std::optional<GatDrop> dr;
+  NTS_RET(gat_drop(__func__, p_attn, p_out, seed, off_attn, off_out, &dr));
+  return gat_forward_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size, H, ldh, F,
+                          att, m_out, a_out, Y, ldy, gat_drop_ptr(dr));
 }
 
 int nts_hip_gat_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -983,13 +892,11 @@ int nts_hip_gat_backward_drop(nts_hip_ctx* ctx, const uint32_t* column_offset,
                               uint64_t ldy, const float* GY, uint64_t ldg, float* du, float* ds2,
                               float* GM, uint64_t ldm, float* dH, uint64_t lddh, float* dS,
                               float p_attn, float p_out, uint64_t seed, uint64_t off_attn) {
-  const char* fn = __func__;
-  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
-  const GatDrop dr = gat_drop(p_attn, p_out, seed, off_attn, 0);
-  return gat_backward_impl(fn, ctx, column_offset, row_indices, dst_local_id, v_size, row_offset,
-                           column_indices, csr_edge_id, src_size, H, ldh, F, att, a, m, Y, ldy, GY,
-                           ldg, du, ds2, GM, ldm, dH, lddh, dS,
-                           p_attn > 0.f || p_out > 0.f ? &dr : nullptr);
+  std::optional<GatDrop> dr;
+  NTS_RET(gat_drop(__func__, p_attn, p_out, seed, off_attn, 0, &dr));
+  return gat_backward_impl(__func__, ctx, column_offset, row_indices, dst_local_id, v_size,
+                           row_offset, column_indices, csr_edge_id, src_size, H, ldh, F, att, a, m, Y,
+                           ldy, GY, ldg, du, ds2, GM, ldm, dH, lddh, dS, gat_drop_ptr(dr));
 }
 
 int nts_hip_dropout_f32(nts_hip_ctx* ctx, uint32_t rows, uint32_t feature_size, const float* x,

@@ -1,7 +1,12 @@
 // Helpers shared by the attention kernels (gat.hip, gatv2.hip): the vector
 // types, the dropout keep bits, the segmented per-head wave
-// reductions (§8i) and the host-side shape / rate checks and dispatch macros.
+// reductions (§8i) and the host side of the entry points: the shape / rate
+// checks, the float4 rule, the typed kernel dispatch and the launch.
 #pragma once
+#include <initializer_list>
+#include <optional>
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace nts_hip {
@@ -205,12 +210,13 @@ __device__ __forceinline__ void head_sums(float (&p)[U][NCH], const uint32_t (&h
   }
 }
 
-[[maybe_unused]] static bool gat_vec4(uint32_t F, uint64_t l1, uint64_t l2, const void* p1, const void* p2,
-                     const void* att) {
-  return F % 4 == 0 && l1 % 4 == 0 && l2 % 4 == 0 && ((uintptr_t)p1 % 16) == 0 &&
-         ((uintptr_t)p2 % 16) == 0 && ((uintptr_t)att % 16) == 0;
+// What lane j of a chunk of ne edges holds (a row index, an edge id), in every
+// lane; past the chunk's end the last lane's, a valid index the caller masks.
+__device__ __forceinline__ uint32_t chunk_get(uint32_t mine, uint32_t j, uint32_t ne) {
+  return (uint32_t)__shfl((int)mine, (int)min(j, ne - 1), 64);
 }
 
+// ---- host side: checks, shapes and dispatch of the entry points -------------------
 // argument check of an entry point: `fn` (in scope) is its name for the error text
 #define GAT_CHECK(cond, msg)                                                \
   do {                                                                      \
@@ -222,38 +228,52 @@ __device__ __forceinline__ void head_sums(float (&p)[U][NCH], const uint32_t (&h
 
 static const char kGatRateMsg[] = "dropout probability must be in [0, 1]";
 
-namespace {
-bool gat_rate_ok(float p) { return p >= 0.f && p <= 1.f; }  // (a NaN fails both)
-GatDrop gat_drop(float p_attn, float p_out, uint64_t seed, uint64_t off_attn, uint64_t off_out) {
-  GatDrop dr;
-  dr.thr_attn = dropout_threshold(p_attn);
-  dr.thr_out = dropout_threshold(p_out);
-  dr.scale_attn = p_attn >= 1.f ? 0.f : 1.0f / (1.0f - p_attn);
-  dr.scale_out = p_out >= 1.f ? 0.f : 1.0f / (1.0f - p_out);
-  dr.seed = seed;
-  dr.off_attn = off_attn;
-  dr.off_out = off_out;
-  return dr;
-}
-}  // namespace
+inline bool gat_rate_ok(float p) { return p >= 0.f && p <= 1.f; }  // (a NaN fails both)
 
-// The tail of a kernel's template arguments: none for the plain kernel,
-// GAT_T_DROP with `*dr` as the last argument.  The single-head dispatch takes
-// it as TAIL, the multi-head macros read GAT_T where they are used.
-#define GAT_T_NONE
-#define GAT_T_DROP , true, GatDrop
+// The dropout of an entry point `fn`: refused unless both rates are in [0, 1],
+// empty when both are 0 (the plain kernels, the same launches as without the
+// options).
+inline int gat_drop(const char* fn, float p_attn, float p_out, uint64_t seed, uint64_t off_attn,
+                    uint64_t off_out, std::optional<GatDrop>* out) {
+  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
+  if (p_attn > 0.f || p_out > 0.f) {
+    GatDrop dr;
+    dr.thr_attn = dropout_threshold(p_attn);
+    dr.thr_out = dropout_threshold(p_out);
+    dr.scale_attn = p_attn >= 1.f ? 0.f : 1.0f / (1.0f - p_attn);
+    dr.scale_out = p_out >= 1.f ? 0.f : 1.0f / (1.0f - p_out);
+    dr.seed = seed;
+    dr.off_attn = off_attn;
+    dr.off_out = off_out;
+    *out = dr;
+  }
+  return NTS_OK;
+}
+inline const GatDrop* gat_drop_ptr(const std::optional<GatDrop>& dr) { return dr ? &*dr : nullptr; }
+
+// The float4 path: the per-head (or single-head) width a multiple of 4 and
+// every operand on a 16-byte base with a pitch (in floats; 0: one row) that is a
+// multiple of 4.
+struct GatOperand {
+  const void* p;
+  uint64_t ld;
+};
+inline bool gat_vec4(uint32_t D, std::initializer_list<GatOperand> ops) {
+  bool ok = D % 4 == 0;
+  for (const GatOperand& o : ops) ok = ok && o.ld % 4 == 0 && ((uintptr_t)o.p % 16) == 0;
+  return ok;
+}
 
 static const char kGatHeadsWidthMsg[] =
     "feature width too large (F = heads * D <= 1024 on 16-byte aligned rows with pitches that "
     "are multiples of 4 and D a multiple of 4, F <= 256 otherwise)";
 
-namespace {
 struct HeadsShape {
   uint32_t nvec, g;
   int nch, mode;
 };
 // the shape of a (heads, D) layer on the float4 (v4) or the scalar path
-HeadsShape heads_shape(uint32_t heads, uint32_t D, bool v4) {
+inline HeadsShape heads_shape(uint32_t heads, uint32_t D, bool v4) {
   HeadsShape s;
   s.g = v4 ? D / 4 : D;
   s.nvec = heads * s.g;
@@ -263,31 +283,71 @@ HeadsShape heads_shape(uint32_t heads, uint32_t D, bool v4) {
                                                 : kHeadsAny;
   return s;
 }
-}  // namespace
 
-#define NTS_GAT_HEADS_NCH(KERNEL, V, ...)                                                       \
-  switch (hs.nch) {                                                                             \
-    case 1: hipLaunchKernelGGL((KERNEL<V, 1, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-    case 2: hipLaunchKernelGGL((KERNEL<V, 2, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-    case 3: hipLaunchKernelGGL((KERNEL<V, 3, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-    default: hipLaunchKernelGGL((KERNEL<V, 4, __VA_ARGS__ GAT_T>), grid, dim3(kGatThreads), lds, st, ARGS); break; \
-  }
-#define NTS_GAT_HEADS_MODE(KERNEL, V)                                     \
-  switch (hs.mode) {                                                      \
-    case kHeadsPow2: NTS_GAT_HEADS_NCH(KERNEL, V, kHeadsPow2) break;      \
-    case kHeadsChunk: NTS_GAT_HEADS_NCH(KERNEL, V, kHeadsChunk) break;    \
-    default: NTS_GAT_HEADS_NCH(KERNEL, V, kHeadsAny) break;               \
-  }
-// KERNEL<VEC, NCH, MODE> over n waves (hs, v4, st, lds and ARGS in scope)
-#define NTS_GAT_HEADS_DISPATCH(KERNEL)                                    \
-  do {                                                                    \
-    const dim3 grid(std::max(1u, ceil_div(n, kGatThreads / 64)));         \
-    if (v4) {                                                             \
-      NTS_GAT_HEADS_MODE(KERNEL, 4)                                       \
-    } else {                                                              \
-      NTS_GAT_HEADS_MODE(KERNEL, 1)                                       \
-    }                                                                     \
-    NTS_LAUNCH_CHECK();                                                   \
-  } while (0)
+// the checks every multi-head entry point `fn` starts with, and its shape once
+// the path is known (at most 4 vectors per lane)
+inline int gat_heads_check(const char* fn, uint32_t heads, uint32_t D) {
+  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
+  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  return NTS_OK;
+}
+inline int gat_heads_shape(const char* fn, uint32_t heads, uint32_t D, bool v4, HeadsShape* hs) {
+  *hs = heads_shape(heads, D, v4);
+  GAT_CHECK(hs->nch <= 4, kGatHeadsWidthMsg);
+  return NTS_OK;
+}
+
+// one wave per row, kGatThreads / 64 rows a block
+inline dim3 gat_grid(uint32_t rows) { return dim3(std::max(1u, ceil_div(rows, kGatThreads / 64))); }
+// mean mode of the multi-head forward: one row of nch * 64 vectors per wave
+// (16 KiB a block at VEC 4, NCH 4); none in concat mode
+inline size_t gat_mean_lds(int mean, int nch, bool v4) {
+  return mean ? (size_t)(kGatThreads / 64) * nch * 64 * (v4 ? 16 : 4) : 0;
+}
+
+// The run-time (v4, nch[, mode]) as compile-time constants: f(V, N[, M]) is
+// called with std::integral_constants, so a generic lambda can name
+// KERNEL<V(), N(), M()>; its status is returned.  nch is 1 ... 4 (checked by
+// the caller), mode one of kHeads*.
+template <int I>
+using GatInt = std::integral_constant<int, I>;
+
+template <class F>
+int gat_dispatch(bool v4, int nch, F&& f) {
+  auto chunks = [&](auto V) {
+    switch (nch) {
+      case 1: return f(V, GatInt<1>());
+      case 2: return f(V, GatInt<2>());
+      case 3: return f(V, GatInt<3>());
+      default: return f(V, GatInt<4>());
+    }
+  };
+  return v4 ? chunks(GatInt<4>()) : chunks(GatInt<1>());
+}
+template <class F>
+int gat_dispatch(bool v4, int nch, int mode, F&& f) {
+  return gat_dispatch(v4, nch, [&](auto V, auto N) {
+    switch (mode) {
+      case kHeadsPow2: return f(V, N, GatInt<kHeadsPow2>());
+      case kHeadsChunk: return f(V, N, GatInt<kHeadsChunk>());
+      default: return f(V, N, GatInt<kHeadsAny>());
+    }
+  });
+}
+
+// One launch of kGatThreads-wide blocks and its check: the plain kernel, or
+// with a dropout its <..., true, GatDrop> form, which takes *dr last.  The
+// kernels' trailing pack DR is what lets k<V, N> (DR empty) and
+// k<V, N, true, GatDrop> deduce P... here.
+template <class... P, class... A>
+int gat_launch(void (*plain)(P...), void (*drop)(P..., GatDrop), dim3 grid, size_t lds,
+               hipStream_t st, const GatDrop* dr, A... args) {
+  if (!dr)
+    hipLaunchKernelGGL(plain, grid, dim3(kGatThreads), lds, st, args...);
+  else
+    hipLaunchKernelGGL(drop, grid, dim3(kGatThreads), lds, st, args..., *dr);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
 
 }  // namespace nts_hip

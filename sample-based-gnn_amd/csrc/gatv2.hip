@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gatv2_fwd(
 #pragma unroll
       for (int u = 0; u < kGatU; ++u) {
         const bool ok = j0 + u < ne;
-        const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+        const uint32_t r = chunk_get(my_r, j0 + u, ne);
         const T* hr = reinterpret_cast<const T*>(Hs + (uint64_t)r * ldhs);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gatv2_bwd_dst(
 #pragma unroll
           for (int u = 0; u < kGatU; ++u) {
             const bool ok = j0 + u < ne;
-            const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+            const uint32_t r = chunk_get(my_r, j0 + u, ne);
             const T* hr = reinterpret_cast<const T*>(Hs + (uint64_t)r * ldhs);
             const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
 #pragma unroll
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gatv2_bwd_dst(
 #pragma unroll
         for (int u = 0; u < kV2U; ++u) {
           const bool ok = j0 + u < ne;
-          const uint32_t r = (uint32_t)__shfl((int)my_r, (int)min(j0 + u, ne - 1), 64);
+          const uint32_t r = chunk_get(my_r, j0 + u, ne);
           const T* hr = reinterpret_cast<const T*>(Hs + (uint64_t)r * ldhs);
           const uint64_t eb = (uint64_t)(cb + j0 + u) * heads;
 #pragma unroll
@@ -424,8 +424,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gatv2_bwd_src(
       for (int u = 0; u < kV2U; ++u) {
         const bool ok = j0 + u < ne;
         const int jj = (int)min(j0 + u, ne - 1);
-        const uint32_t dd = (uint32_t)__shfl((int)my_d, jj, 64);
-        const uint64_t eb = (uint64_t)(uint32_t)__shfl((int)my_e, jj, 64) * heads;
+        const uint32_t dd = chunk_get(my_d, j0 + u, ne);
+        const uint64_t eb = (uint64_t)chunk_get(my_e, j0 + u, ne) * heads;
         const T* gm = reinterpret_cast<const T*>(GM + (uint64_t)dd * ldm);
         const T* hr = reinterpret_cast<const T*>(Hd + (uint64_t)dd * ldhd);
         [[maybe_unused]] uint64_t kj[NCH];
@@ -470,8 +470,6 @@ uint32_t gatv2_rows_per_block(uint32_t v_size) {
   return std::max(waves, (per + waves - 1) / waves * waves);
 }
 
-static bool al16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace nts_hip
 
 using namespace nts_hip;
@@ -487,40 +485,22 @@ int nts_hip_gatv2_forward(nts_hip_ctx* ctx, const uint32_t* column_offset,
   const char* fn = __func__;
   GAT_CHECK(ctx && column_offset && row_indices && Hs && Hd && att && u_out && a_out && Y,
             "NULL argument");
-  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
-  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
-  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  std::optional<GatDrop> drv;
+  NTS_RET(gat_drop(fn, p_attn, p_out, seed, off_attn, off_out, &drv));
+  NTS_RET(gat_heads_check(fn, heads, D));
   const uint32_t F = heads * D, FY = mean ? D : F;
   GAT_CHECK(ldhs >= F && ldhd >= F && ldy >= FY, "leading dimension");
-  const bool v4 = D % 4 == 0 && ldhs % 4 == 0 && ldhd % 4 == 0 && ldy % 4 == 0 && al16(Hs) &&
-                  al16(Hd) && al16(Y) && al16(att);
-  const HeadsShape hs = heads_shape(heads, D, v4);
-  GAT_CHECK(hs.nch <= 4, kGatHeadsWidthMsg);
+  const bool v4 = gat_vec4(D, {{Hs, ldhs}, {Hd, ldhd}, {Y, ldy}, {att, 0}});
+  HeadsShape hs;
+  NTS_RET(gat_heads_shape(fn, heads, D, v4, &hs));
   if (v_size == 0) return NTS_OK;
-  const GatDrop drv = gat_drop(p_attn, p_out, seed, off_attn, off_out);
-  const GatDrop* dr = p_attn > 0.f || p_out > 0.f ? &drv : nullptr;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
-  const hipStream_t st = ctx->stream;
-  const uint32_t n = v_size;
-  // mean mode: one row of nch * 64 vectors per wave (16 KiB a block at VEC 4, NCH 4)
-  const size_t lds = mean ? (size_t)(kGatThreads / 64) * hs.nch * 64 * (v4 ? 16 : 4) : 0;
-#define BASE column_offset, row_indices, v_size, Hs, ldhs, Hd, ldhd, hs.nvec, hs.g, heads, att, \
-             u_out, a_out, Y, ldy, mean
-  if (!dr) {
-#define ARGS BASE
-#define GAT_T
-    NTS_GAT_HEADS_DISPATCH(k_gatv2_fwd);
-#undef GAT_T
-#undef ARGS
-  } else {
-#define ARGS BASE, *dr
-#define GAT_T GAT_T_DROP
-    NTS_GAT_HEADS_DISPATCH(k_gatv2_fwd);
-#undef GAT_T
-#undef ARGS
-  }
-#undef BASE
-  return NTS_OK;
+  return gat_dispatch(v4, hs.nch, hs.mode, [&](auto V, auto N, auto M) {
+    return gat_launch(k_gatv2_fwd<V(), N(), M()>, k_gatv2_fwd<V(), N(), M(), true, GatDrop>,
+                      gat_grid(v_size), gat_mean_lds(mean, hs.nch, v4), ctx->stream,
+                      gat_drop_ptr(drv), column_offset, row_indices, v_size, Hs, ldhs, Hd, ldhd,
+                      hs.nvec, hs.g, heads, att, u_out, a_out, Y, ldy, mean);
+  });
 }
 
 int nts_hip_gatv2_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
@@ -537,24 +517,21 @@ int nts_hip_gatv2_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
   GAT_CHECK(ctx && column_offset && row_indices && row_offset && column_indices && csr_edge_id &&
                 Hs && Hd && att && a && Y && GY && du && GM && dHs && dHd && datt,
             "NULL argument");
-  GAT_CHECK(gat_rate_ok(p_attn) && gat_rate_ok(p_out), kGatRateMsg);
-  GAT_CHECK(heads >= 1 && D >= 1, "heads must be >= 1 and D >= 1");
-  GAT_CHECK((uint64_t)heads * D <= 1024, kGatHeadsWidthMsg);
+  std::optional<GatDrop> drv;
+  NTS_RET(gat_drop(fn, p_attn, p_out, seed, off_attn, 0, &drv));
+  const GatDrop* dr = gat_drop_ptr(drv);
+  NTS_RET(gat_heads_check(fn, heads, D));
   const uint32_t F = heads * D, FY = mean ? D : F;
   GAT_CHECK(ldhs >= F && ldhd >= F && ldy >= FY && ldg >= FY && ldm >= F && lddhs >= F &&
                 lddhd >= F,
             "leading dimension");
-  const bool v4 = D % 4 == 0 && ldhs % 4 == 0 && ldhd % 4 == 0 && ldy % 4 == 0 && ldg % 4 == 0 &&
-                  ldm % 4 == 0 && lddhs % 4 == 0 && lddhd % 4 == 0 && al16(Hs) && al16(Hd) &&
-                  al16(Y) && al16(att) && al16(GY) && al16(GM) && al16(dHs) && al16(dHd);
-  const HeadsShape hs = heads_shape(heads, D, v4);
+  const bool v4 = gat_vec4(D, {{Hs, ldhs}, {Hd, ldhd}, {Y, ldy}, {att, 0}, {GY, ldg}, {GM, ldm},
+                               {dHs, lddhs}, {dHd, lddhd}});
   // a refused shape leaves every output as it was
-  GAT_CHECK(hs.nch <= 4, kGatHeadsWidthMsg);
-  const GatDrop drv = gat_drop(p_attn, p_out, seed, off_attn, 0);
-  const GatDrop* dr = p_attn > 0.f || p_out > 0.f ? &drv : nullptr;
+  HeadsShape hs;
+  NTS_RET(gat_heads_shape(fn, heads, D, v4, &hs));
   NTS_HIP_TRY(hipSetDevice(ctx->device));
   const hipStream_t st = ctx->stream;
-  const size_t lds = 0;  // the backward kernels use static LDS only
   if (v_size == 0) {
     NTS_HIP_TRY(hipMemsetAsync(datt, 0, (size_t)F * sizeof(float), st));
   } else {
@@ -562,64 +539,23 @@ int nts_hip_gatv2_backward(nts_hip_ctx* ctx, const uint32_t* column_offset,
     const uint32_t nblk = ceil_div(v_size, rpb);
     NTS_RET(ensure_scratch(ctx, (size_t)nblk * F * sizeof(float)));
     float* part = reinterpret_cast<float*>(ctx->scratch);
-    const dim3 grid(nblk);
-#define BASE column_offset, row_indices, v_size, rpb, Hs, ldhs, Hd, ldhd, hs.nvec, hs.g, heads, att, \
-             a, Y, ldy, GY, ldg, du, GM, ldm, dHd, lddhd, part, mean
-    if (!dr) {
-#define ARGS BASE
-#define GAT_T
-      if (v4) {
-        NTS_GAT_HEADS_MODE(k_gatv2_bwd_dst, 4)
-      } else {
-        NTS_GAT_HEADS_MODE(k_gatv2_bwd_dst, 1)
-      }
-#undef GAT_T
-#undef ARGS
-    } else {
-#define ARGS BASE, *dr
-#define GAT_T GAT_T_DROP
-      if (v4) {
-        NTS_GAT_HEADS_MODE(k_gatv2_bwd_dst, 4)
-      } else {
-        NTS_GAT_HEADS_MODE(k_gatv2_bwd_dst, 1)
-      }
-#undef GAT_T
-#undef ARGS
-    }
-#undef BASE
-    NTS_LAUNCH_CHECK();
+    NTS_RET(gat_dispatch(v4, hs.nch, hs.mode, [&](auto V, auto N, auto M) {
+      return gat_launch(k_gatv2_bwd_dst<V(), N(), M()>,
+                        k_gatv2_bwd_dst<V(), N(), M(), true, GatDrop>, dim3(nblk), 0, st, dr,
+                        column_offset, row_indices, v_size, rpb, Hs, ldhs, Hd, ldhd, hs.nvec, hs.g,
+                        heads, att, a, Y, ldy, GY, ldg, du, GM, ldm, dHd, lddhd, part, mean);
+    }));
     hipLaunchKernelGGL(k_gatv2_datt_reduce, dim3(ceil_div(F, 64)), dim3(64 * kV2Segs), 0, st, part,
                        nblk, F, datt);
     NTS_LAUNCH_CHECK();
   }
-  if (src_size) {
-    const dim3 grid(std::max(1u, ceil_div(src_size, kGatThreads / 64)));
-#define BASE row_offset, column_indices, csr_edge_id, src_size, hs.nvec, hs.g, heads, a, du, att, \
-             Hs, ldhs, Hd, ldhd, GM, ldm, dHs, lddhs
-    if (!dr) {
-#define ARGS BASE
-#define GAT_T
-      if (v4) {
-        NTS_GAT_HEADS_NCH(k_gatv2_bwd_src, 4, 0)
-      } else {
-        NTS_GAT_HEADS_NCH(k_gatv2_bwd_src, 1, 0)
-      }
-#undef GAT_T
-#undef ARGS
-    } else {
-#define ARGS BASE, *dr
-#define GAT_T GAT_T_DROP
-      if (v4) {
-        NTS_GAT_HEADS_NCH(k_gatv2_bwd_src, 4, 0)
-      } else {
-        NTS_GAT_HEADS_NCH(k_gatv2_bwd_src, 1, 0)
-      }
-#undef GAT_T
-#undef ARGS
-    }
-#undef BASE
-    NTS_LAUNCH_CHECK();
-  }
+  if (src_size)
+    NTS_RET(gat_dispatch(v4, hs.nch, [&](auto V, auto N) {
+      return gat_launch(k_gatv2_bwd_src<V(), N(), 0>, k_gatv2_bwd_src<V(), N(), 0, true, GatDrop>,
+                        gat_grid(src_size), 0, st, dr, row_offset, column_indices, csr_edge_id,
+                        src_size, hs.nvec, hs.g, heads, a, du, att, Hs, ldhs, Hd, ldhd, GM, ldm, dHs,
+                        lddhs);
+    }));
   return NTS_OK;
 }
 

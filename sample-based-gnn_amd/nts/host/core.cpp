@@ -1375,15 +1375,15 @@ void KernelProfiler::reset() {
 // columns h and K + h (the other columns, products of one head's rows with
 // another head's dS, are dropped): the GEMM is the MFMA kernel that is there,
 // deterministic, and at K <= 8 its 2K columns still fill one 16-column tile.
-// p_attn / p_out > 0: the _drop entry points (attention and output dropout in
-// the same kernels; the backward regenerates the attention keep bits from
+// The _drop entry points take the rates as they are: with both 0 they run the
+// plain kernels; p_attn / p_out > 0 adds attention and output dropout in the
+// same kernels (the backward regenerates the attention keep bits from
 // (seed, off_attn) and reads the output mask off Y > 0).
 struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
   static NtsVar forward(AutogradContext* ctx, NtsVar X, NtsVar W, NtsVar Watt, int64_t sg_ptr,
                         int64_t cs_ptr, int64_t prof_ptr, int64_t heads, bool mean, double p_attn,
                         double p_out, int64_t seed, int64_t off_attn, int64_t off_out) {
     auto* sg = reinterpret_cast<sampCSC*>(sg_ptr);
-    const bool drop = p_attn > 0.0 || p_out > 0.0;  // else today's entry points
     auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
     auto* prof = reinterpret_cast<KernelProfiler*>(prof_ptr);
     TORCH_CHECK(sg->dst_local_id.defined() && sg->csr_edge_id.defined(),
@@ -1408,7 +1408,7 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     NtsVar Y = torch::empty({v, FY}, f32_opts(dev));
     hipStream_t st = (hipStream_t)cs->stream();
     if (prof) prof->begin(KernelProfiler::GAT_FWD, st);
-    if (drop && K == 1)
+    if (K == 1)
       hip_check(nts_hip_gat_forward_drop(
                     cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
                     H.data_ptr<float>(), (uint64_t)F, (uint32_t)F, Ac.data_ptr<float>(),
@@ -1416,7 +1416,7 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                     (float)p_attn, (float)p_out, (uint64_t)seed, (uint64_t)off_attn,
                     (uint64_t)off_out),
                 "nts_hip_gat_forward_drop");
-    else if (drop)
+    else
       hip_check(nts_hip_gat_forward_heads_drop(
                     cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
                     H.data_ptr<float>(), (uint64_t)F, (uint32_t)K, (uint32_t)D,
@@ -1424,20 +1424,6 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                     Y.data_ptr<float>(), (uint64_t)FY, mean ? 1 : 0, (float)p_attn, (float)p_out,
                     (uint64_t)seed, (uint64_t)off_attn, (uint64_t)off_out),
                 "nts_hip_gat_forward_heads_drop");
-    else if (K == 1)
-      hip_check(nts_hip_gat_forward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
-                                    (uint32_t)v, H.data_ptr<float>(), (uint64_t)F, (uint32_t)F,
-                                    Ac.data_ptr<float>(), m.data_ptr<float>(), a.data_ptr<float>(),
-                                    Y.data_ptr<float>(), (uint64_t)F),
-                "nts_hip_gat_forward");
-    else
-      hip_check(nts_hip_gat_forward_heads(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(),
-                                          sg->dev_dst_local_id(), (uint32_t)v, H.data_ptr<float>(),
-                                          (uint64_t)F, (uint32_t)K, (uint32_t)D,
-                                          Ac.data_ptr<float>(), m.data_ptr<float>(),
-                                          a.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)FY,
-                                          mean ? 1 : 0),
-                "nts_hip_gat_forward_heads");
     // compulsory bytes: H rows once, offsets, row index + score + weight per
     // edge, dst local ids, W_att, output rows
     if (prof)
@@ -1464,7 +1450,6 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     const double p_out = ctx->saved_data["p_out"].toDouble();
     const uint64_t seed = (uint64_t)ctx->saved_data["seed"].toInt();
     const uint64_t off_attn = (uint64_t)ctx->saved_data["off_attn"].toInt();
-    const bool drop = p_attn > 0.0 || p_out > 0.0;
     auto* sg = reinterpret_cast<sampCSC*>(ctx->saved_data["sg"].toInt());
     auto* cs = reinterpret_cast<NtsStream*>(ctx->saved_data["cs"].toInt());
     NtsVar GY = grads[0].contiguous();
@@ -1480,7 +1465,7 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
     NtsVar dH = torch::empty({s, F}, f32_opts(dev));
     NtsVar dS = torch::empty({s, 2 * K}, f32_opts(dev));
     NtsVar GM = torch::empty({std::max<int64_t>(v, 1), F}, f32_opts(dev));
-    if (drop && K > 1)
+    if (K > 1)
       hip_check(nts_hip_gat_backward_heads_drop(
                     cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
                     sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
@@ -1490,7 +1475,7 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                     GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(), (uint64_t)F,
                     dS.data_ptr<float>(), mean ? 1 : 0, (float)p_attn, (float)p_out, seed, off_attn),
                 "nts_hip_gat_backward_heads_drop");
-    else if (drop)
+    else
       hip_check(nts_hip_gat_backward_drop(
                     cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
                     sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
@@ -1500,27 +1485,6 @@ struct HipGATLayerFn : public torch::autograd::Function<HipGATLayerFn> {
                     GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(), (uint64_t)F,
                     dS.data_ptr<float>(), (float)p_attn, (float)p_out, seed, off_attn),
                 "nts_hip_gat_backward_drop");
-    else if (K > 1)
-      hip_check(nts_hip_gat_backward_heads(
-                    cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(), (uint32_t)v,
-                    sg->dev_r_o(), sg->dev_c_i(), dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
-                    H.data_ptr<float>(), (uint64_t)F, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(),
-                    a.data_ptr<float>(), m.data_ptr<float>(), Y.data_ptr<float>(), (uint64_t)FY,
-                    GY.data_ptr<float>(), (uint64_t)FY, du.data_ptr<float>(), ds2.data_ptr<float>(),
-                    GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(), (uint64_t)F,
-                    dS.data_ptr<float>(), mean ? 1 : 0),
-                "nts_hip_gat_backward_heads");
-    else
-      hip_check(nts_hip_gat_backward(cs->ctx(), sg->dev_c_o(), sg->dev_r_i(), sg->dev_dst_local_id(),
-                                     (uint32_t)v, sg->dev_r_o(), sg->dev_c_i(),
-                                     dptr<uint32_t>(sg->csr_edge_id), (uint32_t)s,
-                                     H.data_ptr<float>(), (uint64_t)F, (uint32_t)F,
-                                     A.data_ptr<float>(), a.data_ptr<float>(), m.data_ptr<float>(),
-                                     Y.data_ptr<float>(), (uint64_t)F, GY.data_ptr<float>(),
-                                     (uint64_t)F, du.data_ptr<float>(), ds2.data_ptr<float>(),
-                                     GM.data_ptr<float>(), (uint64_t)F, dH.data_ptr<float>(),
-                                     (uint64_t)F, dS.data_ptr<float>()),
-                "nts_hip_gat_backward");
     NtsVar dW = torch::empty({Fin, F}, f32_opts(dev));
     hip_check(nts_hip_gemm_f32(cs->ctx(), 1, (int)Fin, (int)F, (int)s, X.data_ptr<float>(),
                                (uint64_t)X.stride(0), dH.data_ptr<float>(), (uint64_t)F,

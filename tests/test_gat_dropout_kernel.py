@@ -15,6 +15,12 @@ extreme scores:
 
     err(kernel) <= C * err(q32) + 8 * 2^-24,   C = 8 (tests/step_check.py).
 
+CELLS adds, with the rates (0.6, 0.5) and moderate scores, a shape for every
+(vector width, chunks[, reduction scheme]) combination of the single-head and
+the multi-head kernels that the cases above leave out, so that each dropout
+kernel the dispatch can pick is run; the scalar-path cells put every row
+operand 4 bytes past a 16-byte boundary.
+
 Incoming gradients are zeroed where the float64 pre-activation has 0 < |Z| <
 1e-4 (§8b).  The cap on their share, 1e-3 (or one element), counts the elements
 of non-empty rows in which a head keeps at least a quarter of its attention
@@ -50,7 +56,41 @@ HEADS = {"K8-D8-concat": (8, 8, False), "K4-D256-concat": (4, 256, False),
          "K3-D20-concat": (3, 20, False), "K3-D7-concat": (3, 7, False),
          "K4-D16-mean": (4, 16, True), "K2-D128-mean": (2, 128, True)}
 CASES = {**SINGLE, **HEADS}
-RATES = [(0.6, 0.0), (0.0, 0.5), (0.6, 0.5)]
+RATES = {"attn": (0.6, 0.0), "feat": (0.0, 0.5), "both": (0.6, 0.5)}
+# The cells of the kernel dispatch that CASES leaves out: the other four
+# (VEC, NCH) of the single-head kernels and, for the multi-head ones, the
+# smallest shape of every other (VEC, NCH, MODE) (g = D / 4 lanes per head on the
+# float4 path, D on the scalar one; NCH = ceil(K g / 64)).  id: (K, D, mean, base
+# offset in floats of every row operand: 1 forces the scalar path).  Run with
+# both dropouts in the moderate regime.
+CELLS = {
+    "cell-F516-v4n3": (1, 516, False, 0),
+    "cell-F33-v1n1": (1, 33, False, 0),
+    "cell-F129-v1n3": (1, 129, False, 0),
+    "cell-F193-v1n4": (1, 193, False, 0),
+    "cell-v4-pow2-n2-K8-D64": (8, 64, False, 0),
+    "cell-v4-pow2-n3-K5-D128": (5, 128, False, 0),
+    "cell-v4-pow2-n4-K8-D128": (8, 128, False, 0),
+    "cell-v4-chunk-n1-K1-D256-heads-entry": (1, 256, False, 0),
+    "cell-v4-chunk-n2-K2-D256": (2, 256, False, 0),
+    "cell-v4-chunk-n3-K3-D256": (3, 256, False, 0),
+    "cell-v4-any-n2-K2-D132": (2, 132, False, 0),
+    "cell-v4-any-n3-K3-D176": (3, 176, False, 0),
+    "cell-v4-any-n4-K4-D208": (4, 208, False, 0),
+    "cell-v1-pow2-n1-K8-D8-base+4B": (8, 8, False, 1),
+    "cell-v1-pow2-n2-K4-D32-base+4B": (4, 32, False, 1),
+    "cell-v1-pow2-n3-K6-D32-base+4B": (6, 32, False, 1),
+    "cell-v1-pow2-n4-K8-D32-base+4B": (8, 32, False, 1),
+    "cell-v1-chunk-n1-K1-D64-base+4B-heads-entry": (1, 64, False, 1),
+    "cell-v1-chunk-n2-K2-D64-base+4B": (2, 64, False, 1),
+    "cell-v1-chunk-n3-K3-D64-base+4B": (3, 64, False, 1),
+    "cell-v1-chunk-n4-K4-D64-base+4B": (4, 64, False, 1),
+    "cell-v1-any-n2-K3-D41": (3, 41, False, 0),
+    "cell-v1-any-n3-K3-D51": (3, 51, False, 0),
+    "cell-v1-any-n4-K5-D51": (5, 51, False, 0),
+}
+RUNS = ([(c, r, g) for g in ("moderate", "extreme") for r in RATES for c in CASES]
+        + [(c, "both", "moderate") for c in CELLS])
 
 
 @pytest.fixture(scope="module")
@@ -81,19 +121,32 @@ def keep_mask(hip, rows, cols, p, offset, seed=SEED):
     return (y > 0).cpu()
 
 
+def _at(rows, width, off, fill):
+    """[rows, width] on the device, contiguous, its base `off` floats past a fresh
+    allocation's; fill: a value or the [rows, width] tensor to hold"""
+    t = torch.empty(rows * width + 4, device=DEV)[off:off + rows * width].view(rows, width)
+    if torch.is_tensor(fill):
+        t.copy_(fill)
+    else:
+        t.fill_(fill)
+    return t
+
+
 class Run:
     """One forward + backward through the wrappers.  new: the _drop entry points
-    (single: K = 1 through the single-head ones); else the existing ones."""
+    (single: K = 1 through the single-head ones); else the existing ones.  off:
+    the base offset in floats of every row operand."""
 
-    def __init__(self, hip, block, H, att, GY, K, D, mean, q, p, new=True, heads_entry=None):
+    def __init__(self, hip, block, H, att, GY, K, D, mean, q, p, new=True, heads_entry=None,
+                 off=0):
         v, s, e = block["v"], block["s"], block["e"]
         d = block["dev"]
         F, FY = K * D, (D if mean else K * D)
         single = K == 1 if heads_entry is None else not heads_entry
-        self.H, self.att = H.to(DEV), att.to(DEV)
+        self.H, self.att = _at(s, F, off, H), att.to(DEV)
         self.m = torch.full((e * K,), SENT, device=DEV)
         self.a = torch.full((e * K,), SENT, device=DEV)
-        self.Y = torch.full((v, FY), SENT, device=DEV)
+        self.Y = _at(v, FY, off, SENT)
         co, ri, dl = d["column_offset"], d["row_indices"], d["dst_local_id"]
         fkw = dict(p_attn=q, p_out=p, seed=SEED, off_attn=OFF_A, off_out=OFF_F) if new else {}
         if single:
@@ -102,12 +155,12 @@ class Run:
         else:
             f = hip.gat_forward_heads_drop if new else hip.gat_forward_heads
             f(co, ri, dl, v, self.H, K, self.att, self.m, self.a, self.Y, mean=mean, **fkw)
-        self.GY = GY.to(DEV)
+        self.GY = _at(v, FY, off, GY)
         self.du = torch.full((e * K,), SENT, device=DEV)
         self.ds2 = torch.full((s * K,), SENT, device=DEV)
         self.dS = torch.full((s, 2 * K), SENT, device=DEV)
-        self.dH = torch.full((s, F), SENT, device=DEV)
-        self.GM = torch.full((v, F), SENT, device=DEV)
+        self.dH = _at(s, F, off, SENT)
+        self.GM = _at(v, F, off, SENT)
         bkw = dict(p_attn=q, p_out=p, seed=SEED, off_attn=OFF_A) if new else {}
         tail = (d["row_offset"], d["column_indices"], d["csr_edge_id"], s, self.H)
         if single:
@@ -191,11 +244,11 @@ def _case_data(hip, block, K, D, mean, regime, q, p, tag):
     return H, att, GY, keepA, keepF, sa, sf
 
 
-@pytest.mark.parametrize("regime", ["moderate", "extreme"])
-@pytest.mark.parametrize("q,p", RATES, ids=["attn", "feat", "both"])
-@pytest.mark.parametrize("case", list(CASES))
-def test_dropout_kernels_match_the_float64_chain(hip, block, case, q, p, regime):
-    K, D, mean = CASES[case]
+@pytest.mark.parametrize("case,rates,regime", RUNS, ids=[f"{c}-{r}-{g}" for c, r, g in RUNS])
+def test_dropout_kernels_match_the_float64_chain(hip, block, case, rates, regime):
+    K, D, mean, off = (*CASES[case], 0) if case in CASES else CELLS[case]
+    q, p = RATES[rates]
+    entry = dict(off=off, heads_entry=True if "heads-entry" in case else None)
     tag = f"{case} q={q} p={p} {regime}"
     H, att, GY, keepA, keepF, sa, sf = _case_data(hip, block, K, D, mean, regime, q, p, tag)
     if q:  # the masks are not trivial
@@ -206,7 +259,7 @@ def test_dropout_kernels_match_the_float64_chain(hip, block, case, q, p, regime)
     r32 = _reference(block, H, att, GY, K, D, mean, keepA, sa, keepF, sf, torch.float32)
     if regime == "extreme":
         assert float(r64["m"].max()) > 89.0  # float32 exp overflows there
-    run = Run(hip, block, H, att, GY, K, D, mean, q, p)
+    run = Run(hip, block, H, att, GY, K, D, mean, q, p, **entry)
     got = run.results()
     for k, t in got.items():
         assert bool(torch.isfinite(t).all()), f"{k} has a NaN or inf"
@@ -229,13 +282,13 @@ def test_dropout_kernels_match_the_float64_chain(hip, block, case, q, p, regime)
         ones = dict(keepA=None, sa=1.0, keepF=None, sf=1.0)
         p64 = _reference(block, H, att, GY, K, D, mean, dtype=torch.float64, **ones)
         p32 = _reference(block, H, att, GY, K, D, mean, dtype=torch.float32, **ones)
-        plain = Run(hip, block, H, att, GY, K, D, mean, 0.0, 0.0, new=False).results()
+        plain = Run(hip, block, H, att, GY, K, D, mean, 0.0, 0.0, new=False, **entry).results()
         for k in ("Y", "m", "a", "dH", "dW_att"):
             ek, e32 = err(plain[k], p64[k]), err(p32[k], p64[k])
             print(f"  PLAIN {tag} {k}: err(kernel) {ek:.3e} err(fp32 chain) {e32:.3e} "
                   f"ratio {ek / max(e32, 2.0 ** -30):.2f}")
     assert not bad, "; ".join(bad)
-    again = Run(hip, block, H, att, GY, K, D, mean, q, p).outputs()
+    again = Run(hip, block, H, att, GY, K, D, mean, q, p, **entry).outputs()
     for k, t in run.outputs().items():
         assert torch.equal(t, again[k]), f"{k} differs between two runs"
 

@@ -7,7 +7,10 @@ of tests/test_gat_kernel.py.
 Cases cover every reduction scheme (g = D / VEC lanes per head a power of two
 below 64, a multiple of 64, anything else), both vector widths, 1 to 4 chunks
 and both output modes, each in the moderate (att = randn * 0.3) and the extreme
-(att = randn * 150 / (1.4 sqrt(D))) score regime.
+(att = randn * 150 / (1.4 sqrt(D))) score regime.  CELLS adds, in concat mode
+and the moderate regime, the smallest shape of every (vector width, chunks,
+scheme) combination the cases leave out, so that each of the 24 kernels the
+dispatch can pick is run.
 
 Bound, for each of Y, m, a, dH, dW_att against float64 autograd through the
 per-head chain of tests/gat_heads_blocks.py, with q32 the same chain in float32:
@@ -65,6 +68,28 @@ CASES = {
     "K2-D128-mean": (2, 128, True, 0),
     "K3-D41-mean-scalar": (3, 41, True, 0),
 }
+# The (VEC, NCH, MODE) cells of the kernel dispatch that CASES leaves out (g = D / 4
+# lanes per head on the float4 path, D on the scalar one; NCH = ceil(K g / 64)):
+# concat mode, run in the moderate regime only.
+CELLS = {
+    "cell-v4-pow2-n2-K8-D64": (8, 64, False, 0),
+    "cell-v4-pow2-n3-K5-D128": (5, 128, False, 0),
+    "cell-v4-pow2-n4-K8-D128": (8, 128, False, 0),
+    "cell-v4-chunk-n1-K1-D256": (1, 256, False, 0),
+    "cell-v4-chunk-n2-K2-D256": (2, 256, False, 0),
+    "cell-v4-chunk-n3-K3-D256": (3, 256, False, 0),
+    "cell-v4-any-n3-K3-D176": (3, 176, False, 0),
+    "cell-v4-any-n4-K4-D208": (4, 208, False, 0),
+    "cell-v1-pow2-n1-K8-D8-base+4B": (8, 8, False, 1),
+    "cell-v1-pow2-n2-K4-D32-base+4B": (4, 32, False, 1),
+    "cell-v1-pow2-n3-K6-D32-base+4B": (6, 32, False, 1),
+    "cell-v1-chunk-n1-K1-D64-base+4B": (1, 64, False, 1),
+    "cell-v1-chunk-n2-K2-D64-base+4B": (2, 64, False, 1),
+    "cell-v1-chunk-n3-K3-D64-base+4B": (3, 64, False, 1),
+    "cell-v1-chunk-n4-K4-D64-base+4B": (4, 64, False, 1),
+    "cell-v1-any-n3-K3-D51": (3, 51, False, 0),
+}
+RUNS = [(c, r) for r in ("moderate", "extreme") for c in CASES] + [(c, "moderate") for c in CELLS]
 
 
 def _pitch(width):
@@ -229,13 +254,12 @@ def _check_bound(got, r64, r32, case, regime, keys=("Y", "m", "a", "dH", "dW_att
     assert not bad, "; ".join(bad)
 
 
-@pytest.mark.parametrize("regime", ["moderate", "extreme"])
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case,regime", RUNS, ids=[f"{c}-{r}" for c, r in RUNS])
 def test_heads_kernels_match_the_float64_chain(hip, block, case, regime):
     """Y, m, a, dH and dW_att within C times the float32 chain's own error
     (measured ratios: DESIGN.md §8i), with the exact properties of empty
     columns, untouched padding and run-to-run bit identity."""
-    K, D, mean, off = CASES[case]
+    K, D, mean, off = {**CASES, **CELLS}[case]
     F, FY = K * D, (D if mean else K * D)
     v, s, e = block["v"], block["s"], block["e"]
     H, att, GY = _inputs(block, K, D, mean, regime)

@@ -4,7 +4,7 @@ the 64-edge chunk loops of k_gat_fwd, k_gat_bwd_dst and k_gat_bwd_src iterate,
 the running max / sum is carried, and the parked m / du are read back from a
 later chunk.
 
-Widths cover every (VEC, NCH) instantiation of NTS_GAT_DISPATCH, each in two
+Widths cover every (VEC, NCH) instantiation gat_dispatch can pick, each in two
 score regimes: moderate (att = randn * 0.3) and extreme (att = randn * 150 /
 (1.4 sqrt(F)): post-leaky scores from about -100 to several hundred, where a
 plain exp overflows and the attention is nearly one-hot).
@@ -49,6 +49,7 @@ LAYOUTS = {
     "F260-v4n2-partial": (260, 264, 0, 0),
     "F516-v4n3": (516, 520, 0, 0),
     "F1024-v4n4-full": (1024, 1028, 0, 0),
+    "F33-v1n1": (33, 36, 0, 0),
     "F67-v1n2": (67, 70, 0, 0),
     "F130-v1n3": (130, 133, 0, 0),
     "F255-v1n4": (255, 258, 0, 0),

@@ -7,7 +7,12 @@ tests/test_gat_heads_kernel.py.
 Cases cover every reduction scheme (g = D / VEC lanes per head a power of two
 below 64, a multiple of 64, anything else), both vector widths, 1 to 4 chunks
 and both output modes, each in the moderate (att = randn * 0.3) and the extreme
-(att = randn * 150 / (1.4 sqrt(D))) score regime.
+(att = randn * 150 / (1.4 sqrt(D))) score regime.  CELLS adds, in concat mode
+and the moderate regime, the smallest shape of every (vector width, chunks,
+scheme) combination the cases leave out, plain and with dropout, and DROP_HAVE
+runs the combinations the cases do have with dropout too, so that each of the
+48 forward and backward-per-destination kernels the dispatch can pick is run
+in its plain and in its dropout form.
 
 Bound, for each of Y, u, a, dHs, dHd, datt against float64 autograd through the
 materialised chain of tests/gatv2_blocks.py, with q32 the same chain in float32:
@@ -56,6 +61,37 @@ CASES = {
     "K4-D16-mean": (4, 16, True, 0),
     "K3-D41-mean-scalar": (3, 41, True, 0),
 }
+# The (VEC, NCH, MODE) cells of the kernel dispatch that CASES leaves out (g = D / 4
+# lanes per head on the float4 path, D on the scalar one; NCH = ceil(K g / 64)):
+# concat mode, run in the moderate regime, plain and with the rates (0.3, 0.4).
+CELLS = {
+    "cell-v4-pow2-n2-K8-D64": (8, 64, False, 0),
+    "cell-v4-pow2-n3-K5-D128": (5, 128, False, 0),
+    "cell-v4-pow2-n4-K8-D128": (8, 128, False, 0),
+    "cell-v4-chunk-n1-K1-D256": (1, 256, False, 0),
+    "cell-v4-chunk-n2-K2-D256": (2, 256, False, 0),
+    "cell-v4-chunk-n3-K3-D256": (3, 256, False, 0),
+    "cell-v4-any-n3-K3-D176": (3, 176, False, 0),
+    "cell-v4-any-n4-K4-D208": (4, 208, False, 0),
+    "cell-v1-pow2-n1-K8-D8-base+4B": (8, 8, False, 1),
+    "cell-v1-pow2-n2-K4-D32-base+4B": (4, 32, False, 1),
+    "cell-v1-pow2-n3-K6-D32-base+4B": (6, 32, False, 1),
+    "cell-v1-chunk-n1-K1-D64-base+4B": (1, 64, False, 1),
+    "cell-v1-chunk-n2-K2-D64-base+4B": (2, 64, False, 1),
+    "cell-v1-chunk-n3-K3-D64-base+4B": (3, 64, False, 1),
+    "cell-v1-chunk-n4-K4-D64-base+4B": (4, 64, False, 1),
+    "cell-v1-any-n3-K3-D51": (3, 51, False, 0),
+}
+ALL = {**CASES, **CELLS}
+RUNS = [(c, r) for r in ("moderate", "extreme") for c in CASES] + [(c, "moderate") for c in CELLS]
+DROP_CASES = ["K8-D8-concat-g2", "K5-D51-concat-scalar-straddle", "K4-D16-mean"]
+DROP_RATES = {"attn": (0.5, 0.0), "feat": (0.0, 0.5), "both": (0.3, 0.4)}
+# every cell of the table with both dropouts: the 16 added CELLS and the cells
+# CASES already has plain (K8-D8 and K5-D51 run "both" through DROP_CASES)
+DROP_HAVE = ["K4-D256-concat-chunk-per-head", "K3-D20-concat-g5", "K2-D132-concat-g33",
+             "K8-D32-concat-base+4B-scalar", "K8-D7-mean-scalar", "K3-D41-mean-scalar"]
+DROP_RUNS = ([(c, r) for r in DROP_RATES for c in DROP_CASES] +
+             [(c, "both") for c in DROP_HAVE] + [(c, "both") for c in CELLS])
 
 
 def _pitch(width):
@@ -218,13 +254,12 @@ def _check_bound(got, r64, r32, case, regime, keys=KEYS):
     assert not bad, "; ".join(bad)
 
 
-@pytest.mark.parametrize("regime", ["moderate", "extreme"])
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case,regime", RUNS, ids=[f"{c}-{r}" for c, r in RUNS])
 def test_v2_kernels_match_the_float64_chain(hip, block, case, regime):
     """Y, u, a, dHs, dHd and datt within C times the float32 chain's own error
     (measured ratios: DESIGN.md §8n), with the exact properties of empty
     columns, untouched padding and run-to-run bit identity."""
-    K, D, mean, off = CASES[case]
+    K, D, mean, off = ALL[case]
     F = K * D
     v, s, e = block["v"], block["s"], block["e"]
     Hs, Hd, att, GY = _inputs(block, K, D, mean, regime)
@@ -314,15 +349,15 @@ def keep_mask(hip, rows, cols, p, offset):
     return (y > 0).cpu()
 
 
-@pytest.mark.parametrize("q,p", [(0.5, 0.0), (0.0, 0.5), (0.3, 0.4)], ids=["attn", "feat", "both"])
-@pytest.mark.parametrize("case", ["K8-D8-concat-g2", "K5-D51-concat-scalar-straddle", "K4-D16-mean"])
-def test_dropout_matches_the_masked_chain(hip, block, case, q, p):
+@pytest.mark.parametrize("case,rates", DROP_RUNS, ids=[f"{c}-{r}" for c, r in DROP_RUNS])
+def test_dropout_matches_the_masked_chain(hip, block, case, rates):
     """Attention and output dropout against the chain with the masks that
     relu_dropout leaves of a ones tensor at the same key and offsets (element
     (e, h) at off_attn, element (d, c) of Y at off_out).  GY is zeroed where
     0 < |Z| < 1e-4; the cap on their share counts the rows in which a head keeps
     a quarter of its attention mass, as tests/test_gat_dropout_kernel.py does."""
-    K, D, mean, off = CASES[case]
+    K, D, mean, off = ALL[case]
+    q, p = DROP_RATES[rates]
     F, FY = K * D, (D if mean else K * D)
     v, e = block["v"], block["e"]
     Hs, Hd, att, GY = _inputs(block, K, D, mean, "moderate")
