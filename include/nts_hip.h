@@ -69,11 +69,20 @@ extern "C" {
  *                    (core/ntsFastSampler.hpp:200-205) in libstdc++ >= 11 form
  *                    (Lemire nearly-divisionless, uniform_int_dist.h:246-263).
  *  MT19937_DIV     : same stream, libstdc++ <= 10 form (2-division rejection).
+ *  PHILOX_SHARED   : one Philox word r(s) per *source* s of a layer call
+ *                    (counter (0, s, layer | 0x80000000, batch_seq)); a dst
+ *                    with deg > fanout keeps the `fanout` positions p with the
+ *                    smallest key (r(src_p) << 32) | p, in CSC order.  Each
+ *                    dst's set is still a uniform fanout-subset, but dsts
+ *                    sharing neighbours pick the same ones: a smaller
+ *                    frontier (fixed-size LABOR).  Stateless like
+ *                    PHILOX; any fanout.
  * The MT modes consume one generator shared by all layers/batches of a
  * context, exactly like the reference's thread_local generator. */
 #define NTS_RNG_PHILOX 0
 #define NTS_RNG_MT19937_LEMIRE 1
 #define NTS_RNG_MT19937_DIV 2
+#define NTS_RNG_PHILOX_SHARED 3
 
 /* Edge weights, mirrors `enum class WeightType{Sum, Mean, None}`
  * (core/ntsFastSampler.hpp:27) with the CPU sampler's formulas
@@ -229,7 +238,9 @@ int nts_hip_build_csc(nts_hip_ctx *ctx, const uint32_t *src, const uint32_t *dst
  *   (WeightCompute, core/coocsc.hpp:301-324).  Replaces
  *   sample_processing_get_co_gpu + sample_processing_traverse_gpu +
  *   sample_processing_update_ri_gpu + GetWeight (cuda/ntsCUDAGraphOP.cu:1246-1700).
- * batch_seq/layer key the PHILOX stream; MT modes ignore them. */
+ * batch_seq/layer key the PHILOX and PHILOX_SHARED streams; MT modes ignore
+ * them.  PHILOX_SHARED replaces only the draw: the deg > fanout dsts keep the
+ * positions with the smallest shared keys; everything else is the same. */
 int nts_hip_sample_layer(nts_hip_ctx *ctx, const nts_graph_dev *graph, int fanout,
                          int layer, uint64_t batch_seq, int rng_mode, int weight_type,
                          nts_sampcsc_dev *out);

@@ -384,6 +384,188 @@ __global__ __launch_bounds__(kSelThreads) void k_select_philox_g16(SelectArgs a)
   }
 }
 
+// ---- PHILOX_SHARED: one variate per source -------------------
+// Every source s of a layer call owns one word r(s) — word 0 of the PHILOX
+// stream of "destination" s with the layer word's top bit set, so it is no
+// word of a per-destination stream.  A destination with deg > n keeps the n
+// positions p of its list with the smallest key (r(grows[beg + p]) << 32) | p,
+// written in ascending position.  Destinations that share neighbours pick the
+// same ones, so the frontier shrinks; on its own each set is a uniform
+// n-subset (the keys of distinct sources are i.i.d.).
+//
+// One wave per destination.  The n-th smallest r is found exactly by a radix
+// select: T = its value, k = how many of the positions with r == T are kept
+// (the earliest k: the key's low word).  Then one ordered walk writes
+// {r < T} and the first k of {r == T} with ballot prefixes.
+//   deg <= kShRegMax : ids and keys in registers (kShKeys per lane), one bit
+//                      of r per step, counts by ballot + popcount;
+//   deg >  kShRegMax : four passes of 8-bit digits over a per-wave LDS
+//                      histogram (integer ds_add only), keys recomputed from
+//                      the ids in every pass — no scratch sized by the degrees.
+constexpr int kShKeys = 16;                             // keys per lane, register path
+constexpr uint32_t kShRegMax = kShKeys * kWave;         // last degree of the register path
+constexpr uint32_t kShLayerBit = 0x80000000u;
+
+__device__ __forceinline__ uint32_t shared_key(const SelectArgs& a, uint32_t s) {
+  return philox_word(a.seed, s, a.layer | kShLayerBit, a.batch_seq, 0u);
+}
+
+// LDS traffic of one wave is ordered; this keeps the compiler from moving
+// accesses across the point and drains the wave's outstanding LDS operations
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// The ordered walk, 64 positions per call (ascending): keeps r < T and the
+// first k positions with r == T.
+struct SharedEmit {
+  uint32_t out = 0, eqseen = 0;
+  __device__ __forceinline__ void round(const SelectArgs& a, uint32_t i, uint32_t c, uint32_t n,
+                                        bool valid, uint32_t r, uint32_t g, uint32_t T, uint32_t k,
+                                        uint64_t lt_mask) {
+    const bool eq = valid && r == T;
+    const uint64_t eqm = __ballot(eq);
+    const bool keep = (valid && r < T) || (eq && eqseen + (uint32_t)__popcll(eqm & lt_mask) < k);
+    const uint64_t km = __ballot(keep);
+    const uint32_t slot = out + (uint32_t)__popcll(km & lt_mask);
+    if (keep && slot < n) {
+      a.ans[c + slot] = g;
+      a.edst[c + slot] = i;
+      a.marks[g] = 1;
+    }
+    out += (uint32_t)__popcll(km);
+    eqseen += (uint32_t)__popcll(eqm);
+  }
+};
+
+__device__ __forceinline__ void shared_select_regs(const SelectArgs& a, uint32_t i, uint64_t beg,
+                                                   uint32_t deg, uint32_t n, uint32_t c, int lane) {
+  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const uint32_t J = (deg + kWave - 1) / kWave;  // rounds of 64 positions (wave-uniform)
+  uint32_t id[kShKeys], r[kShKeys];
+  uint32_t have = 0u;  // bit j: this lane holds position 64 j + lane
+#pragma unroll
+  for (int j = 0; j < kShKeys; ++j) {  // coalesced: 64 ids per round
+    const uint32_t p = (uint32_t)j * kWave + (uint32_t)lane;
+    id[j] = 0u;
+    r[j] = 0u;
+    if ((uint32_t)j < J && p < deg) {
+      id[j] = a.grows[beg + p];
+      r[j] = shared_key(a, id[j]);
+      have |= 1u << j;
+    }
+  }
+  // bit by bit from the top: the candidates (bit j of cand) are the positions
+  // whose higher bits equal the prefix; cnt0 of them have a 0 in bit b
+  uint32_t prefix = 0u, k = n, cand = have;
+  for (int b = 31; b >= 0; --b) {
+    const uint32_t bit = 1u << b;
+    uint32_t cnt0 = 0u;
+#pragma unroll
+    for (int j = 0; j < kShKeys; ++j)
+      if ((uint32_t)j < J)
+        cnt0 += (uint32_t)__popcll(__ballot(((cand >> j) & 1u) != 0u && (r[j] & bit) == 0u));
+    const bool one = k > cnt0;
+    if (one) {
+      k -= cnt0;
+      prefix |= bit;
+    }
+#pragma unroll
+    for (int j = 0; j < kShKeys; ++j)
+      if ((uint32_t)j < J && ((r[j] & bit) != 0u) != one) cand &= ~(1u << j);
+  }
+  SharedEmit em;
+#pragma unroll
+  for (int j = 0; j < kShKeys; ++j)
+    if ((uint32_t)j < J)
+      em.round(a, i, c, n, ((have >> j) & 1u) != 0u, r[j], id[j], prefix, k, lt_mask);
+}
+
+__device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t i, uint64_t beg,
+                                                   uint32_t deg, uint32_t n, uint32_t c, int lane,
+                                                   uint32_t* hist) {
+  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  uint4* mine = reinterpret_cast<uint4*>(hist) + lane;  // counters 4 lane .. 4 lane + 3
+  uint32_t prefix = 0u, known = 0u, k = n;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    *mine = make_uint4(0u, 0u, 0u, 0u);
+    wave_lds_sync();
+    for (uint32_t p0 = 0; p0 < deg; p0 += kWave) {
+      const uint32_t p = p0 + (uint32_t)lane;
+      if (p < deg) {
+        const uint32_t r = shared_key(a, a.grows[beg + p]);
+        if ((r & known) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
+      }
+    }
+    wave_lds_sync();
+    // the digit whose running count first reaches k (the candidates number
+    // at least k, so exactly one lane holds it)
+    const uint4 h = *mine;
+    const uint32_t s = h.x + h.y + h.z + h.w;
+    uint32_t incl = s;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+      const uint32_t t = __shfl_up(incl, o);
+      if (lane >= o) incl += t;
+    }
+    const uint32_t excl = incl - s;
+    const int L = __ffsll((long long)__ballot(excl < k && k <= incl)) - 1;
+    uint32_t kk = k - excl, d = 0u;
+    if (kk > h.x) {
+      kk -= h.x;
+      d = 1u;
+      if (kk > h.y) {
+        kk -= h.y;
+        d = 2u;
+        if (kk > h.z) {
+          kk -= h.z;
+          d = 3u;
+        }
+      }
+    }
+    const uint32_t digit = (uint32_t)__shfl((int)((uint32_t)lane * 4u + d), L);
+    k = (uint32_t)__shfl((int)kk, L);
+    prefix |= digit << shift;
+    known |= 255u << shift;
+    wave_lds_sync();  // the counters are read before the next pass zeroes them
+  }
+  SharedEmit em;
+  for (uint32_t p0 = 0; p0 < deg; p0 += kWave) {
+    const uint32_t p = p0 + (uint32_t)lane;
+    uint32_t g = 0u, r = 0u;
+    if (p < deg) {
+      g = a.grows[beg + p];
+      r = shared_key(a, g);
+    }
+    em.round(a, i, c, n, p < deg, r, g, prefix, k, lt_mask);
+  }
+}
+
+// PHILOX_SHARED: one wave per destination, grid-stride.
+__global__ __launch_bounds__(kSelThreads) void k_select_shared(SelectArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[kSelWaves][256];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t v = a.sizes[0];
+  const uint32_t nw = gridDim.x * kSelWaves;
+  for (uint32_t i = blockIdx.x * kSelWaves + w; i < v; i += nw) {
+    const uint32_t d = a.dst[i];
+    const uint64_t beg = a.goff[d];
+    const uint32_t deg = (uint32_t)(a.goff[d + 1] - beg);
+    const uint32_t c = a.co[i];
+    const uint32_t n = a.co[i + 1] - c;
+    if (c + n > a.e_cap) continue;  // capacity overflow (flagged by count_scan)
+    if (n == deg) {
+      copy_all(a, i, beg, deg, c, lane);
+    } else if (n > 0) {
+      if (deg <= kShRegMax)
+        shared_select_regs(a, i, beg, deg, n, c, lane);
+      else
+        shared_select_hist(a, i, beg, deg, n, c, lane, hist[w]);
+    }
+  }
+}
+
 // ---- MT19937 (reference stream) -------------------------------------------
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
   y ^= y >> 11;
@@ -1926,9 +2108,14 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
                                                    g->out_degree),
                 "weights requested without buffers/degrees");
   const bool up = up_degree && weight_type != NTS_WEIGHT_NONE;
-  NTS_CHECK_ARG(rng_mode >= NTS_RNG_PHILOX && rng_mode <= NTS_RNG_MT19937_DIV, "rng_mode");
-  NTS_CHECK_ARG(fanout <= (int)kBigFanoutMax, "fanout above 16384 (the distinct-position hash set)");
-  NTS_CHECK_ARG(rng_mode == NTS_RNG_PHILOX || fanout <= (int)(kMtTab / 2),
+  NTS_CHECK_ARG(rng_mode >= NTS_RNG_PHILOX && rng_mode <= NTS_RNG_PHILOX_SHARED, "rng_mode");
+  // the MT19937 modes replay one sequential generator (stream ring, per-dst
+  // info, re-runs); PHILOX and PHILOX_SHARED keep no generator state
+  const bool is_mt = rng_mode == NTS_RNG_MT19937_LEMIRE || rng_mode == NTS_RNG_MT19937_DIV;
+  // (PHILOX_SHARED selects by key order: no rejection set, any fanout)
+  NTS_CHECK_ARG(rng_mode == NTS_RNG_PHILOX_SHARED || fanout <= (int)kBigFanoutMax,
+                "fanout above 16384 (the distinct-position hash set)");
+  NTS_CHECK_ARG(!is_mt || fanout <= (int)(kMtTab / 2),
                 "MT19937 modes: fanout above 8192 (the exact path's hash set)");
   NTS_CHECK_ARG(g->n_vertices <= 0xFFFFFFFFull, "vertex count exceeds uint32 ids");
   const bool csr = o->row_offset != nullptr;
@@ -1962,7 +2149,7 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
   const uint32_t mt_csz = o->v_cap <= kMtSmallV                            ? kMtChunkSmall
                           : o->v_cap <= (uint64_t)kMtMaxChunks * kMtChunkMid ? kMtChunkMid
                                                                              : kMtChunk;
-  const bool mt_chunked = rng_mode != NTS_RNG_PHILOX && !mt_serial_env && fanout >= 1 &&
+  const bool mt_chunked = is_mt && !mt_serial_env && fanout >= 1 &&
                           fanout <= 32 && (uint64_t)o->v_cap <= (uint64_t)kMtMaxChunks * mt_csz &&
                           (mt_chunked_env || o->v_cap >= kMtChunkedMinV);
   const uint64_t nch_cap = (uint64_t)o->v_cap / mt_csz + 1;
@@ -1974,7 +2161,7 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
   // covers every degree profile's mean with 5 % and 131,072 words to spare
   // (the per-dst spread is ~sqrt(f) draws: invisible past a few dsts)
   const uint64_t w_cap = mt_word_bound(o->e_cap, fanout, ctx->mt_budget_scale);
-  const uint64_t mt_info_n = rng_mode != NTS_RNG_PHILOX ? al((uint64_t)o->v_cap * 4) : 0;
+  const uint64_t mt_info_n = is_mt ? al((uint64_t)o->v_cap * 4) : 0;
   const uint64_t mt_base_n = mt_chunked ? al((uint64_t)o->v_cap + 1) : 0;
   const uint64_t mt_stat_n = mt_chunked ? al(2 * nch_cap) : 0;
   const uint64_t mt_win_n = mt_chunked ? al(2 * nch_cap) : 0;
@@ -2051,6 +2238,9 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
       const uint32_t gs = std::max(1u, std::min(o->v_cap, 2048u));
       hipLaunchKernelGGL(k_select_philox_big, dim3(gs), dim3(kWave), lds, st, a, cap);
     }
+  } else if (rng_mode == NTS_RNG_PHILOX_SHARED) {
+    const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves), 4096u));
+    hipLaunchKernelGGL(k_select_shared, dim3(gs), dim3(kSelThreads), 0, st, a);
   } else {
     const int lem = rng_mode == NTS_RNG_MT19937_LEMIRE ? 1 : 0;
     constexpr int mt_dbg = 0;  // (the kernels' debug-dump argument: off)

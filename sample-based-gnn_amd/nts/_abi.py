@@ -22,6 +22,7 @@ ABI_VERSION = 11  # NTS_HIP_ABI_VERSION of the header these ctypes structs mirro
 NTS_RNG_PHILOX = 0
 NTS_RNG_MT19937_LEMIRE = 1
 NTS_RNG_MT19937_DIV = 2
+NTS_RNG_PHILOX_SHARED = 3
 NTS_GEMM_F32 = 0
 NTS_GEMM_SPLIT3 = 1
 NTS_GEMM_SPLIT3_ALL = 2  # the split kernels for every shape they take (kernel tests)

@@ -333,6 +333,14 @@ class InputInfo:
     # W_d x_dst), in every attention layer (GAT algorithms only; not with
     # FULL_INFERENCE)
     gat_v2: int = 0
+    # SAMPLE_SHARED (this build's key): 1 = shared-variate neighbour selection
+    # (one random variate per source vertex; every destination keeps its FANOUT
+    # neighbours with the smallest variates — the same per-destination
+    # distribution, a smaller frontier).  Philox-sampled algorithms without PD
+    # cache
+    sample_shared: int = 0
+    # SEED (this build's key): the driver's seed (sampler streams, dropout)
+    seed: int = 2000
     extra: dict = field(default_factory=dict)
 
     @property
@@ -366,6 +374,8 @@ class InputInfo:
             "GAT_ATTN_DROP": ("gat_attn_drop", float),
             "GAT_FEAT_DROP": ("gat_feat_drop", float),
             "GAT_V2": ("gat_v2", int),
+            "SAMPLE_SHARED": ("sample_shared", int),
+            "SEED": ("seed", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

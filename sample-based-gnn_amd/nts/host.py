@@ -85,7 +85,12 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
-               gat_feat_drop=0.0, gat_v2=False):
+               gat_feat_drop=0.0, gat_v2=False, shared_sampling=False):
+    if shared_sampling:  # one variate per source vertex
+        if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
+            raise ValueError("shared_sampling is not supported with an MT19937 rng_mode (it "
+                             "draws from a Philox stream of its own)")
+        rng_mode = _abi.NTS_RNG_PHILOX_SHARED
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
     gat_heads = check_gat_heads(layers, gat, gat_heads)

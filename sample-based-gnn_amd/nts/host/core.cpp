@@ -314,7 +314,7 @@ void FastSampler::issue_gpu_sample(int batch_size, int ssg_id, NtsStream& cs, We
   r.omit_key = omit_key;
   r.omit_loc = omit_loc;
   r.cs = &cs;
-  if (rng_mode != NTS_RNG_PHILOX) {
+  if (is_mt_mode(rng_mode)) {
     if (!r.mt_ckpt.defined())
       r.mt_ckpt = torch::empty({625}, u32_opts(whole_graph->device));
     // the generator state before the batch's first layer (stream order)
@@ -403,7 +403,7 @@ void FastSampler::set_mt_budget_scale(NtsStream& cs, double scale) {
 // checkpoint with every bound scaled up: the batch and each one issued after
 // it, in order (the same stream, so the same, reference-exact sets).
 void FastSampler::rerun_from(int ssg_id) {
-  TORCH_CHECK(rng_mode != NTS_RNG_PHILOX, "only the MT19937 modes can fall short");
+  TORCH_CHECK(is_mt_mode(rng_mode), "only the MT19937 modes can fall short");
   TORCH_CHECK(rerun_ok, "a short MT19937 stream with work chained to the sampled batches "
               "(early aggregation): cannot re-run");
   auto it = std::find(issued_.begin(), issued_.end(), ssg_id);

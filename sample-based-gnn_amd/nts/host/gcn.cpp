@@ -216,7 +216,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   else if (cfg.pipeline)
     ss = std::make_unique<NtsStream>(graph->device, nullptr, (uint64_t)cfg.seed,
                                      cfg.sampler_priority == 1 ||
-                                         (cfg.sampler_priority == 2 && cfg.rng_mode != NTS_RNG_PHILOX));
+                                         (cfg.sampler_priority == 2 && is_mt_mode(cfg.rng_mode)));
   // size the scratch arenas once so the training loop never allocates
   uint64_t items = graph->global_vertices;
   for (auto* s : sampler->ssg->sampled_sgs) items = std::max<uint64_t>({items, s->e_cap, s->v_cap});
@@ -237,6 +237,11 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                 "PD cache: GCN/GraphSAGE with >= 2 layers on the MFMA GEMMs");
     pd_cache_map_ = torch::full({(int64_t)graph->global_vertices}, -1, u32_opts(graph->device));
     pd_cache_loc_ = torch::zeros({(int64_t)graph->global_vertices}, u32_opts(graph->device));
+  }
+  if (cfg.rng_mode == NTS_RNG_PHILOX_SHARED) {  // (after every other option check)
+    TORCH_CHECK(!cfg.sample_gpu, "shared sampling is not supported with sample_gpu (the "
+                                 "reference's mt19937 stream)");
+    TORCH_CHECK(!cfg.pd_cache, "shared sampling is not supported with pd_cache");
   }
   for (int i = 0; i < nslots_; ++i) {
     TORCH_CHECK(hipEventCreateWithFlags(&ready_[i], hipEventDisableTiming) == hipSuccess,

@@ -11,6 +11,11 @@ struct GCNConfig {
   int batch_size = 1024;        // BATCH_SIZE
   float learn_rate = 0.01f, weight_decay = 1e-4f, drop_rate = 0.5f;
   float beta1 = 0.9f, beta2 = 0.999f, epsilon = 1e-9f;  // toolkits/GCN_SAMPLE_GPU.hpp:115-117
+  // NTS_RNG_PHILOX (default), the MT19937 modes (the reference's stream), or
+  // NTS_RNG_PHILOX_SHARED: one variate per source vertex, every destination
+  // keeps its `fanout` neighbours with the smallest variates (fixed-size LABOR,
+  // DESIGN §8o) — the same per-destination distribution, a smaller frontier.
+  // Not with sample_gpu or pd_cache.
   int rng_mode = NTS_RNG_PHILOX;
   // GCN_SAMPLE_GPU (toolkits/GCN_SAMPLE_GPU.hpp:289-394): the CPU sampler's
   // blocks (sample_fast: the reference's mt19937 stream, here replayed on the

@@ -228,6 +228,12 @@ class FeatureCache {
 // FastSampler (GPU form): sample_gpu_fast runs every hop on the device, with
 // one D2H copy of the layer sizes per batch.
 // ---------------------------------------------------------------------------
+// the modes that replay the reference's sequential generator (stream ring,
+// checkpoints, re-runs); PHILOX and PHILOX_SHARED keep no generator state
+inline bool is_mt_mode(int rng_mode) {
+  return rng_mode == NTS_RNG_MT19937_LEMIRE || rng_mode == NTS_RNG_MT19937_DIV;
+}
+
 class FastSampler {
  public:
   std::shared_ptr<FullyRepGraph> whole_graph;
@@ -240,7 +246,7 @@ class FastSampler {
   std::vector<SampledSubgraph*> ssgs;
   int rng_mode = NTS_RNG_PHILOX;
   bool up_degree = false;  // UP_DEGREE: weights from each sampled layer's own degrees
-  uint64_t batch_seq = 0;  // keys the PHILOX stream (one per sampled batch)
+  uint64_t batch_seq = 0;  // keys the PHILOX / PHILOX_SHARED streams (one per sampled batch)
   // sample_gpu_fast_omit (core/ntsFastSampler.hpp:711-915): when set, the
   // bottom layer skips the dsts with omit_map[d] == omit_key
   const uint32_t* omit_map = nullptr;

@@ -37,6 +37,12 @@ LAYER_NORM:1 (GCN / GraphSAGE algorithms without PD cache): every hidden layer
 is dropout(relu(LayerNorm(.))) in one fused pass, with a gamma and a beta per
 hidden layer that are trained without weight decay.
 
+SAMPLE_SHARED:1 (Philox-sampled algorithms without PD cache): neighbour
+selection with one random variate per source vertex, shared by every
+destination of a hop (fixed-size layer-neighbour sampling): each destination's
+set keeps its distribution, the hop's frontier shrinks.  SEED:n sets the
+driver's seed (default 2000).
+
 GAT_ATTN_DROP:0.6 / GAT_FEAT_DROP:0.6 (GAT algorithms): dropout of the attention
 coefficients and of every layer's input while training, fused into the GAT
 kernels.  DROP_RATE is not read by a GAT job (as in the reference).
@@ -135,6 +141,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.layer_norm and (model == "gat" or place == "pd"):
         raise SystemExit(f"ALGORITHM {info.algorithm}: LAYER_NORM is not supported with GAT or "
                          "PD-cache algorithms (GCN / GraphSAGE layers only)")
+    if info.sample_shared and (rng == "mt" or place == "pd"):
+        raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_SHARED is not supported with the "
+                         "mt19937-stream or PD-cache algorithms (Philox-sampled algorithms only)")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -152,7 +161,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         multi_label=bool(info.multi_label), root_weight=bool(info.root_weight),
         aggregator=info.aggregator, gat_heads=info.gat_heads or None,
         layer_norm=bool(info.layer_norm), gat_attn_drop=info.gat_attn_drop,
-        gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2))
+        gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2),
+        shared_sampling=bool(info.sample_shared), seed=info.seed)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
