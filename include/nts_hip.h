@@ -319,6 +319,43 @@ int nts_hip_spmm_graph_fwd(nts_hip_ctx *ctx, const nts_graph_dev *graph,
                            uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
                            const float *x, uint64_t ldx, uint32_t feature_size,
                            float *y, uint64_t ldy);
+/* ---- f16 feature table (csrc/agghalf.hip; GCNConfig::feature_f16) ---------
+ * The three gathers that read the feature table, over a table stored as IEEE
+ * half: f16 storage, fp32 arithmetic.  xh / tableh hold the bits of the halves
+ * (2-byte aligned at least), pitches of the half table are in halves, outputs
+ * stay fp32.  Widening a half is exact, so each call gives, bit for bit, what
+ * its fp32 sibling gives on the fp32 widening of the same table.  A lane loads
+ * 16 bytes (8 halves) where the base is 16-byte aligned, the pitch a multiple
+ * of 8 halves and the row, rounded up to 8, inside the pitch (the partial last
+ * vector then reads pitch padding of its own row); 8-, 4- or 2-byte loads
+ * otherwise.  A NULL table, feature_size == 0, a pitch below feature_size or
+ * an odd table address: NTS_ERR_INVALID with a message, nothing written.
+ *
+ * nts_hip_spmm_csc_fwd over a half table:
+ *   Y[d,:] = sum_{e in [co[d],co[d+1])} w[e] * float(Xh[row(e),:])
+ * serial in CSC edge order as (x*w)+acc from 0, no FMA contraction; weight
+ * NULL: w = 1; row(e) through x_row_map when non-NULL (fused feature gather).
+ * Every row d < *v (v NULL: v_cap) is written, empty columns as zeros; rows
+ * >= *v and the pitch padding of Y are not touched. */
+int nts_hip_spmm_csc_fwd_h(nts_hip_ctx *ctx, const uint32_t *column_offset,
+                           const uint32_t *row_indices, const float *weight,
+                           const uint32_t *v, uint32_t v_cap, const uint16_t *xh, uint64_t ldxh,
+                           const uint32_t *x_row_map, uint32_t feature_size, float *y,
+                           uint64_t ldy);
+/* nts_hip_spmm_graph_fwd over a half table (layer 0 of the full-neighbour
+ * pass): the same weights (SUM, MEAN, NONE; MEAN_SAMPLED and the UP_DEGREE bit
+ * are NTS_ERR_INVALID, as is a range outside the graph), the same order, hub
+ * columns (more than 2,048 edges) split by column slice and never by edge
+ * range, optional relu.  The same scratch. */
+int nts_hip_spmm_graph_fwd_h(nts_hip_ctx *ctx, const nts_graph_dev *graph,
+                             uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
+                             const uint16_t *xh, uint64_t ldxh, uint32_t feature_size,
+                             float *y, uint64_t ldy);
+/* out[i,:] = float(tableh[index[i],:]) for i < *n (n == NULL: n_cap rows):
+ * nts_hip_gather_rows from a half table into fp32 rows. */
+int nts_hip_gather_rows_h(nts_hip_ctx *ctx, const uint16_t *tableh, uint64_t ld_table,
+                          const uint32_t *index, const uint32_t *n, uint32_t n_cap,
+                          uint32_t feature_size, float *out, uint64_t ld_out);
 /* Stage the NON-cached rows of a layer's sources once into HBM:
  *   stage[i,:] = host_table[index[i],:]  for every i with cache_map[index[i]] ==
  *   NTS_NOT_CACHED (other rows of stage are left untouched).

@@ -26,17 +26,13 @@
 //
 // The GAT layer over the whole graph (nts_hip_gat_scores, nts_hip_gat_graph_fwd,
 // below) runs on the same items with an online softmax per lane.
-#include "common.hpp"
+#include "graph_hubs.hpp"
 
 #pragma clang fp contract(off)
 
 namespace nts_hip {
 
-constexpr int kInfThreads = 256;
-constexpr int kInfU = 8;             // neighbour rows in flight per lane group
-constexpr uint32_t kHubEdges = 2048; // rows longer than this are column-sliced
-constexpr int kHubLpd = 16;          // lanes per hub item
-constexpr uint32_t kHubGrid = 1024;  // hub kernel: grid-stride over the hub items
+// (kInfThreads, kInfU, kHubEdges, kHubLpd, kHubGrid: graph_hubs.hpp)
 
 template <int VEC>
 struct IV;
@@ -212,16 +208,9 @@ static int launch_graph_vec(hipStream_t st, const GraphAgg& a) {
   }
 }
 
-// The call's scratch (the two sqrt tables [V], the hub flags / their scan
-// [n + 1], the hub list [n], the scan's temporaries) and the hub list of rows
-// [v_begin, v_begin + n): flag, scan, scatter on the context's stream.
-struct HubScratch {
-  float *so, *si;
-  uint32_t *pos, *hubs;  // pos[n] = the hub count
-  float* extra;          // extra_words floats of the caller's own, 256-byte aligned
-};
-static int list_hubs(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_begin, uint64_t n,
-                     HubScratch& h, size_t extra_words = 0) {
+// (HubScratch: graph_hubs.hpp)
+int list_hubs(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_begin, uint64_t n,
+              HubScratch& h, size_t extra_words) {
   const uint64_t V = graph->n_vertices;
   hipStream_t st = ctx->stream;
   auto pad = [](uint64_t e) { return (e + 63) / 64 * 64; };
@@ -240,6 +229,14 @@ static int list_hubs(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_be
   NTS_RET(scan_exclusive<uint32_t>(h.pos, h.pos, nullptr, n, tmp, st));
   hipLaunchKernelGGL(k_hub_scatter, dim3(g), dim3(256), 0, st, (const uint32_t*)h.pos, v_begin, n,
                      h.hubs);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
+int degree_sqrt_tables(nts_hip_ctx* ctx, const nts_graph_dev* graph, float* so, float* si) {
+  const uint64_t V = graph->n_vertices;
+  hipLaunchKernelGGL(k_degree_sqrt, dim3(std::min(ceil_div(V, 256), kMaxGrid)), dim3(256), 0,
+                     ctx->stream, V, graph->out_degree, graph->in_degree, so, si);
   NTS_LAUNCH_CHECK();
   return NTS_OK;
 }
@@ -592,7 +589,7 @@ int nts_hip_spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_
   NTS_CHECK_ARG(weight_type == NTS_WEIGHT_NONE || (graph->in_degree && graph->out_degree),
                 "graph without its degrees");
   NTS_CHECK_ARG(ldx >= feature_size && ldy >= feature_size, "leading dimension < feature_size");
-  const uint64_t n = v_end - v_begin, V = graph->n_vertices;
+  const uint64_t n = v_end - v_begin;
   if (n == 0 || feature_size == 0) return NTS_OK;
   NTS_HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -600,11 +597,7 @@ int nts_hip_spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_
   NTS_RET(list_hubs(ctx, graph, v_begin, n, h));
   float *so = h.so, *si = h.si;
   uint32_t *pos = h.pos, *hubs = h.hubs;
-  if (weight_type != NTS_WEIGHT_NONE) {
-    hipLaunchKernelGGL(k_degree_sqrt, dim3(std::min(ceil_div(V, 256), kMaxGrid)), dim3(256), 0, st,
-                       V, graph->out_degree, graph->in_degree, so, si);
-    NTS_LAUNCH_CHECK();
-  }
+  if (weight_type != NTS_WEIGHT_NONE) NTS_RET(degree_sqrt_tables(ctx, graph, so, si));
 
   GraphAgg a;
   a.co = graph->column_offset;

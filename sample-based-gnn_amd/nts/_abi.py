@@ -66,6 +66,7 @@ EXPORTED = (
     "nts_hip_gat_forward_drop", "nts_hip_gat_backward_drop", "nts_hip_gat_forward_heads_drop",
     "nts_hip_gat_backward_heads_drop", "nts_hip_dropout_f32",
     "nts_hip_gatv2_forward", "nts_hip_gatv2_backward",
+    "nts_hip_spmm_csc_fwd_h", "nts_hip_spmm_graph_fwd_h", "nts_hip_gather_rows_h",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -131,6 +132,10 @@ def lib() -> C.CDLL:
         "nts_hip_gather_labels": ([P, P, P, P, U32, P], I),
         "nts_hip_spmm_csc_fwd": ([P, P, P, P, P, U32, P, U64, P, U32, P, U64], I),
         "nts_hip_spmm_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, I, I, P, U64, U32, P, U64], I),
+        # the f16 feature table's gathers: their fp32 siblings' arguments, a half table
+        "nts_hip_spmm_csc_fwd_h": ([P, P, P, P, P, U32, P, U64, P, U32, P, U64], I),
+        "nts_hip_spmm_graph_fwd_h": ([P, C.POINTER(GraphDev), U64, U64, I, I, P, U64, U32, P, U64], I),
+        "nts_hip_gather_rows_h": ([P, P, U64, P, P, U32, U32, P, U64], I),
         "nts_hip_spmm_csc_fwd_act": ([P, P, P, P, P, U32, P, U64, U32, P, U64, F, U64, U64], I),
         "nts_hip_spmm_csr_bwd_masked": ([P, P, P, P, P, U32, P, U64, P, U64, F, U32, P, U64], I),
         "nts_hip_spmm_csr_bwd_postmask": ([P, P, P, P, P, U32, P, U64, P, U64, F, U32, P, U64], I),

@@ -339,6 +339,11 @@ class InputInfo:
     # distribution, a smaller frontier).  Philox-sampled algorithms without PD
     # cache
     sample_shared: int = 0
+    # FEATURE_F16 (this build's key): 1 = the feature table is rounded to IEEE
+    # half on the host and kept in HBM as f16; every gather widens it back to
+    # fp32 (f16 storage, fp32 arithmetic).  GCN / GraphSAGE algorithms with the
+    # sum aggregator, without PD cache or root weight
+    feature_f16: int = 0
     # SEED (this build's key): the driver's seed (sampler streams, dropout)
     seed: int = 2000
     extra: dict = field(default_factory=dict)
@@ -375,6 +380,7 @@ class InputInfo:
             "GAT_FEAT_DROP": ("gat_feat_drop", float),
             "GAT_V2": ("gat_v2", int),
             "SAMPLE_SHARED": ("sample_shared", int),
+            "FEATURE_F16": ("feature_f16", int),
             "SEED": ("seed", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():

@@ -268,6 +268,29 @@ class HipContext:
                                               int(weight_type), int(bool(relu)), ptr(x),
                                               x.stride(0), x.shape[1], ptr(y), y.stride(0)))
 
+    # ---- f16 feature table: xh / table are torch.float16, outputs fp32 ----
+    def spmm_csc_fwd_h(self, co, ri, w, v_dev, v_cap, xh, y, row_map=None):
+        """spmm_csc_fwd over a half table: fp32 arithmetic, the bytes of the
+        fp32 call on xh.float()."""
+        check(self.lib.nts_hip_spmm_csc_fwd_h(self.h, ptr(co), ptr(ri), ptr(w), ptr(v_dev), v_cap,
+                                              ptr(xh), xh.stride(0), ptr(row_map), xh.shape[1],
+                                              ptr(y), y.stride(0)))
+
+    def spmm_graph_fwd_h(self, graph, xh, y, weight_type, relu=False, v_begin=0, v_end=None):
+        """spmm_graph_fwd over a half table."""
+        g = graph.as_struct()
+        if v_end is None:
+            v_end = graph.n_vertices
+        check(self.lib.nts_hip_spmm_graph_fwd_h(self.h, C.byref(g), int(v_begin), int(v_end),
+                                                int(weight_type), int(bool(relu)), ptr(xh),
+                                                xh.stride(0), xh.shape[1], ptr(y), y.stride(0)))
+
+    def gather_rows_h(self, table, index, n_dev, n_cap, out):
+        """out[i] = table[index[i]].float() from a half table."""
+        check(self.lib.nts_hip_gather_rows_h(self.h, ptr(table), table.stride(0), ptr(index),
+                                             ptr(n_dev), n_cap, table.shape[1], ptr(out),
+                                             out.stride(0)))
+
     def spmm_csc_fwd_act(self, co, ri, w, v_dev, v_cap, x, y, p=0.0, seed=0, offset=0):
         """y = dropout(relu(A x), p) (transform-first bottom layer)."""
         F = x.shape[1]

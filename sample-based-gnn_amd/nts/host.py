@@ -85,7 +85,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
-               gat_feat_drop=0.0, gat_v2=False, shared_sampling=False):
+               gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False):
     if shared_sampling:  # one variate per source vertex
         if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
             raise ValueError("shared_sampling is not supported with an MT19937 rng_mode (it "
@@ -140,6 +140,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.gat_feat_drop = gat_drop["gat_feat_drop"]  # by a GAT driver)
     if gat_v2:  # GATv2 scores; the default leaves the field as constructed
         c.gat_v2 = True
+    if feature_f16:  # f16 feature table; the default leaves the field as constructed
+        c.feature_f16 = True
     c.pd_cache = bool(pd_cache)
     c.pd_rate = float(pd_rate)
     c.pd_super_batch = int(pd_super_batch)

@@ -235,6 +235,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("aggregator", &GCNConfig::aggregator)
       .def_readwrite("layer_norm", &GCNConfig::layer_norm)
       .def_readwrite("layer_norm_eps", &GCNConfig::layer_norm_eps)
+      .def_readwrite("feature_f16", &GCNConfig::feature_f16)
       .def_readwrite("sampler_cus", &GCNConfig::sampler_cus)
       .def_readwrite("sampler_gate", &GCNConfig::sampler_gate)
       .def_readwrite("pad_features", &GCNConfig::pad_features)
@@ -328,6 +329,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("restart", &GCN_SAMPLE_ALLGPU_impl::restart)
       .def("synchronize", [](GCN_SAMPLE_ALLGPU_impl& d) { d.sync(); })
       .def_property_readonly("loss", [](GCN_SAMPLE_ALLGPU_impl& d) { return d.loss; })
+      // the feature table as the driver keeps it (feature_f16: the half table)
+      .def_property_readonly("F", [](GCN_SAMPLE_ALLGPU_impl& d) { return d.F; })
       .def_property_readonly("n_train", [](GCN_SAMPLE_ALLGPU_impl& d) { return d.sampler->work_range[1]; })
       .def_property_readonly("last_layers",
                              [](GCN_SAMPLE_ALLGPU_impl& d) {

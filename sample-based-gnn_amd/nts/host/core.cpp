@@ -460,6 +460,14 @@ void FastSampler::load_feature_gpu(NtsStream& cs, SampledSubgraph* sg, NtsVar& l
   if (!local_feature.defined() || local_feature.size(0) != (int64_t)top->src_size ||
       local_feature.size(1) != F)  // 128-byte row pitch: float4 rows for the GEMMs
     local_feature = row_padded_empty((int64_t)top->src_size, F, whole_graph->device);
+  if (global_feature.dtype() == torch::kFloat16) {  // the f16 table: widened as it is gathered
+    hip_check(nts_hip_gather_rows_h(cs.ctx(), dptr<const uint16_t>(global_feature),
+                                    (uint64_t)global_feature.stride(0), top->dev_src(), nullptr,
+                                    top->src_size, (uint32_t)F, local_feature.data_ptr<float>(),
+                                    (uint64_t)local_feature.stride(0)),
+              "nts_hip_gather_rows_h");
+    return;
+  }
   hip_check(nts_hip_gather_rows(cs.ctx(), global_feature.data_ptr<float>(),
                                 (uint64_t)global_feature.stride(0), top->dev_src(), nullptr,
                                 top->src_size, (uint32_t)F, local_feature.data_ptr<float>(),
@@ -548,10 +556,18 @@ void FastSampler::load_label_gpu(NtsStream& cs, SampledSubgraph* sg, NtsVar& loc
 // ---------------------------------------------------------------------------
 void spmm_csc_fwd(NtsStream& cs, AggKind kind, const sampCSC* s, const NtsVar& x, bool gather,
                   const uint32_t* v_dev, uint32_t v_rows, NtsVar& y, uint32_t* arg, bool early) {
-  const float* xp = x.data_ptr<float>();
   const uint64_t ldx = (uint64_t)x.stride(0), ldy = (uint64_t)y.stride(0);
   const uint32_t F = (uint32_t)x.size(1);
   const VertexId* map = gather ? s->dev_src() : nullptr;
+  if (x.dtype() == torch::kFloat16) {  // the f16 feature table: half rows in, fp32 sums out
+    TORCH_CHECK(gather && !kind.max && !kind.root,
+                "a half table is gathered by the sum aggregation only");
+    hip_check(nts_hip_spmm_csc_fwd_h(cs.ctx(), s->dev_c_o(), s->dev_r_i(), s->dev_e_w_f(), v_dev,
+                                     v_rows, dptr<const uint16_t>(x), ldx, map, F, y.data_ptr<float>(), ldy),
+              early ? "nts_hip_spmm_csc_fwd_h(early)" : "nts_hip_spmm_csc_fwd_h");
+    return;
+  }
+  const float* xp = x.data_ptr<float>();
   const VertexId* self = !kind.root ? nullptr : gather ? s->dev_dst() : s->dev_dst_local_id();
   if (kind.max)
     hip_check(nts_hip_spmm_csc_fwd_max(cs.ctx(), s->dev_c_o(), s->dev_r_i(), v_dev, v_rows, xp,
@@ -596,8 +612,10 @@ NtsVar SingleGPUAllSampleGraphOp::forward(NtsVar& f_input) {
   } else {
     TORCH_CHECK(!kind.root || sg->dst_local_id.defined(),
                 "root weight needs a merged src/dst layer");
-    TORCH_CHECK(f_input.is_cuda() && f_input.dtype() == torch::kFloat32 && f_input.dim() == 2 &&
-                    f_input.stride(1) == 1,
+    // (the f16 feature table is the one half input: gathered rows, no backward)
+    const bool half_table = gather_from_table && f_input.dtype() == torch::kFloat16;
+    TORCH_CHECK(f_input.is_cuda() && (f_input.dtype() == torch::kFloat32 || half_table) &&
+                    f_input.dim() == 2 && f_input.stride(1) == 1,
                 "graph op input must be a row-major fp32 CUDA matrix");
     TORCH_CHECK(gather_from_table || f_input.size(0) >= (int64_t)sg->src_size,
                 "graph op input has fewer rows than src_size");

@@ -22,6 +22,41 @@ static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// cfg.feature_f16: the table as IEEE half with rows a lane can load 16 bytes
+// of.  The pitch is the row rounded up to 8 halves; rows of 256 bytes and more
+// are padded to a 128-byte multiple, the fp32 table's rule for its wide rows
+// (a gathered row then spans the fewest cache lines).  An fp32 table is rounded
+// to nearest even by the copy; a half table that already has such rows is used
+// as given.  Values that are not finite as a half are refused.
+static NtsVar half_feature_table(const NtsVar& t, int device) {
+  const int64_t V = t.size(0), K = t.size(1);
+  const int64_t ld = K >= 128 ? (K + 63) / 64 * 64 : (K + 7) / 8 * 8;
+  NtsVar h = t;
+  // (as given: also the last row's pitch padding, which a 16-byte load of a
+  // partial last vector reads, must lie inside the tensor's storage)
+  const int64_t K8 = (K + 7) / 8 * 8;
+  const bool as_given =
+      t.dtype() == torch::kFloat16 && t.stride(1) == 1 && t.stride(0) % 8 == 0 &&
+      t.stride(0) >= K8 && (uintptr_t)t.data_ptr() % 16 == 0 &&
+      (uint64_t)(t.storage_offset() + std::max<int64_t>(V - 1, 0) * t.stride(0) + K8) * 2 <=
+          (uint64_t)t.storage().nbytes();
+  if (!as_given) {
+    h = torch::empty({V, ld}, torch::TensorOptions().dtype(torch::kFloat16).device(torch::kCUDA, device))
+            .narrow(1, 0, K);
+    h.copy_(t);
+  }
+  const NtsVar bad = torch::logical_not(torch::isfinite(h)).any(1);
+  const int64_t rows = bad.sum().item<int64_t>();
+  if (rows > 0) {
+    const int64_t n = torch::logical_not(torch::isfinite(h)).sum().item<int64_t>();
+    const int64_t first = bad.to(torch::kInt32).argmax().item<int64_t>();
+    TORCH_CHECK(false, "feature_f16: ", n, " feature value(s) are not finite as IEEE half (the "
+                "largest finite half is 65504); the first is in row ", first,
+                ": scale the features or keep the fp32 table");
+  }
+  return h;
+}
+
 GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
                                                NtsVar label, std::vector<VertexId> train_nids,
                                                GCNConfig c, std::shared_ptr<Communicator> comm_)
@@ -29,7 +64,11 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
       comm(std::move(comm_)) {
   TORCH_CHECK(cfg.layer_size.size() >= 2, "need at least one layer");
   TORCH_CHECK(cfg.fanout.size() == cfg.layer_size.size() - 1, "fanout per layer");
-  TORCH_CHECK(F.is_cuda() && F.dtype() == torch::kFloat32 && F.size(1) == cfg.layer_size[0],
+  TORCH_CHECK(F.dtype() != torch::kFloat16 || cfg.feature_f16,
+              "a float16 feature table needs feature_f16 (FEATURE_F16:1): without it the driver "
+              "takes an fp32 table");
+  TORCH_CHECK(F.is_cuda() && (F.dtype() == torch::kFloat32 || F.dtype() == torch::kFloat16) &&
+                  F.size(1) == cfg.layer_size[0],
               "feature table must be fp32 [V, layer_size[0]] on the GPU");
   if (cfg.multi_label) {
     TORCH_CHECK(!cfg.gat, "multi_label is not supported with GAT layers (GCN / GraphSAGE only)");
@@ -122,12 +161,15 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // +1% memory): a gathered row then spans the minimum number of cache lines
   // (19 instead of ~19.8 for 602 floats), ~2% less traffic in the bottom
   // aggregation, which reads every sampled row once per edge.
-  if (cfg.pad_features && F.size(1) >= 256 && F.size(1) % 32 != 0 && F.stride(1) == 1) {
+  // (feature_f16: its refusals follow every other option's below, and the
+  // half table is laid out there; nothing here touches the table before)
+  const bool f16 = cfg.feature_f16;
+  if (!f16 && cfg.pad_features && F.size(1) >= 256 && F.size(1) % 32 != 0 && F.stride(1) == 1) {
     NtsVar Fp = row_padded_empty(F.size(0), F.size(1), graph->device);
     Fp.copy_(F);
     F = Fp;
   }
-  if (cfg.cache_rate >= 0.0) {
+  if (cfg.cache_rate >= 0.0 && !f16) {
     TORCH_CHECK(cfg.cache_rate <= 1.0, "cache_rate must be in [0, 1]");
     const uint64_t V = graph->global_vertices;
     const uint64_t n_cache = std::min<uint64_t>(V, (uint64_t)(cfg.cache_rate * (double)V));
@@ -152,7 +194,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // least 4x and its GEMMs run on the whole-row fp32-exact kernels
   // (csrc/gemmx3.hip, split-bf16) or the f16 pair tables (C2: 602 -> 128,
   // 0.93 vs 1.04 ms/step fp32-exact); the reference's order elsewhere
-  tf_ = tf_ok && (cfg.transform_first == 1 ||
+  tf_ = tf_ok && !f16 && (cfg.transform_first == 1 ||
                   (cfg.transform_first < 0 &&
                    (cfg.pair_table >= 3 || cfg.gemm_mode == NTS_GEMM_SPLIT3) &&
                    cfg.layer_size[0] >= 4 * cfg.layer_size[1]));
@@ -242,6 +284,21 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     TORCH_CHECK(!cfg.sample_gpu, "shared sampling is not supported with sample_gpu (the "
                                  "reference's mt19937 stream)");
     TORCH_CHECK(!cfg.pd_cache, "shared sampling is not supported with pd_cache");
+  }
+  if (f16) {  // (after every other option's refusals)
+    const std::pair<bool, const char*> conflicts[] = {
+        {cfg.gat, "gat (GCN / GraphSAGE layers only)"},
+        {cfg.pd_cache, "pd_cache"},
+        {cfg.transform_first == 1,
+         "transform_first = 1 (the transform-first GEMMs gather fp32 rows: aggregate-first only)"},
+        {cfg.pair_table > 0, "pair_table > 0"},
+        {!(cfg.cache_rate < 0.0), "cache_rate >= 0"},
+        {cfg.root_weight, "root_weight"},
+        {max_aggr(), "aggregator = max"},
+    };
+    for (const auto& c : conflicts)
+      TORCH_CHECK(!c.first, "feature_f16 is not supported with ", c.second);
+    F = half_feature_table(F, graph->device);
   }
   for (int i = 0; i < nslots_; ++i) {
     TORCH_CHECK(hipEventCreateWithFlags(&ready_[i], hipEventDisableTiming) == hipSuccess,
@@ -368,7 +425,8 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
 double GCN_SAMPLE_ALLGPU_impl::bottom_bytes(SampledSubgraph* sg, bool fused_map) const {
   sampCSC* s = sg->sampled_sgs[sg->layers - 1];
   const double Fd = (double)(fcache ? fcache->F : F.size(1));
-  return Fd * 4.0 * s->src_size + 8.0 * s->e_size + 4.0 * (s->v_size + 1) +
+  const double xb = fcache ? 4.0 : (double)F.element_size();  // 2 with feature_f16
+  return Fd * xb * s->src_size + 8.0 * s->e_size + 4.0 * (s->v_size + 1) +
          Fd * 4.0 * s->v_size + (fused_map ? 4.0 * s->src_size : 0.0);
 }
 
@@ -1020,7 +1078,13 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
       evs.push_back({a, b});
       (void)hipEventRecord(a, st);
     }
-    if (max_aggr())
+    if (xr.dtype() == torch::kFloat16)  // feature_f16: layer 0 reads the half table
+      hip_check(nts_hip_spmm_graph_fwd_h(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+                                         dptr<const uint16_t>(xr), (uint64_t)xr.stride(0),
+                                         (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                         (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd_h");
+    else if (max_aggr())
       hip_check(nts_hip_spmm_graph_fwd_max(cs->ctx(), &g, 0, (uint64_t)V, relu ? 1 : 0,
                                            xr.data_ptr<float>(), (uint64_t)xr.stride(0),
                                            (uint32_t)xr.size(1), y.data_ptr<float>(),
@@ -1045,7 +1109,9 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
       // layer_norm: the hidden layer's activation is the fused LayerNorm pass
       // over A X W, whichever way the (linear) product was formed
       const bool ln = cfg.layer_norm && !last;
-      if (!cfg.root_weight && !max_aggr() && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
+      // (feature_f16: layer 0 aggregates first, from the half table: no fp32 copy of it)
+      const bool half_in = X.dtype() == torch::kFloat16;
+      if (!cfg.root_weight && !max_aggr() && !half_in && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
         NtsVar H = P[l]->forward(X);
         NtsVar Y = aggregate(H, !last && !ln);
         X = ln ? layer_norm_act(l, Y, 0.0, 0) : last && !cfg.multi_label ? Y.log_softmax(1) : Y;

@@ -93,6 +93,19 @@ struct GCNConfig {
   // transform_first = 1, pair_table > 0 or a hidden width above 1024.
   bool layer_norm = false;
   float layer_norm_eps = 1e-5f;
+  // f16 feature table: the table is kept in HBM as IEEE half and
+  // every gather of it (the bottom aggregation, early or in the step; the row
+  // gather of fused_gather = false; infer_full()'s layer 0) widens the rows to
+  // fp32 as it reads them — f16 storage, fp32 arithmetic, so the driver
+  // computes, bit for bit, what a driver without the option computes on
+  // table.half().float() with an aggregate-first bottom layer.  The
+  // constructor takes a kFloat32 table (rounded to nearest even on the device,
+  // the fp32 tensor released) or a kFloat16 one (used as given where its rows
+  // allow 16-byte loads); a value that is not finite as a half is refused.
+  // Aggregate-first only (transform_first = -1 resolves to 0).  Not with gat,
+  // pd_cache, transform_first = 1, pair_table > 0, cache_rate >= 0,
+  // root_weight or aggregator = max.
+  bool feature_f16 = false;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its

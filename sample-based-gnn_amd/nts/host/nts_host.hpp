@@ -332,7 +332,8 @@ struct AggKind {
 // `destination`), else x holds the layer's source rows (self rows:
 // dst_local_id).  v_dev / v_rows: the device row count, or NULL and the exact
 // one.  arg: the max kernel's winners (nullable).  early: the driver's launch
-// behind the sampling (the error label says so).
+// behind the sampling (the error label says so).  A kFloat16 x is the f16
+// feature table (gather, the plain sum): nts_hip_spmm_csc_fwd_h, y stays fp32.
 void spmm_csc_fwd(NtsStream& cs, AggKind kind, const sampCSC* s, const NtsVar& x, bool gather,
                   const uint32_t* v_dev, uint32_t v_rows, NtsVar& y, uint32_t* arg = nullptr,
                   bool early = false);

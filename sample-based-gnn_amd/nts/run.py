@@ -144,6 +144,9 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.sample_shared and (rng == "mt" or place == "pd"):
         raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_SHARED is not supported with the "
                          "mt19937-stream or PD-cache algorithms (Philox-sampled algorithms only)")
+    if info.feature_f16 and (model == "gat" or place == "pd"):
+        raise SystemExit(f"ALGORITHM {info.algorithm}: FEATURE_F16 is not supported with GAT or "
+                         "PD-cache algorithms (the sum aggregation of GCN / GraphSAGE only)")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -162,7 +165,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         aggregator=info.aggregator, gat_heads=info.gat_heads or None,
         layer_norm=bool(info.layer_norm), gat_attn_drop=info.gat_attn_drop,
         gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2),
-        shared_sampling=bool(info.sample_shared), seed=info.seed)
+        shared_sampling=bool(info.sample_shared), feature_f16=bool(info.feature_f16),
+        seed=info.seed)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
@@ -211,8 +215,10 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
     G = E.FullyRepGraph.from_edges(src, dst, info.vertices)
     n_edges = src.numel()
     del src, dst
+    if info.feature_f16:  # rounded on the host: the fp32 table never reaches the device
+        feats = feats.astype(np.float16)
     feat = torch.from_numpy(feats).to(dev)
-    lab = torch.from_numpy(labels).to(dev)
+    lab =torch.from_numpy(labels).to(dev)
     ids = {k: np.nonzero(masks == v)[0].astype(np.int32) for k, v in
            (("train", dataloader.MASK_TRAIN), ("val", dataloader.MASK_VAL),
             ("test", dataloader.MASK_TEST))}
