@@ -244,6 +244,31 @@ int nts_hip_build_csc(nts_hip_ctx *ctx, const uint32_t *src, const uint32_t *dst
 int nts_hip_sample_layer(nts_hip_ctx *ctx, const nts_graph_dev *graph, int fanout,
                          int layer, uint64_t batch_seq, int rng_mode, int weight_type,
                          nts_sampcsc_dev *out);
+/* The same hop with edge-weighted neighbour selection (DGL
+ * sample_neighbors(prob=), PyG NeighborLoader(weight_attr=)).  edge_prob holds
+ * one fp32 value per edge of `graph` in CSC order, finite and in
+ * [2^-60, 2^60] (the caller checks the range once, at load).  Position p of a
+ * dst d with deg > fanout draws
+ *   x   = word p of the Philox stream (d, layer | 0x40000000, batch_seq),
+ *   u   = ((x >> 9) + 0.5f) * 2^-23      (exact in fp32, inside (0, 1)),
+ *   key = -log2f(u) / edge_prob[beg + p] (fp32),
+ * and d keeps the `fanout` positions with the smallest
+ * (float_as_uint(key) << 32) | p, in CSC order: successive sampling without
+ * replacement with probability proportional to edge_prob (Efraimidis-Spirakis).
+ * Only the draw differs from NTS_RNG_PHILOX: counts (min(deg, fanout)),
+ * frontier, relabel, CSR and the weight_type weights are the same code, and
+ * edge_prob is no aggregation coefficient.  Stateless; any fanout.
+ * NTS_ERR_INVALID, before any write: edge_prob == NULL, out->omit_map set. */
+int nts_hip_sample_layer_weighted(nts_hip_ctx *ctx, const nts_graph_dev *graph,
+                                  const float *edge_prob, int fanout, int layer,
+                                  uint64_t batch_seq, int weight_type, nts_sampcsc_dev *out);
+/* Test and diagnostic entry: the key bits nts_hip_sample_layer_weighted gives
+ * every position of the `v` destinations (device ids):
+ * keys_out[out_offset[i] + p] = float_as_uint(key of position p of
+ * destination[i]), p < deg(destination[i]).  All pointers on the device. */
+int nts_hip_weighted_keys(nts_hip_ctx *ctx, const nts_graph_dev *graph, const float *edge_prob,
+                          const uint32_t *destination, uint32_t v, int layer,
+                          uint64_t batch_seq, uint32_t *keys_out, const uint64_t *out_offset);
 
 /* ---- feature / label movement ------------------------------------------- */
 /* out[i,:] = table[index[i],:] for i < *n (n == NULL: n_cap rows).

@@ -87,6 +87,7 @@ struct SelectArgs {
   uint32_t layer;
   uint64_t batch_seq;
   uint64_t seed;
+  const float* eprob = nullptr;  // weighted selection only: one value per edge, CSC order
 };
 
 // Copy path: all neighbours of dst i in CSC order (coalesced stride).
@@ -402,13 +403,22 @@ __global__ __launch_bounds__(kSelThreads) void k_select_philox_g16(SelectArgs a)
 //   deg >  kShRegMax : four passes of 8-bit digits over a per-wave LDS
 //                      histogram (integer ds_add only), keys recomputed from
 //                      the ids in every pass — no scratch sized by the degrees.
+// The select is written over a key functor key(p, g) -> uint32 of a position p
+// of the list and its source id g; the weighted selection below
+// is the same code with another key.
 constexpr int kShKeys = 16;                             // keys per lane, register path
 constexpr uint32_t kShRegMax = kShKeys * kWave;         // last degree of the register path
 constexpr uint32_t kShLayerBit = 0x80000000u;
 
-__device__ __forceinline__ uint32_t shared_key(const SelectArgs& a, uint32_t s) {
-  return philox_word(a.seed, s, a.layer | kShLayerBit, a.batch_seq, 0u);
-}
+struct SharedKey {  // r(s): the word of the source, whatever its position
+  uint64_t seed, batch_seq;
+  uint32_t layer;
+  __device__ __forceinline__ explicit SharedKey(const SelectArgs& a)
+      : seed(a.seed), batch_seq(a.batch_seq), layer(a.layer | kShLayerBit) {}
+  __device__ __forceinline__ uint32_t operator()(uint32_t, uint32_t s) const {
+    return philox_word(seed, s, layer, batch_seq, 0u);
+  }
+};
 
 // LDS traffic of one wave is ordered; this keeps the compiler from moving
 // accesses across the point and drains the wave's outstanding LDS operations
@@ -439,8 +449,10 @@ struct SharedEmit {
   }
 };
 
+template <typename KeyFn>
 __device__ __forceinline__ void shared_select_regs(const SelectArgs& a, uint32_t i, uint64_t beg,
-                                                   uint32_t deg, uint32_t n, uint32_t c, int lane) {
+                                                   uint32_t deg, uint32_t n, uint32_t c, int lane,
+                                                   const KeyFn& key) {
   const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const uint32_t J = (deg + kWave - 1) / kWave;  // rounds of 64 positions (wave-uniform)
   uint32_t id[kShKeys], r[kShKeys];
@@ -452,7 +464,7 @@ __device__ __forceinline__ void shared_select_regs(const SelectArgs& a, uint32_t
     r[j] = 0u;
     if ((uint32_t)j < J && p < deg) {
       id[j] = a.grows[beg + p];
-      r[j] = shared_key(a, id[j]);
+      r[j] = key(p, id[j]);
       have |= 1u << j;
     }
   }
@@ -482,9 +494,10 @@ __device__ __forceinline__ void shared_select_regs(const SelectArgs& a, uint32_t
       em.round(a, i, c, n, ((have >> j) & 1u) != 0u, r[j], id[j], prefix, k, lt_mask);
 }
 
+template <typename KeyFn>
 __device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t i, uint64_t beg,
                                                    uint32_t deg, uint32_t n, uint32_t c, int lane,
-                                                   uint32_t* hist) {
+                                                   uint32_t* hist, const KeyFn& key) {
   const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   uint4* mine = reinterpret_cast<uint4*>(hist) + lane;  // counters 4 lane .. 4 lane + 3
   uint32_t prefix = 0u, known = 0u, k = n;
@@ -494,7 +507,7 @@ __device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t
     for (uint32_t p0 = 0; p0 < deg; p0 += kWave) {
       const uint32_t p = p0 + (uint32_t)lane;
       if (p < deg) {
-        const uint32_t r = shared_key(a, a.grows[beg + p]);
+        const uint32_t r = key(p, a.grows[beg + p]);
         if ((r & known) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
       }
     }
@@ -536,15 +549,17 @@ __device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t
     uint32_t g = 0u, r = 0u;
     if (p < deg) {
       g = a.grows[beg + p];
-      r = shared_key(a, g);
+      r = key(p, g);
     }
     em.round(a, i, c, n, p < deg, r, g, prefix, k, lt_mask);
   }
 }
 
-// PHILOX_SHARED: one wave per destination, grid-stride.
-__global__ __launch_bounds__(kSelThreads) void k_select_shared(SelectArgs a) {
-  __shared__ __attribute__((aligned(16))) uint32_t hist[kSelWaves][256];
+// One wave per destination, grid-stride: copy, register select or histogram
+// select.  make_key(d, beg) builds the destination's key functor.
+template <typename MakeKey>
+__device__ __forceinline__ void select_by_key(const SelectArgs& a, uint32_t (*hist)[256],
+                                              const MakeKey& make_key) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint32_t v = a.sizes[0];
   const uint32_t nw = gridDim.x * kSelWaves;
@@ -558,11 +573,73 @@ __global__ __launch_bounds__(kSelThreads) void k_select_shared(SelectArgs a) {
     if (n == deg) {
       copy_all(a, i, beg, deg, c, lane);
     } else if (n > 0) {
+      const auto key = make_key(d, beg);
       if (deg <= kShRegMax)
-        shared_select_regs(a, i, beg, deg, n, c, lane);
+        shared_select_regs(a, i, beg, deg, n, c, lane, key);
       else
-        shared_select_hist(a, i, beg, deg, n, c, lane, hist[w]);
+        shared_select_hist(a, i, beg, deg, n, c, lane, hist[w], key);
     }
+  }
+}
+
+// PHILOX_SHARED: one wave per destination, grid-stride.
+__global__ __launch_bounds__(kSelThreads) void k_select_shared(SelectArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[kSelWaves][256];
+  const SharedKey key(a);
+  select_by_key(a, hist, [&](uint32_t, uint64_t) { return key; });
+}
+
+// ---- weighted selection: Efraimidis-Spirakis keys -------------
+// Every edge carries a probability weight w > 0 (eprob, CSC order).  Position
+// p of destination d's list draws
+//   x   = word p of the stream (d, layer | 0x40000000, batch_seq): a domain of
+//         its own, as PHILOX_SHARED's 0x80000000
+//   u   = ((x >> 9) + 0.5) * 2^-23        exact in fp32, strictly inside (0, 1)
+//   key = -log2(u) / w                    an Exp(1) variate (in bits) over w
+// and d keeps the n positions with the smallest (bits(key) << 32) | p: successive
+// sampling without replacement with probability proportional to w.  With w in
+// [2^-60, 2^60] every key is a normal positive float (2^-24.5 / 2^60 .. 24 x 2^60),
+// so the order of the keys is the order of their bit patterns and the radix
+// select above applies unchanged.  The weights are read beside the ids (same
+// index, coalesced); the histogram path recomputes the keys in every pass.
+constexpr uint32_t kWtLayerBit = 0x40000000u;
+
+__device__ __forceinline__ uint32_t weighted_key_bits(uint64_t seed, uint32_t d, uint32_t layer,
+                                                      uint64_t batch_seq, uint32_t p, float w) {
+  const uint32_t x = philox_word(seed, d, layer | kWtLayerBit, batch_seq, p);
+  const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
+  return __float_as_uint(-log2f(u) / w);
+}
+
+struct WeightedKey {
+  uint64_t seed, batch_seq;
+  uint32_t layer, d;
+  const float* w;  // the destination's weights: w[p] belongs to position p
+  __device__ __forceinline__ uint32_t operator()(uint32_t p, uint32_t) const {
+    return weighted_key_bits(seed, d, layer, batch_seq, p, w[p]);
+  }
+};
+
+__global__ __launch_bounds__(kSelThreads) void k_select_weighted(SelectArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t hist[kSelWaves][256];
+  select_by_key(a, hist, [&](uint32_t d, uint64_t beg) {
+    return WeightedKey{a.seed, a.batch_seq, a.layer, d, a.eprob + beg};
+  });
+}
+
+// The key bits of every position of the given destinations (test and
+// diagnostic entry): keys[off[i] + p] for destination i, one wave each.
+__global__ __launch_bounds__(kSelThreads) void k_weighted_keys(
+    const uint64_t* goff, const float* eprob, const uint32_t* dst, uint32_t v, uint64_t seed,
+    uint32_t layer, uint64_t batch_seq, uint32_t* keys, const uint64_t* off) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t nw = gridDim.x * kSelWaves;
+  for (uint32_t i = blockIdx.x * kSelWaves + w; i < v; i += nw) {
+    const uint32_t d = dst[i];
+    const uint64_t beg = goff[d];
+    const uint32_t deg = (uint32_t)(goff[d + 1] - beg);
+    const WeightedKey key{seed, batch_seq, layer, d, eprob + beg};
+    for (uint32_t p = lane; p < deg; p += kWave) keys[off[i] + p] = key(p, 0u);
   }
 }
 
@@ -2091,9 +2168,12 @@ int mt_ring_finish(nts_hip_ctx* ctx, hipStream_t st) {
 
 using namespace nts_hip;
 
-extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanout,
-                                    int layer, uint64_t batch_seq, int rng_mode,
-                                    int weight_type, nts_sampcsc_dev* o) {
+// One hop.  `edge_prob` != nullptr: the weighted selection (k_select_weighted)
+// replaces the draw of rng_mode, which the caller passes as NTS_RNG_PHILOX
+// (stateless); everything around the selection is the same code.
+static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanout, int layer,
+                             uint64_t batch_seq, int rng_mode, int weight_type,
+                             nts_sampcsc_dev* o, const float* edge_prob) {
   NTS_CHECK_ARG(ctx && g && o, "NULL argument");
   NTS_CHECK_ARG(g->column_offset && g->row_indices, "graph not on device");
   NTS_CHECK_ARG((o->destination || o->v_cap == 0) && o->v_size && o->column_offset &&
@@ -2113,7 +2193,7 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
   // info, re-runs); PHILOX and PHILOX_SHARED keep no generator state
   const bool is_mt = rng_mode == NTS_RNG_MT19937_LEMIRE || rng_mode == NTS_RNG_MT19937_DIV;
   // (PHILOX_SHARED selects by key order: no rejection set, any fanout)
-  NTS_CHECK_ARG(rng_mode == NTS_RNG_PHILOX_SHARED || fanout <= (int)kBigFanoutMax,
+  NTS_CHECK_ARG(rng_mode == NTS_RNG_PHILOX_SHARED || edge_prob || fanout <= (int)kBigFanoutMax,
                 "fanout above 16384 (the distinct-position hash set)");
   NTS_CHECK_ARG(!is_mt || fanout <= (int)(kMtTab / 2),
                 "MT19937 modes: fanout above 8192 (the exact path's hash set)");
@@ -2221,7 +2301,11 @@ extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, in
   a.layer = (uint32_t)layer;
   a.batch_seq = batch_seq;
   a.seed = ctx->seed;
-  if (rng_mode == NTS_RNG_PHILOX) {
+  a.eprob = edge_prob;
+  if (edge_prob) {
+    const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves), 4096u));
+    hipLaunchKernelGGL(k_select_weighted, dim3(gs), dim3(kSelThreads), 0, st, a);
+  } else if (rng_mode == NTS_RNG_PHILOX) {
     if (fanout >= 0 && fanout <= kGrp) {
       const uint32_t gs =
           std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves * kGrpPerWave), 4096u));
@@ -2423,6 +2507,41 @@ frontier:
                        o->csr_edge_id, o->sizes_host);
     NTS_LAUNCH_CHECK();
   }
+  return NTS_OK;
+}
+
+extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanout,
+                                    int layer, uint64_t batch_seq, int rng_mode,
+                                    int weight_type, nts_sampcsc_dev* o) {
+  return sample_layer_impl(ctx, g, fanout, layer, batch_seq, rng_mode, weight_type, o, nullptr);
+}
+
+extern "C" int nts_hip_sample_layer_weighted(nts_hip_ctx* ctx, const nts_graph_dev* g,
+                                             const float* edge_prob, int fanout, int layer,
+                                             uint64_t batch_seq, int weight_type,
+                                             nts_sampcsc_dev* o) {
+  NTS_CHECK_ARG(ctx && g && o, "NULL argument");
+  NTS_CHECK_ARG(edge_prob, "edge_prob is NULL");
+  NTS_CHECK_ARG(!o->omit_map, "weighted sampling with omit_map (PD cache) is not supported");
+  return sample_layer_impl(ctx, g, fanout, layer, batch_seq, NTS_RNG_PHILOX, weight_type, o,
+                           edge_prob);
+}
+
+extern "C" int nts_hip_weighted_keys(nts_hip_ctx* ctx, const nts_graph_dev* g,
+                                     const float* edge_prob, const uint32_t* destination,
+                                     uint32_t v, int layer, uint64_t batch_seq, uint32_t* keys_out,
+                                     const uint64_t* out_offset) {
+  NTS_CHECK_ARG(ctx && g, "NULL argument");
+  NTS_CHECK_ARG(g->column_offset && g->row_indices, "graph not on device");
+  NTS_CHECK_ARG(edge_prob, "edge_prob is NULL");
+  NTS_CHECK_ARG(v == 0 || (destination && keys_out && out_offset), "NULL argument");
+  if (v == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const uint32_t gs = std::max(1u, std::min(ceil_div(v, kSelWaves), 4096u));
+  hipLaunchKernelGGL(k_weighted_keys, dim3(gs), dim3(kSelThreads), 0, ctx->stream,
+                     g->column_offset, edge_prob, destination, v, ctx->seed, (uint32_t)layer,
+                     batch_seq, keys_out, out_offset);
+  NTS_LAUNCH_CHECK();
   return NTS_OK;
 }
 

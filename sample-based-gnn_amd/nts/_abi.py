@@ -67,6 +67,7 @@ EXPORTED = (
     "nts_hip_gat_backward_heads_drop", "nts_hip_dropout_f32",
     "nts_hip_gatv2_forward", "nts_hip_gatv2_backward",
     "nts_hip_spmm_csc_fwd_h", "nts_hip_spmm_graph_fwd_h", "nts_hip_gather_rows_h",
+    "nts_hip_sample_layer_weighted", "nts_hip_weighted_keys",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -128,6 +129,10 @@ def lib() -> C.CDLL:
         "nts_hip_degrees": ([P, P, P, U64, U64, P, P], I),
         "nts_hip_build_csc": ([P, P, P, U64, U64, P, P], I),
         "nts_hip_sample_layer": ([P, C.POINTER(GraphDev), I, I, U64, I, I, C.POINTER(SampCSCDev)], I),
+        # edge-weighted neighbour selection: edge_prob after the graph
+        "nts_hip_sample_layer_weighted": ([P, C.POINTER(GraphDev), P, I, I, U64, I,
+                                           C.POINTER(SampCSCDev)], I),
+        "nts_hip_weighted_keys": ([P, C.POINTER(GraphDev), P, P, U32, I, U64, P, P], I),
         "nts_hip_gather_rows": ([P, P, U64, P, P, U32, U32, P, U64], I),
         "nts_hip_gather_labels": ([P, P, P, P, U32, P], I),
         "nts_hip_spmm_csc_fwd": ([P, P, P, P, P, U32, P, U64, P, U32, P, U64], I),

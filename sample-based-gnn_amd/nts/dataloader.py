@@ -10,6 +10,8 @@
   vertices keep the memset(…,1) pattern (core/ntsDataloador.hpp:191) = 0x01010101.
 * FEATURE_FILE:random (core/ntsDataloador.hpp:835-861): all-ones features,
   rand() % C labels, masks 65/10/25 % by vertex id.
+* Edge weight file (EDGE_WEIGHT_FILE, this build's key): raw little-endian
+  fp32 [E], value i the sampling weight of edge i of the edge file.
 * Config: KEY:VALUE lines, `#` comments (InputInfo::readFromCfgFile,
   core/GraphSegment.cpp:222-347).
 """
@@ -19,6 +21,7 @@ import ctypes as C
 import io
 import os
 import pathlib
+import sys
 import tempfile
 import zipfile
 from dataclasses import dataclass, field
@@ -110,6 +113,53 @@ def write_edge_file(path, src: np.ndarray, dst: np.ndarray) -> None:
     e[:, 0] = src
     e[:, 1] = dst
     e.tofile(path)
+
+
+# EDGE_WEIGHT_FILE (this build's key): raw little-endian fp32 [E]; value i is
+# the sampling weight of edge i of EDGE_FILE (SAMPLE_WEIGHTED)
+def write_edge_weight_file(path, weights: np.ndarray) -> None:
+    np.ascontiguousarray(weights, dtype="<f4").tofile(path)
+
+
+def _edge_weight_count(path, n_edges: int) -> None:
+    size = os.path.getsize(path)
+    if size != 4 * n_edges:
+        raise ValueError(f"{path}: {size} bytes, expected {4 * n_edges} (one little-endian fp32 "
+                         f"per edge of the edge file, {n_edges} edges)")
+
+
+def read_edge_weights(path, n_edges: int) -> np.ndarray:
+    """The weights of an EDGE_WEIGHT_FILE for an edge file of `n_edges` edges
+    (any other size is refused)."""
+    _edge_weight_count(path, n_edges)
+    return np.fromfile(path, dtype="<f4").astype(np.float32, copy=False)
+
+
+def load_edge_weights_to_device(path, n_edges: int, device, chunk: int = 1 << 26):
+    """read_edge_weights straight into a float32 device tensor, in chunks of
+    `chunk` values through pinned staging buffers (as load_edges_to_device)."""
+    import torch
+    _edge_weight_count(path, n_edges)
+    w = torch.empty(n_edges, dtype=torch.float32, device=device)
+    stage = [torch.empty(min(chunk, max(n_edges, 1)), dtype=torch.float32).pin_memory()
+             for _ in range(2)]
+    ev = [None, None]
+    with open(path, "rb") as f:
+        for i, first in enumerate(range(0, n_edges, chunk)):
+            n = min(chunk, n_edges - first)
+            buf = stage[i % 2]
+            if ev[i % 2] is not None:
+                ev[i % 2].synchronize()  # the previous copy out of this buffer is done
+            got = f.readinto(memoryview(buf[:n].numpy().view(np.uint8)))
+            if got != 4 * n:
+                raise ValueError(f"{path}: short read at value {first}")
+            if sys.byteorder != "little":
+                buf[:n].numpy().byteswap(inplace=True)
+            w[first:first + n].copy_(buf[:n], non_blocking=True)
+            ev[i % 2] = torch.cuda.Event()
+            ev[i % 2].record()
+    torch.cuda.synchronize(device)
+    return w
 
 
 def _text(path) -> str:
@@ -344,6 +394,15 @@ class InputInfo:
     # fp32 (f16 storage, fp32 arithmetic).  GCN / GraphSAGE algorithms with the
     # sum aggregator, without PD cache or root weight
     feature_f16: int = 0
+    # EDGE_WEIGHT_FILE (this build's key): raw little-endian fp32 [E], value i
+    # the sampling weight of edge i of EDGE_FILE (finite, in [2^-60, 2^60])
+    edge_weight_file: str = ""
+    # SAMPLE_WEIGHTED (this build's key): 1 = a destination with more
+    # neighbours than its fanout keeps FANOUT of them with probability
+    # proportional to the edge weights (successive sampling without
+    # replacement).  Needs EDGE_WEIGHT_FILE; Philox-sampled algorithms without
+    # PD cache; not with SAMPLE_SHARED
+    sample_weighted: int = 0
     # SEED (this build's key): the driver's seed (sampler streams, dropout)
     seed: int = 2000
     extra: dict = field(default_factory=dict)
@@ -381,6 +440,8 @@ class InputInfo:
             "GAT_V2": ("gat_v2", int),
             "SAMPLE_SHARED": ("sample_shared", int),
             "FEATURE_F16": ("feature_f16", int),
+            "EDGE_WEIGHT_FILE": ("edge_weight_file", str),
+            "SAMPLE_WEIGHTED": ("sample_weighted", int),
             "SEED": ("seed", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():

@@ -76,11 +76,31 @@ class HipContext:
 
     # ---- sampler -------------------------------------------------------------
     def sample_layer(self, graph: "DeviceGraph", lay: "LayerBuffers", fanout: int, layer: int,
-                     batch_seq: int, rng_mode: int, weight_type: int):
+                     batch_seq: int, rng_mode: int, weight_type: int, edge_prob=None):
+        """`edge_prob` (float32 [E], CSC order): edge-weighted selection
+        (nts_hip_sample_layer_weighted); rng_mode is then not read."""
         g = graph.as_struct()
         o = lay.as_struct()
+        if edge_prob is not None:
+            assert edge_prob.dtype == torch.float32 and edge_prob.numel() == graph.n_edges
+            check(self.lib.nts_hip_sample_layer_weighted(self.h, C.byref(g), ptr(edge_prob), fanout,
+                                                         layer, batch_seq, weight_type, C.byref(o)))
+            return
         check(self.lib.nts_hip_sample_layer(self.h, C.byref(g), fanout, layer, batch_seq,
                                             rng_mode, weight_type, C.byref(o)))
+
+    def weighted_keys(self, graph: "DeviceGraph", edge_prob, destination, layer: int,
+                      batch_seq: int, out_offset):
+        """Test and diagnostic entry: the fp32 key bits (uint32, as int32) of
+        every position of the given destinations; out_offset int64 [v]."""
+        g = graph.as_struct()
+        deg = (graph.column_offset[destination.long() + 1] - graph.column_offset[destination.long()])
+        total = int((out_offset + deg).max().item()) if destination.numel() else 0
+        keys = _u32(max(total, 1), destination.device)
+        check(self.lib.nts_hip_weighted_keys(self.h, C.byref(g), ptr(edge_prob), ptr(destination),
+                                             destination.numel(), layer, batch_seq, ptr(keys),
+                                             ptr(out_offset)))
+        return keys[:total]
 
     # ---- movement / aggregation ------------------------------------------------
     def gather_rows(self, table, index, n_dev, n_cap, out):

@@ -85,7 +85,15 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gemm="split3", overlap_allreduce=-1, pair_table=0, sample_gpu=False,
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
-               gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False):
+               gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False,
+               weighted_sampling=False):
+    if weighted_sampling:  # neighbours drawn in proportion to the graph's edge_prob
+        if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
+            raise ValueError("weighted_sampling is not supported with an MT19937 rng_mode (it "
+                             "draws from a Philox stream of its own)")
+        if shared_sampling or int(rng_mode) == _abi.NTS_RNG_PHILOX_SHARED:
+            raise ValueError("weighted_sampling is not supported with shared_sampling "
+                             "(rng_mode NTS_RNG_PHILOX_SHARED)")
     if shared_sampling:  # one variate per source vertex
         if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
             raise ValueError("shared_sampling is not supported with an MT19937 rng_mode (it "
@@ -142,6 +150,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
         c.gat_v2 = True
     if feature_f16:  # f16 feature table; the default leaves the field as constructed
         c.feature_f16 = True
+    if weighted_sampling:  # (the default leaves the field as constructed)
+        c.weighted_sampling = True
     c.pd_cache = bool(pd_cache)
     c.pd_rate = float(pd_rate)
     c.pd_super_batch = int(pd_super_batch)

@@ -54,12 +54,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::class_<FullyRepGraph, std::shared_ptr<FullyRepGraph>>(m, "FullyRepGraph")
       .def_static(
           "from_edges",
-          [](const torch::Tensor& src, const torch::Tensor& dst, VertexId V) {
+          [](const torch::Tensor& src, const torch::Tensor& dst, VertexId V,
+             std::optional<torch::Tensor> edge_weight) {
             NtsStream cs(src.device().index(), nullptr, 2000);
-            return FullyRepGraph::from_edges(cs, src, dst, V);
+            return FullyRepGraph::from_edges(cs, src, dst, V,
+                                             edge_weight ? *edge_weight : torch::Tensor());
           },
-          py::arg("src"), py::arg("dst"), py::arg("vertices"))
-      .def_static("from_csc", &FullyRepGraph::from_csc)
+          py::arg("src"), py::arg("dst"), py::arg("vertices"),
+          py::arg("edge_weight") = py::none())
+      .def_static(
+          "from_csc",
+          [](torch::Tensor column_offset, torch::Tensor row_indices, torch::Tensor in_degree,
+             torch::Tensor out_degree, std::optional<torch::Tensor> edge_prob) {
+            return FullyRepGraph::from_csc(column_offset, row_indices, in_degree, out_degree,
+                                           edge_prob ? *edge_prob : torch::Tensor());
+          },
+          py::arg("column_offset"), py::arg("row_indices"), py::arg("in_degree"),
+          py::arg("out_degree"), py::arg("edge_prob") = py::none())
+      // the edges' sampling weights in CSC order (None: the graph has none)
+      .def_property_readonly("edge_prob",
+                             [](const FullyRepGraph& g) -> py::object {
+                               if (!g.edge_prob.defined()) return py::none();
+                               return py::cast(g.edge_prob);
+                             })
       .def_readonly("global_vertices", &FullyRepGraph::global_vertices)
       .def_readonly("global_edges", &FullyRepGraph::global_edges)
       .def_readonly("column_offset", &FullyRepGraph::column_offset)
@@ -75,7 +92,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::class_<PySampler>(m, "FastSampler")
       .def(py::init([](std::shared_ptr<FullyRepGraph> g, const torch::Tensor& seeds, int layers,
                        int batch, std::vector<int> fanout, int rng_mode, uint64_t seed,
-                       bool csr, int pipeline) {
+                       bool csr, int pipeline, bool weighted) {
+             TORCH_CHECK(!weighted || g->edge_prob.defined(),
+                         "weighted: the graph has no edge_prob");
              auto p = new PySampler();
              TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
              p->cs = std::make_unique<NtsStream>(g->device, nullptr, seed);
@@ -84,11 +103,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              p->s = std::make_unique<FastSampler>(g, to_ids(seeds), layers, batch, fanout, pipeline,
                                                   c, true);
              p->s->rng_mode = rng_mode;
+             p->s->weighted = weighted;
              return p;
            }),
            py::arg("graph"), py::arg("seeds"), py::arg("layers"), py::arg("batch_size"),
            py::arg("fanout"), py::arg("rng_mode") = (int)NTS_RNG_PHILOX, py::arg("seed") = 2000,
-           py::arg("csr") = true, py::arg("pipeline") = 1)
+           py::arg("csr") = true, py::arg("pipeline") = 1, py::arg("weighted") = false)
       // the split form (several slots in flight, finished in issue order)
       .def("issue",
            [](PySampler& p, int batch, int slot, WeightType w) {
@@ -142,11 +162,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       "sampler_throughput",
       [](std::shared_ptr<FullyRepGraph> g, const torch::Tensor& seeds, int batch,
          std::vector<int> fanout, WeightType w, int rng_mode, int n_batches,
-         std::vector<bool> csr) {
+         std::vector<bool> csr, bool weighted) {
         SamplerRate r;
         {
           py::gil_scoped_release nogil;
-          r = sampler_throughput(g, to_ids(seeds), batch, fanout, w, rng_mode, n_batches, csr);
+          r = sampler_throughput(g, to_ids(seeds), batch, fanout, w, rng_mode, n_batches, csr, weighted);
         }
         py::dict d;
         d["seconds"] = r.seconds;
@@ -156,7 +176,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       },
       py::arg("graph"), py::arg("seeds"), py::arg("batch_size"), py::arg("fanout"),
       py::arg("weight_type") = WeightType::Sum, py::arg("rng_mode") = (int)NTS_RNG_PHILOX,
-      py::arg("n_batches") = 16, py::arg("csr_layers") = std::vector<bool>());
+      py::arg("n_batches") = 16, py::arg("csr_layers") = std::vector<bool>(),
+      py::arg("weighted") = false);
 
   py::class_<Communicator, std::shared_ptr<Communicator>>(m, "Communicator")
       .def(py::init([](int n, int r, py::bytes uid, int dev) {
@@ -236,6 +257,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("layer_norm", &GCNConfig::layer_norm)
       .def_readwrite("layer_norm_eps", &GCNConfig::layer_norm_eps)
       .def_readwrite("feature_f16", &GCNConfig::feature_f16)
+      .def_readwrite("weighted_sampling", &GCNConfig::weighted_sampling)
       .def_readwrite("sampler_cus", &GCNConfig::sampler_cus)
       .def_readwrite("sampler_gate", &GCNConfig::sampler_gate)
       .def_readwrite("pad_features", &GCNConfig::pad_features)

@@ -99,9 +99,36 @@ void NtsStream::synchronize() const {
 }
 
 // ---------------------------------------------------------------------------
+// The sampling weights of a graph, checked once at load: float32 [E] on the
+// graph's device, every value finite and in [2^-60, 2^60] (the range keeps
+// every selection key a normal positive float).  The check runs on
+// the device and is read once; `name` is the caller's argument.
+static torch::Tensor checked_edge_prob(const torch::Tensor& w, uint64_t edges, int device,
+                                       const char* name) {
+  TORCH_CHECK(w.is_cuda() && w.device().index() == device && w.dtype() == torch::kFloat32 &&
+                  w.dim() == 1 && (uint64_t)w.numel() == edges,
+              name, ": a float32 CUDA tensor with one value per edge (", edges, "), got ",
+              w.numel(), " value(s) of ", w.dtype());
+  auto p = w.contiguous();
+  if (edges == 0) return p;
+  const float lo = 0x1p-60f, hi = 0x1p60f;
+  // (a NaN fails both comparisons; +-inf fail one of them)
+  const auto bad = torch::logical_not(torch::logical_and(p >= lo, p <= hi));
+  const auto first = bad.to(torch::kInt32).argmax();
+  const auto rep = torch::stack({bad.sum().to(torch::kFloat64), first.to(torch::kFloat64),
+                                 p.index_select(0, first.reshape({1}))[0].to(torch::kFloat64)})
+                       .cpu();
+  const int64_t n = (int64_t)rep[0].item<double>();
+  TORCH_CHECK(n == 0, name, ": ", n, " value(s) are not finite and in [2^-60, 2^60] (zero, "
+              "negative, NaN, inf and out-of-range weights are refused); the first is edge ",
+              (int64_t)rep[1].item<double>(), " with value ", rep[2].item<double>());
+  return p;
+}
+
 std::shared_ptr<FullyRepGraph> FullyRepGraph::from_edges(NtsStream& cs, const torch::Tensor& src,
                                                          const torch::Tensor& dst,
-                                                         VertexId vertices) {
+                                                         VertexId vertices,
+                                                         const torch::Tensor& edge_weight) {
   TORCH_CHECK(src.is_cuda() && dst.is_cuda() && src.dtype() == torch::kInt32 &&
                   dst.dtype() == torch::kInt32 && src.numel() == dst.numel(),
               "from_edges: src/dst must be int32 CUDA tensors of equal length");
@@ -124,6 +151,14 @@ std::shared_ptr<FullyRepGraph> FullyRepGraph::from_edges(NtsStream& cs, const to
   hip_check(nts_hip_degrees(cs.ctx(), dptr<uint32_t>(s), dptr<uint32_t>(d), g->global_edges,
                             vertices, dptr<uint32_t>(g->out_degree), dptr<uint32_t>(g->in_degree)),
             "nts_hip_degrees");
+  if (edge_weight.defined()) {
+    // file edge i -> its CSC position: nts_hip_build_csc keeps the file order
+    // within a destination, which is the stable order by destination (load
+    // time: a libtorch sort is enough)
+    const auto w = checked_edge_prob(edge_weight, g->global_edges, g->device, "edge_weight");
+    const auto key = d.to(torch::kInt64).bitwise_and(0xFFFFFFFFll);  // ids are uint32
+    g->edge_prob = w.index_select(0, torch::argsort(key, /*stable=*/true, 0, false));
+  }
   cs.synchronize();
   return g;
 }
@@ -131,7 +166,8 @@ std::shared_ptr<FullyRepGraph> FullyRepGraph::from_edges(NtsStream& cs, const to
 std::shared_ptr<FullyRepGraph> FullyRepGraph::from_csc(torch::Tensor column_offset,
                                                        torch::Tensor row_indices,
                                                        torch::Tensor in_degree,
-                                                       torch::Tensor out_degree) {
+                                                       torch::Tensor out_degree,
+                                                       torch::Tensor edge_prob) {
   auto g = std::make_shared<FullyRepGraph>();
   TORCH_CHECK(column_offset.dtype() == torch::kInt64 && row_indices.dtype() == torch::kInt32,
               "from_csc: column_offset int64, row_indices int32");
@@ -142,6 +178,8 @@ std::shared_ptr<FullyRepGraph> FullyRepGraph::from_csc(torch::Tensor column_offs
   g->row_indices = row_indices.contiguous();
   g->in_degree = in_degree.contiguous();
   g->out_degree = out_degree.contiguous();
+  if (edge_prob.defined())
+    g->edge_prob = checked_edge_prob(edge_prob, g->global_edges, g->device, "edge_prob");
   return g;
 }
 
@@ -375,8 +413,13 @@ void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
       o.omit_row = dptr<uint32_t>(s->omit_row);
     }
     const double tl = now_s();
-    hip_check(nts_hip_sample_layer(cs.ctx(), &g, fanout[l], l, bseq, rng_mode, wt, &o),
-              "nts_hip_sample_layer");
+    if (weighted)
+      hip_check(nts_hip_sample_layer_weighted(cs.ctx(), &g, dptr<float>(whole_graph->edge_prob),
+                                              fanout[l], l, bseq, wt, &o),
+                "nts_hip_sample_layer_weighted");
+    else
+      hip_check(nts_hip_sample_layer(cs.ctx(), &g, fanout[l], l, bseq, rng_mode, wt, &o),
+                "nts_hip_sample_layer");
     if (host_profile()) fprintf(stderr, "[host] sample_layer %d: %.1f us\n", l, (now_s() - tl) * 1e6);
     // the reference keeps the destination as a view of the previous source
     if (l == 0)

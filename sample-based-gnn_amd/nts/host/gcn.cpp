@@ -245,6 +245,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                                           nslots_, csr, sample_weight() != WeightType::None,
                                           cfg.gat || cfg.root_weight, max_aggr());
   sampler->rng_mode = cfg.rng_mode;
+  sampler->weighted = cfg.weighted_sampling;  // (its refusals follow every other option's below)
   sampler->up_degree = cfg.up_degree;
   if (cfg.root_weight)  // the inverse of dst_local_id, for every hop with a graph-op backward
     for (auto* q : sampler->ssgs)
@@ -299,6 +300,19 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     for (const auto& c : conflicts)
       TORCH_CHECK(!c.first, "feature_f16 is not supported with ", c.second);
     F = half_feature_table(F, graph->device);
+  }
+  if (cfg.weighted_sampling) {  // (after every other option's refusals)
+    TORCH_CHECK(graph->edge_prob.defined(),
+                "weighted_sampling needs a graph with edge_prob (from_edges(..., edge_weight) or "
+                "from_csc(..., edge_prob))");
+    TORCH_CHECK(!is_mt_mode(cfg.rng_mode), "weighted_sampling is not supported with an MT19937 "
+                "rng_mode (it draws from a Philox stream of its own)");
+    TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX_SHARED,
+                "weighted_sampling is not supported with rng_mode NTS_RNG_PHILOX_SHARED "
+                "(shared_sampling)");
+    TORCH_CHECK(!cfg.pd_cache, "weighted_sampling is not supported with pd_cache");
+    TORCH_CHECK(!cfg.sample_gpu, "weighted_sampling is not supported with sample_gpu (the "
+                                 "reference's mt19937 stream)");
   }
   for (int i = 0; i < nslots_; ++i) {
     TORCH_CHECK(hipEventCreateWithFlags(&ready_[i], hipEventDisableTiming) == hipSuccess,
@@ -911,6 +925,7 @@ std::unique_ptr<FastSampler> GCN_SAMPLE_ALLGPU_impl::eval_sampler(const std::vec
                                          sample_weight() != WeightType::None,
                                          cfg.gat || cfg.root_weight);
   s->rng_mode = cfg.rng_mode;
+  s->weighted = cfg.weighted_sampling;
   s->up_degree = cfg.up_degree;
   s->batch_seq = batch_seq;
   return s;
@@ -1407,7 +1422,9 @@ void GCN_SAMPLE_ALLGPU_impl::reset_stats() {
 
 SamplerRate sampler_throughput(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& seeds,
                                int batch_size, const std::vector<int>& fanout, WeightType w,
-                               int rng_mode, int n_batches, const std::vector<bool>& csr_layers) {
+                               int rng_mode, int n_batches, const std::vector<bool>& csr_layers,
+                               bool weighted) {
+  TORCH_CHECK(!weighted || g->edge_prob.defined(), "weighted: the graph has no edge_prob");
   constexpr int kS = 3;
   TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
   NtsStream st(g->device, nullptr, 2000);
@@ -1415,6 +1432,7 @@ SamplerRate sampler_throughput(std::shared_ptr<FullyRepGraph> g, const std::vect
   const int L = (int)fanout.size();
   FastSampler s(g, seeds, L, batch_size, fanout, kS, csr_layers, w != WeightType::None, false);
   s.rng_mode = rng_mode;
+  s.weighted = weighted;
   uint64_t items = g->global_vertices;
   for (auto* x : s.ssg->sampled_sgs) items = std::max<uint64_t>({items, x->e_cap, x->v_cap});
   hip_check(nts_hip_ctx_reserve(st.ctx(), g->global_vertices, items), "nts_hip_ctx_reserve");

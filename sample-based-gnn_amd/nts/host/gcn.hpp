@@ -106,6 +106,16 @@ struct GCNConfig {
   // pd_cache, transform_first = 1, pair_table > 0, cache_rate >= 0,
   // root_weight or aggregator = max.
   bool feature_f16 = false;
+  // Edge-weighted neighbour selection (DGL prob=, PyG
+  // weight_attr=): a destination with more neighbours than its fanout keeps
+  // `fanout` of them by successive sampling without replacement with
+  // probability proportional to the graph's edge_prob (Efraimidis-Spirakis
+  // keys on a Philox stream of their own).  Only the draw changes: counts,
+  // frontier, CSR and the weight_type weights are the default sampler's, and
+  // edge_prob is no aggregation coefficient.  Every sampler the driver builds
+  // (training, evaluate, forward_eval) uses it.  Needs a graph with edge_prob;
+  // not with an MT19937 rng_mode, NTS_RNG_PHILOX_SHARED, pd_cache or sample_gpu.
+  bool weighted_sampling = false;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its
@@ -173,7 +183,8 @@ struct SamplerRate {
 };
 SamplerRate sampler_throughput(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& seeds,
                                int batch_size, const std::vector<int>& fanout, WeightType w,
-                               int rng_mode, int n_batches, const std::vector<bool>& csr_layers);
+                               int rng_mode, int n_batches, const std::vector<bool>& csr_layers,
+                               bool weighted = false);
 
 class GCN_SAMPLE_ALLGPU_impl {
  public:

@@ -98,15 +98,22 @@ class FullyRepGraph {
   torch::Tensor row_indices;    // int32 [E]
   torch::Tensor in_degree;      // int32 [V]  in_degree_for_backward
   torch::Tensor out_degree;     // int32 [V]  out_degree_for_backward
+  // float32 [E] in CSC order, or undefined: the edges' sampling weights
+  // (weighted_sampling), every value finite and in [2^-60, 2^60]
+  torch::Tensor edge_prob;
 
   // GenerateAll/ReadRepGraphFromRawFile from an edge list already on the device
   // (src/dst int32 tensors in file order), degrees from the same list.
+  // edge_weight (optional, float32 [E]): value i belongs to file edge i and is
+  // moved to that edge's CSC position (edge_prob).
   static std::shared_ptr<FullyRepGraph> from_edges(NtsStream& cs, const torch::Tensor& src,
-                                                   const torch::Tensor& dst, VertexId vertices);
-  // Wrap an existing device CSC (+ degrees).
+                                                   const torch::Tensor& dst, VertexId vertices,
+                                                   const torch::Tensor& edge_weight = {});
+  // Wrap an existing device CSC (+ degrees, + edge_prob in CSC order).
   static std::shared_ptr<FullyRepGraph> from_csc(torch::Tensor column_offset,
                                                  torch::Tensor row_indices,
-                                                 torch::Tensor in_degree, torch::Tensor out_degree);
+                                                 torch::Tensor in_degree, torch::Tensor out_degree,
+                                                 torch::Tensor edge_prob = {});
   nts_graph_dev dev() const;
 };
 
@@ -245,6 +252,9 @@ class FastSampler {
   SampledSubgraph* ssg = nullptr;
   std::vector<SampledSubgraph*> ssgs;
   int rng_mode = NTS_RNG_PHILOX;
+  // edge-weighted selection (nts_hip_sample_layer_weighted with
+  // whole_graph->edge_prob) in place of rng_mode's draw
+  bool weighted = false;
   bool up_degree = false;  // UP_DEGREE: weights from each sampled layer's own degrees
   uint64_t batch_seq = 0;  // keys the PHILOX / PHILOX_SHARED streams (one per sampled batch)
   // sample_gpu_fast_omit (core/ntsFastSampler.hpp:711-915): when set, the

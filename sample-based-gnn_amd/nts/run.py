@@ -43,6 +43,13 @@ destination of a hop (fixed-size layer-neighbour sampling): each destination's
 set keeps its distribution, the hop's frontier shrinks.  SEED:n sets the
 driver's seed (default 2000).
 
+EDGE_WEIGHT_FILE:path / SAMPLE_WEIGHTED:1 (Philox-sampled algorithms without PD
+cache, not with SAMPLE_SHARED): the file holds one little-endian fp32 per edge
+of EDGE_FILE (finite, in [2^-60, 2^60]); a destination with more neighbours
+than its fanout then keeps FANOUT of them with probability proportional to
+these weights (successive sampling without replacement).  The weights choose
+the neighbours only; the aggregation's coefficients do not change.
+
 GAT_ATTN_DROP:0.6 / GAT_FEAT_DROP:0.6 (GAT algorithms): dropout of the attention
 coefficients and of every layer's input while training, fused into the GAT
 kernels.  DROP_RATE is not read by a GAT job (as in the reference).
@@ -147,6 +154,17 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     if info.feature_f16 and (model == "gat" or place == "pd"):
         raise SystemExit(f"ALGORITHM {info.algorithm}: FEATURE_F16 is not supported with GAT or "
                          "PD-cache algorithms (the sum aggregation of GCN / GraphSAGE only)")
+    if info.sample_weighted:
+        if not info.edge_weight_file:
+            raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_WEIGHTED is not supported "
+                             "without an EDGE_WEIGHT_FILE (one fp32 weight per edge)")
+        if rng == "mt" or place == "pd":
+            raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_WEIGHTED is not supported with "
+                             "the mt19937-stream or PD-cache algorithms (Philox-sampled "
+                             "algorithms only)")
+        if info.sample_shared:
+            raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_WEIGHTED is not supported with "
+                             "SAMPLE_SHARED:1 (one selection rule per job)")
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -166,7 +184,7 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         layer_norm=bool(info.layer_norm), gat_attn_drop=info.gat_attn_drop,
         gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2),
         shared_sampling=bool(info.sample_shared), feature_f16=bool(info.feature_f16),
-        seed=info.seed)
+        weighted_sampling=bool(info.sample_weighted), seed=info.seed)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
@@ -212,8 +230,13 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
     E = host.ext()
     t0 = time.time()
     src, dst, feats, labels, masks = load_inputs(info, base, n_classes, device=dev)
-    G = E.FullyRepGraph.from_edges(src, dst, info.vertices)
     n_edges = src.numel()
+    edge_w = None
+    if info.edge_weight_file:  # value i belongs to edge i of the edge file
+        edge_w = dataloader.load_edge_weights_to_device(_path(base, info.edge_weight_file),
+                                                        n_edges, dev)
+    G = E.FullyRepGraph.from_edges(src, dst, info.vertices, edge_w)
+    del edge_w
     del src, dst
     if info.feature_f16:  # rounded on the host: the fp32 table never reaches the device
         feats = feats.astype(np.float16)
