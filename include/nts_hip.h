@@ -256,12 +256,35 @@ int nts_hip_sample_layer(nts_hip_ctx *ctx, const nts_graph_dev *graph, int fanou
  * (float_as_uint(key) << 32) | p, in CSC order: successive sampling without
  * replacement with probability proportional to edge_prob (Efraimidis-Spirakis).
  * Only the draw differs from NTS_RNG_PHILOX: counts (min(deg, fanout)),
- * frontier, relabel, CSR and the weight_type weights are the same code, and
- * edge_prob is no aggregation coefficient.  Stateless; any fanout.
+ * frontier, relabel, CSR and the weight_type weights are the same code; this
+ * entry does not use edge_prob as an aggregation coefficient
+ * (nts_hip_sample_layer_coef does).  Stateless; any fanout.
  * NTS_ERR_INVALID, before any write: edge_prob == NULL, out->omit_map set. */
 int nts_hip_sample_layer_weighted(nts_hip_ctx *ctx, const nts_graph_dev *graph,
                                   const float *edge_prob, int fanout, int layer,
                                   uint64_t batch_seq, int weight_type, nts_sampcsc_dev *out);
+/* The same hop with per-edge aggregation coefficients (DGL
+ * GraphConv(edge_weight=), PyG GCNConv(x, edge_index, edge_weight)): the
+ * sampled convolution becomes Y[d] = sum_e c(e) a_e X[src(e)].  edge_coef holds
+ * one fp32 value per edge of `graph` in CSC order.  The draw is today's:
+ * edge_prob == NULL: nts_hip_sample_layer's with rng_mode NTS_RNG_PHILOX or
+ * NTS_RNG_PHILOX_SHARED; edge_prob != NULL: nts_hip_sample_layer_weighted's
+ * (rng_mode must then be NTS_RNG_PHILOX).  Counts, sample_ans, edge_dst,
+ * frontier, relabel, CSR, csr_edge_id and sizes are the same code and bits.
+ *   edge_weight_forward[k] = fl32(c(e_k) * edge_coef[q_k])
+ * with q_k the CSC position of kept edge k in `graph` and c the weight_type
+ * weight, fully formed (the MEAN / MEAN_SAMPLED division included) before the
+ * one fp32 multiply.  Under NTS_WEIGHT_NONE the array is built all the same and
+ * holds edge_coef[q_k] itself (a caller's own normalisation).
+ * edge_weight_backward, where asked for, holds the same values in CSR order,
+ * under NONE too.
+ * NTS_ERR_INVALID, before any write: edge_coef == NULL, an MT19937 rng_mode,
+ * the NTS_WEIGHT_UP_DEGREE bit, out->omit_map set, edge_prob != NULL with
+ * NTS_RNG_PHILOX_SHARED, out->edge_weight_forward == NULL. */
+int nts_hip_sample_layer_coef(nts_hip_ctx *ctx, const nts_graph_dev *graph,
+                              const float *edge_prob, const float *edge_coef, int fanout,
+                              int layer, uint64_t batch_seq, int rng_mode, int weight_type,
+                              nts_sampcsc_dev *out);
 /* Test and diagnostic entry: the key bits nts_hip_sample_layer_weighted gives
  * every position of the `v` destinations (device ids):
  * keys_out[out_offset[i] + p] = float_as_uint(key of position p of
@@ -344,6 +367,16 @@ int nts_hip_spmm_graph_fwd(nts_hip_ctx *ctx, const nts_graph_dev *graph,
                            uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
                            const float *x, uint64_t ldx, uint32_t feature_size,
                            float *y, uint64_t ldy);
+/* nts_hip_spmm_graph_fwd with per-edge coefficients: edge e uses
+ * fl32(w(e) * edge_coef[e]), edge_coef one fp32 per edge of `graph` in CSC
+ * order (under NTS_WEIGHT_NONE: edge_coef[e] itself).  The same contract
+ * otherwise: order, hub columns by column slice, scratch, refused weight
+ * types.  On the same destinations it gives, bit for bit, what
+ * nts_hip_sample_layer_coef(fanout = -1) + nts_hip_spmm_csc_fwd give. */
+int nts_hip_spmm_graph_fwd_coef(nts_hip_ctx *ctx, const nts_graph_dev *graph,
+                                const float *edge_coef, uint64_t v_begin, uint64_t v_end,
+                                int weight_type, int relu, const float *x, uint64_t ldx,
+                                uint32_t feature_size, float *y, uint64_t ldy);
 /* ---- f16 feature table (csrc/agghalf.hip; GCNConfig::feature_f16) ---------
  * The three gathers that read the feature table, over a table stored as IEEE
  * half: f16 storage, fp32 arithmetic.  xh / tableh hold the bits of the halves
@@ -376,6 +409,11 @@ int nts_hip_spmm_graph_fwd_h(nts_hip_ctx *ctx, const nts_graph_dev *graph,
                              uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
                              const uint16_t *xh, uint64_t ldxh, uint32_t feature_size,
                              float *y, uint64_t ldy);
+/* nts_hip_spmm_graph_fwd_coef over a half table. */
+int nts_hip_spmm_graph_fwd_coef_h(nts_hip_ctx *ctx, const nts_graph_dev *graph,
+                                  const float *edge_coef, uint64_t v_begin, uint64_t v_end,
+                                  int weight_type, int relu, const uint16_t *xh, uint64_t ldxh,
+                                  uint32_t feature_size, float *y, uint64_t ldy);
 /* out[i,:] = float(tableh[index[i],:]) for i < *n (n == NULL: n_cap rows):
  * nts_hip_gather_rows from a half table into fp32 rows. */
 int nts_hip_gather_rows_h(nts_hip_ctx *ctx, const uint16_t *tableh, uint64_t ld_table,

@@ -202,6 +202,7 @@ __global__ __launch_bounds__(kAggThreads) void k_gather_rows_h(
 }
 
 struct GraphAggH {
+  static constexpr bool kCoef = false;
   const uint64_t* co;      // [V+1] global CSC offsets
   const uint32_t* ri;      // [E] global src ids
   const float* so;         // [V] degree_sqrt(out_degree)   (weight_type != NONE)
@@ -221,13 +222,18 @@ struct GraphAggH {
   const uint32_t* hubs_n;
 };
 
+// nts_hip_spmm_graph_fwd_coef_h: GraphAggCoef (infer.hip) over the half table
+struct GraphAggCoefH : GraphAggH {
+  static constexpr bool kCoef = true;
+  const float* ec;         // [E] per-edge coefficient, CSC order
+};
+
 // graph_row_slice (infer.hip) over half rows: one (row d, column slice) item on
 // the calling LPD-lane group, vector column `col` of the row (col >= nv: an
 // idle lane, it still takes part in the shuffles).  The weights and the edge
 // walk are that function's, on both sides of the hub switch.
-template <int HV, int LPD>
-__device__ __forceinline__ void graph_row_slice_h(const GraphAggH& a, uint64_t d, uint32_t col,
-                                                  int sl) {
+template <int HV, int LPD, typename A>
+__device__ __forceinline__ void graph_row_slice_h(const A& a, uint64_t d, uint32_t col, int sl) {
   using T = typename HT<HV>::T;
   const uint64_t beg = a.co[d], end = a.co[d + 1];
   const bool weighted = a.weight_type != NTS_WEIGHT_NONE;
@@ -248,6 +254,7 @@ __device__ __forceinline__ void graph_row_slice_h(const GraphAggH& a, uint64_t d
         my_w = norm_from_sqrt(a.so[my_r], sid);
         if (a.weight_type == NTS_WEIGHT_MEAN) my_w = mean_weight(my_w, ind);
       }
+      if constexpr (A::kCoef) my_w = my_w * __builtin_nontemporal_load(a.ec + cb + sl);
     }
     for (uint32_t j0 = 0; j0 < ne; j0 += kInfU) {
       T xv[kInfU];
@@ -280,8 +287,8 @@ __device__ __forceinline__ void graph_row_slice_h(const GraphAggH& a, uint64_t d
 
 // k_spmm_graph's items (infer.hip): HUB = false: (row v_begin + i, slice s of
 // LPD vectors), hub rows skipped; HUB = true: (h, s) over the hub list
-template <int HV, int LPD, bool HUB>
-__global__ __launch_bounds__(kInfThreads) void k_spmm_graph_h(GraphAggH a) {
+template <int HV, int LPD, bool HUB, typename A>
+__global__ __launch_bounds__(kInfThreads) void k_spmm_graph_h(A a) {
   constexpr int GPB = kInfThreads / LPD;
   const int grp = threadIdx.x / LPD, sl = threadIdx.x % LPD;
   const uint64_t nsl = (a.nv + LPD - 1) / LPD;
@@ -361,10 +368,10 @@ static int launch_rows_h(hipStream_t st, const uint16_t* table, uint64_t ldt, co
   return NTS_OK;
 }
 
-template <int HV>
-static int launch_graph_h(hipStream_t st, const GraphAggH& a) {
+template <int HV, typename A>
+static int launch_graph_h(hipStream_t st, const A& a) {
   // hubs first: they are the longest items of the call
-  hipLaunchKernelGGL((k_spmm_graph_h<HV, kHubLpd, true>), dim3(kHubGrid), dim3(kInfThreads), 0, st,
+  hipLaunchKernelGGL((k_spmm_graph_h<HV, kHubLpd, true, A>), dim3(kHubGrid), dim3(kInfThreads), 0, st,
                      a);
   NTS_LAUNCH_CHECK();
   const int lpd = a.nv <= 8 ? 8 : a.nv <= 16 ? 16 : a.nv <= 32 ? 32 : 64;
@@ -373,7 +380,7 @@ static int launch_graph_h(hipStream_t st, const GraphAggH& a) {
   // one item per lane group up to 2^20 blocks, grid-stride beyond
   const uint32_t grid = (uint32_t)std::min<uint64_t>((items + gpb - 1) / gpb, 1u << 20);
 #define NTS_I(LPD) \
-  hipLaunchKernelGGL((k_spmm_graph_h<HV, LPD, false>), dim3(grid), dim3(kInfThreads), 0, st, a)
+  hipLaunchKernelGGL((k_spmm_graph_h<HV, LPD, false, A>), dim3(grid), dim3(kInfThreads), 0, st, a)
   if (lpd == 8) NTS_I(8); else if (lpd == 16) NTS_I(16); else if (lpd == 32) NTS_I(32); else NTS_I(64);
 #undef NTS_I
   NTS_LAUNCH_CHECK();
@@ -392,6 +399,60 @@ static int launch_graph_h(hipStream_t st, const GraphAggH& a) {
 }  // namespace nts_hip
 
 using namespace nts_hip;
+
+// nts_hip_spmm_graph_fwd_h and its _coef sibling: A = GraphAggH or GraphAggCoefH
+template <typename A>
+static int spmm_graph_fwd_h(nts_hip_ctx* ctx, const nts_graph_dev* graph, const float* edge_coef,
+                            uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
+                            const uint16_t* xh, uint64_t ldxh, uint32_t feature_size, float* y,
+                            uint64_t ldy) {
+  NTS_CHECK_ARG(graph != nullptr, "graph is NULL");
+  NTS_CHECK_ARG(v_begin <= v_end, "v_begin > v_end");
+  NTS_CHECK_ARG(xh != nullptr, "the half table is NULL");
+  NTS_CHECK_ARG(ctx && y, "NULL argument");
+  NTS_CHECK_ARG(v_end <= graph->n_vertices && graph->n_vertices <= 0xFFFFFFFFull,
+                "vertex range outside the graph");
+  NTS_CHECK_ARG(graph->column_offset && (graph->n_edges == 0 || graph->row_indices),
+                "graph without its CSC");
+  NTS_CHECK_ARG(weight_type == NTS_WEIGHT_SUM || weight_type == NTS_WEIGHT_MEAN ||
+                    weight_type == NTS_WEIGHT_NONE,
+                "weight type: SUM, MEAN or NONE (no MEAN_SAMPLED, no UP_DEGREE over the full graph)");
+  NTS_CHECK_ARG(weight_type == NTS_WEIGHT_NONE || (graph->in_degree && graph->out_degree),
+                "graph without its degrees");
+  NTS_CHECK_ARG(feature_size > 0, "feature_size is 0");
+  NTS_CHECK_ARG(ldxh >= feature_size && ldy >= feature_size, "leading dimension < feature_size");
+  NTS_CHECK_ARG((uintptr_t)xh % 2 == 0, "the half table's address is odd");
+  const uint64_t n = v_end - v_begin;
+  if (n == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  HubScratch h;
+  NTS_RET(list_hubs(ctx, graph, v_begin, n, h));
+  if (weight_type != NTS_WEIGHT_NONE) NTS_RET(degree_sqrt_tables(ctx, graph, h.so, h.si));
+  A a;
+  if constexpr (A::kCoef) a.ec = edge_coef;
+  a.co = graph->column_offset;
+  a.ri = graph->row_indices;
+  a.so = h.so;
+  a.si = h.si;
+  a.in_deg = graph->in_degree;
+  a.weight_type = weight_type;
+  a.relu = relu ? 1 : 0;
+  a.x = xh;
+  a.ldx = ldxh;
+  a.y = y;
+  a.ldy = ldy;
+  a.yal = out_align(y, ldy);
+  a.F = feature_size;
+  a.v_begin = v_begin;
+  a.n = n;
+  a.hubs = h.hubs;
+  a.hubs_n = h.pos + n;
+  const int hv = half_vec(feature_size, xh, ldxh);
+  a.nv = (feature_size + hv - 1) / hv;
+#define NTS_C(HV) launch_graph_h<HV>(ctx->stream, a)
+  NTS_BY_HALF_VEC(hv, NTS_C);
+#undef NTS_C
+}
 
 extern "C" {
 
@@ -438,51 +499,18 @@ int nts_hip_gather_rows_h(nts_hip_ctx* ctx, const uint16_t* tableh, uint64_t ld_
 int nts_hip_spmm_graph_fwd_h(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_begin,
                              uint64_t v_end, int weight_type, int relu, const uint16_t* xh,
                              uint64_t ldxh, uint32_t feature_size, float* y, uint64_t ldy) {
+  return spmm_graph_fwd_h<GraphAggH>(ctx, graph, nullptr, v_begin, v_end, weight_type, relu, xh,
+                                     ldxh, feature_size, y, ldy);
+}
+
+int nts_hip_spmm_graph_fwd_coef_h(nts_hip_ctx* ctx, const nts_graph_dev* graph,
+                                  const float* edge_coef, uint64_t v_begin, uint64_t v_end,
+                                  int weight_type, int relu, const uint16_t* xh, uint64_t ldxh,
+                                  uint32_t feature_size, float* y, uint64_t ldy) {
   NTS_CHECK_ARG(graph != nullptr, "graph is NULL");
-  NTS_CHECK_ARG(v_begin <= v_end, "v_begin > v_end");
-  NTS_CHECK_ARG(xh != nullptr, "the half table is NULL");
-  NTS_CHECK_ARG(ctx && y, "NULL argument");
-  NTS_CHECK_ARG(v_end <= graph->n_vertices && graph->n_vertices <= 0xFFFFFFFFull,
-                "vertex range outside the graph");
-  NTS_CHECK_ARG(graph->column_offset && (graph->n_edges == 0 || graph->row_indices),
-                "graph without its CSC");
-  NTS_CHECK_ARG(weight_type == NTS_WEIGHT_SUM || weight_type == NTS_WEIGHT_MEAN ||
-                    weight_type == NTS_WEIGHT_NONE,
-                "weight type: SUM, MEAN or NONE (no MEAN_SAMPLED, no UP_DEGREE over the full graph)");
-  NTS_CHECK_ARG(weight_type == NTS_WEIGHT_NONE || (graph->in_degree && graph->out_degree),
-                "graph without its degrees");
-  NTS_CHECK_ARG(feature_size > 0, "feature_size is 0");
-  NTS_CHECK_ARG(ldxh >= feature_size && ldy >= feature_size, "leading dimension < feature_size");
-  NTS_CHECK_ARG((uintptr_t)xh % 2 == 0, "the half table's address is odd");
-  const uint64_t n = v_end - v_begin;
-  if (n == 0) return NTS_OK;
-  NTS_HIP_TRY(hipSetDevice(ctx->device));
-  HubScratch h;
-  NTS_RET(list_hubs(ctx, graph, v_begin, n, h));
-  if (weight_type != NTS_WEIGHT_NONE) NTS_RET(degree_sqrt_tables(ctx, graph, h.so, h.si));
-  GraphAggH a;
-  a.co = graph->column_offset;
-  a.ri = graph->row_indices;
-  a.so = h.so;
-  a.si = h.si;
-  a.in_deg = graph->in_degree;
-  a.weight_type = weight_type;
-  a.relu = relu ? 1 : 0;
-  a.x = xh;
-  a.ldx = ldxh;
-  a.y = y;
-  a.ldy = ldy;
-  a.yal = out_align(y, ldy);
-  a.F = feature_size;
-  a.v_begin = v_begin;
-  a.n = n;
-  a.hubs = h.hubs;
-  a.hubs_n = h.pos + n;
-  const int hv = half_vec(feature_size, xh, ldxh);
-  a.nv = (feature_size + hv - 1) / hv;
-#define NTS_C(HV) launch_graph_h<HV>(ctx->stream, a)
-  NTS_BY_HALF_VEC(hv, NTS_C);
-#undef NTS_C
+  NTS_CHECK_ARG(edge_coef || graph->n_edges == 0, "edge_coef is NULL");
+  return spmm_graph_fwd_h<GraphAggCoefH>(ctx, graph, edge_coef, v_begin, v_end, weight_type, relu,
+                                         xh, ldxh, feature_size, y, ldy);
 }
 
 }  // extern "C"

@@ -50,6 +50,7 @@ struct IV<4> {
 };
 
 struct GraphAgg {
+  static constexpr bool kCoef = false;
   const uint64_t* co;      // [V+1] global CSC offsets
   const uint32_t* ri;      // [E] global src ids
   const float* so;         // [V] degree_sqrt(out_degree)   (weight_type != NONE)
@@ -66,6 +67,14 @@ struct GraphAgg {
   uint64_t v_begin, n;     // rows [v_begin, v_begin + n)
   const uint32_t* hubs;    // HUB: the hub rows, ascending; hubs_n[0] of them
   const uint32_t* hubs_n;
+};
+
+// nts_hip_spmm_graph_fwd_coef: edge e uses fl32(w(e) * ec[e]), ec
+// one fp32 per edge in CSC order, streamed beside the edge's source id.  A
+// struct of its own, so the kernels above keep their kernarg layout and code.
+struct GraphAggCoef : GraphAgg {
+  static constexpr bool kCoef = true;
+  const float* ec;         // [E] per-edge coefficient
 };
 
 __global__ void k_degree_sqrt(uint64_t n, const uint32_t* __restrict__ out_deg,
@@ -95,8 +104,8 @@ __global__ void k_hub_scatter(const uint32_t* __restrict__ pos, uint64_t v_begin
 
 // one (row d, column slice) item on the calling LPD-lane group: vector column
 // `col` of the row (col >= nv: an idle lane, it still takes part in the shuffles)
-template <int VEC, int LPD>
-__device__ __forceinline__ void graph_row_slice(const GraphAgg& a, uint64_t d, uint32_t col, int sl) {
+template <int VEC, int LPD, typename A>
+__device__ __forceinline__ void graph_row_slice(const A& a, uint64_t d, uint32_t col, int sl) {
   using T = typename IV<VEC>::T;
   const uint64_t beg = a.co[d], end = a.co[d + 1];
   const bool weighted = a.weight_type != NTS_WEIGHT_NONE;
@@ -117,6 +126,7 @@ __device__ __forceinline__ void graph_row_slice(const GraphAgg& a, uint64_t d, u
         my_w = norm_from_sqrt(a.so[my_r], sid);
         if (a.weight_type == NTS_WEIGHT_MEAN) my_w = mean_weight(my_w, ind);
       }
+      if constexpr (A::kCoef) my_w = my_w * __builtin_nontemporal_load(a.ec + cb + sl);
     }
     for (uint32_t j0 = 0; j0 < ne; j0 += kInfU) {
       T xv[kInfU];
@@ -163,8 +173,8 @@ __device__ __forceinline__ void graph_row_slice(const GraphAgg& a, uint64_t d, u
 // i * nsl + s; hub rows are skipped.  HUB = true: items (h, s) over the hub list.
 // Neighbouring groups take neighbouring slices of one row: its edge ids are
 // fetched from memory once and hit in cache for the other slices.
-template <int VEC, int LPD, bool HUB>
-__global__ __launch_bounds__(kInfThreads) void k_spmm_graph(GraphAgg a) {
+template <int VEC, int LPD, bool HUB, typename A>
+__global__ __launch_bounds__(kInfThreads) void k_spmm_graph(A a) {
   constexpr int GPB = kInfThreads / LPD;
   const int grp = threadIdx.x / LPD, sl = threadIdx.x % LPD;
   const uint64_t nsl = (a.nv + LPD - 1) / LPD;
@@ -184,15 +194,15 @@ __global__ __launch_bounds__(kInfThreads) void k_spmm_graph(GraphAgg a) {
   }
 }
 
-template <int VEC, int LPD, bool HUB>
-static int launch_graph(hipStream_t st, uint32_t grid, const GraphAgg& a) {
-  hipLaunchKernelGGL((k_spmm_graph<VEC, LPD, HUB>), dim3(grid), dim3(kInfThreads), 0, st, a);
+template <int VEC, int LPD, bool HUB, typename A>
+static int launch_graph(hipStream_t st, uint32_t grid, const A& a) {
+  hipLaunchKernelGGL((k_spmm_graph<VEC, LPD, HUB, A>), dim3(grid), dim3(kInfThreads), 0, st, a);
   NTS_LAUNCH_CHECK();
   return NTS_OK;
 }
 
-template <int VEC>
-static int launch_graph_vec(hipStream_t st, const GraphAgg& a) {
+template <int VEC, typename A>
+static int launch_graph_vec(hipStream_t st, const A& a) {
   // hubs first: they are the longest items of the call
   NTS_RET((launch_graph<VEC, kHubLpd, true>(st, kHubGrid, a)));
   const int lpd = a.nv <= 8 ? 8 : a.nv <= 16 ? 16 : a.nv <= 32 ? 32 : 64;
@@ -571,11 +581,12 @@ static int gat_graph_vec(uint32_t D, uint32_t F, const float* x, uint64_t ldx, c
 
 using namespace nts_hip;
 
-extern "C" {
-
-int nts_hip_spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_begin,
-                           uint64_t v_end, int weight_type, int relu, const float* x, uint64_t ldx,
-                           uint32_t feature_size, float* y, uint64_t ldy) {
+// nts_hip_spmm_graph_fwd and its _coef sibling: A = GraphAgg or GraphAggCoef
+template <typename A>
+static int spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, const float* edge_coef,
+                          uint64_t v_begin, uint64_t v_end, int weight_type, int relu,
+                          const float* x, uint64_t ldx, uint32_t feature_size, float* y,
+                          uint64_t ldy) {
   NTS_CHECK_ARG(graph != nullptr, "graph is NULL");
   NTS_CHECK_ARG(v_begin <= v_end, "v_begin > v_end");
   NTS_CHECK_ARG(ctx && x && y, "NULL argument");
@@ -599,7 +610,8 @@ int nts_hip_spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_
   uint32_t *pos = h.pos, *hubs = h.hubs;
   if (weight_type != NTS_WEIGHT_NONE) NTS_RET(degree_sqrt_tables(ctx, graph, so, si));
 
-  GraphAgg a;
+  A a;
+  if constexpr (A::kCoef) a.ec = edge_coef;
   a.co = graph->column_offset;
   a.ri = graph->row_indices;
   a.so = so;
@@ -622,6 +634,25 @@ int nts_hip_spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_
   if (vec == 4) return launch_graph_vec<4>(st, a);
   if (vec == 2) return launch_graph_vec<2>(st, a);
   return launch_graph_vec<1>(st, a);
+}
+
+extern "C" {
+
+int nts_hip_spmm_graph_fwd(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_begin,
+                           uint64_t v_end, int weight_type, int relu, const float* x, uint64_t ldx,
+                           uint32_t feature_size, float* y, uint64_t ldy) {
+  return spmm_graph_fwd<GraphAgg>(ctx, graph, nullptr, v_begin, v_end, weight_type, relu, x, ldx,
+                                  feature_size, y, ldy);
+}
+
+int nts_hip_spmm_graph_fwd_coef(nts_hip_ctx* ctx, const nts_graph_dev* graph,
+                                const float* edge_coef, uint64_t v_begin, uint64_t v_end,
+                                int weight_type, int relu, const float* x, uint64_t ldx,
+                                uint32_t feature_size, float* y, uint64_t ldy) {
+  NTS_CHECK_ARG(graph != nullptr, "graph is NULL");
+  NTS_CHECK_ARG(edge_coef || graph->n_edges == 0, "edge_coef is NULL");
+  return spmm_graph_fwd<GraphAggCoef>(ctx, graph, edge_coef, v_begin, v_end, weight_type, relu, x,
+                                      ldx, feature_size, y, ldy);
 }
 
 int nts_hip_spmm_graph_fwd_max(nts_hip_ctx* ctx, const nts_graph_dev* graph, uint64_t v_begin,

@@ -88,22 +88,34 @@ struct SelectArgs {
   uint64_t batch_seq;
   uint64_t seed;
   const float* eprob = nullptr;  // weighted selection only: one value per edge, CSC order
+  // COEF kernels only (nts_hip_sample_layer_coef): the kept edge at
+  // CSC position q leaves ecoef[q] in wf beside its id in ans
+  const float* ecoef = nullptr;
+  float* wf = nullptr;
 };
 
+// One kept edge: output slot pos of destination i takes source g, the edge at
+// CSC position q.  COEF = false is the selection every existing entry runs.
+template <bool COEF>
+__device__ __forceinline__ void keep_edge(const SelectArgs& a, uint32_t pos, uint32_t i, uint32_t g,
+                                          uint64_t q) {
+  a.ans[pos] = g;
+  a.edst[pos] = i;
+  a.marks[g] = 1;
+  if constexpr (COEF) a.wf[pos] = a.ecoef[q];
+}
+
 // Copy path: all neighbours of dst i in CSC order (coalesced stride).
+template <bool COEF>
 __device__ __forceinline__ void copy_all(const SelectArgs& a, uint32_t i, uint64_t beg,
                                          uint32_t deg, uint32_t c, int lane) {
-  for (uint32_t k = lane; k < deg; k += kWave) {
-    uint32_t g = a.grows[beg + k];
-    a.ans[c + k] = g;
-    a.edst[c + k] = i;
-    a.marks[g] = 1;
-  }
+  for (uint32_t k = lane; k < deg; k += kWave)
+    keep_edge<COEF>(a, c + k, i, a.grows[beg + k], beg + k);
 }
 
 // Rejection path: the first `need` distinct accepted draws, in draw order.
 // `word(j)` returns the j-th word of this dst's stream.  Returns words consumed.
-template <typename WordFn>
+template <bool COEF, typename WordFn>
 __device__ __forceinline__ uint32_t select_distinct(const SelectArgs& a, uint32_t i,
                                                     uint64_t beg, uint32_t deg, uint32_t need,
                                                     uint32_t c, int lane, uint32_t* set,
@@ -143,11 +155,7 @@ __device__ __forceinline__ uint32_t select_distinct(const SelectArgs& a, uint32_
     if ((take >> lane) & 1ull) {
       const uint32_t slot = count + (uint32_t)__popcll(take & lt_mask);
       set[slot] = val;
-      const uint32_t pos = c + slot;
-      const uint32_t g = a.grows[beg + val];
-      a.ans[pos] = g;
-      a.edst[pos] = i;
-      a.marks[g] = 1;
+      keep_edge<COEF>(a, c + slot, i, a.grows[beg + val], beg + val);
     }
     count += (uint32_t)__popcll(take);
     __builtin_amdgcn_wave_barrier();
@@ -235,6 +243,7 @@ __device__ uint32_t select_distinct_hashed(uint32_t need, uint32_t* hset, uint32
 
 // PHILOX, fanout > kSetCap: one wave per block (the hash set takes the LDS).
 // Positions go to ans first (in place), then to neighbour ids.
+template <bool COEF>
 __global__ __launch_bounds__(kWave) void k_select_philox_big(SelectArgs a, uint32_t cap) {
   extern __shared__ uint32_t hset[];
   const int lane = threadIdx.x;
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(kWave) void k_select_philox_big(SelectArgs a, uint3
     const uint32_t n = a.co[i + 1] - c;
     if (c + n > a.e_cap) continue;  // capacity overflow (flagged by count_scan)
     if (n == deg) {
-      copy_all(a, i, beg, deg, c, lane);
+      copy_all<COEF>(a, i, beg, deg, c, lane);
       continue;
     }
     if (n == 0) continue;
@@ -258,15 +267,14 @@ __global__ __launch_bounds__(kWave) void k_select_philox_big(SelectArgs a, uint3
     select_distinct_hashed(n, hset, cap, lane, deg, (0u - deg) % deg, true, a.ans + c,
                            [&](uint32_t j) { return philox_word(seed, d, layer, bs, j); });
     for (uint32_t k = lane; k < n; k += kWave) {
-      const uint32_t g = a.grows[beg + a.ans[c + k]];
-      a.ans[c + k] = g;
-      a.edst[c + k] = i;
-      a.marks[g] = 1;
+      const uint64_t q = beg + a.ans[c + k];
+      keep_edge<COEF>(a, c + k, i, a.grows[q], q);
     }
   }
 }
 
 // PHILOX: one wave per destination, grid-stride.
+template <bool COEF>
 __global__ __launch_bounds__(kSelThreads) void k_select_philox(SelectArgs a) {
   __shared__ uint32_t sets[kSelWaves][kSetCap];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -281,14 +289,14 @@ __global__ __launch_bounds__(kSelThreads) void k_select_philox(SelectArgs a) {
     const uint32_t n = a.co[i + 1] - c;
     if (c + n > a.e_cap) continue;  // capacity overflow (flagged by count_scan)
     if (n == deg) {
-      copy_all(a, i, beg, deg, c, lane);
+      copy_all<COEF>(a, i, beg, deg, c, lane);
     } else if (n > 0) {
       Draw dr;
       dr.init(deg, true);
       const uint64_t seed = a.seed;
       const uint32_t layer = a.layer;
       const uint64_t bs = a.batch_seq;
-      select_distinct(a, i, beg, deg, n, c, lane, set, dr, [&](uint32_t j) {
+      select_distinct<COEF>(a, i, beg, deg, n, c, lane, set, dr, [&](uint32_t j) {
         return philox_word(seed, d, layer, bs, j);
       });
     }
@@ -320,6 +328,7 @@ struct GrpDupScan<kGrp> {
   static __device__ __forceinline__ void run(bool&, uint32_t, int, uint32_t) {}
 };
 
+template <bool COEF>
 __global__ __launch_bounds__(kSelThreads) void k_select_philox_g16(SelectArgs a) {
   __shared__ uint32_t sets[kSelWaves * kGrpPerWave][kGrp];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -338,12 +347,8 @@ __global__ __launch_bounds__(kSelThreads) void k_select_philox_g16(SelectArgs a)
     const uint32_t n = a.co[i + 1] - c;
     if (c + n > a.e_cap) continue;  // capacity overflow (flagged by count_scan)
     if (n == deg) {
-      for (uint32_t k = gl; k < deg; k += kGrp) {
-        const uint32_t g = a.grows[beg + k];
-        a.ans[c + k] = g;
-        a.edst[c + k] = i;
-        a.marks[g] = 1;
-      }
+      for (uint32_t k = gl; k < deg; k += kGrp)
+        keep_edge<COEF>(a, c + k, i, a.grows[beg + k], beg + k);
       continue;
     }
     if (n == 0) continue;
@@ -373,11 +378,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select_philox_g16(SelectArgs a)
       if ((take >> gl) & 1u) {
         const uint32_t slot = count + (uint32_t)__popc(take & lt16);
         set[slot] = val;
-        const uint32_t pos = c + slot;
-        const uint32_t g = a.grows[beg + val];
-        a.ans[pos] = g;
-        a.edst[pos] = i;
-        a.marks[g] = 1;
+        keep_edge<COEF>(a, c + slot, i, a.grows[beg + val], beg + val);
       }
       count += (uint32_t)__popc(take);
       __builtin_amdgcn_wave_barrier();
@@ -428,28 +429,25 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 // The ordered walk, 64 positions per call (ascending): keeps r < T and the
-// first k positions with r == T.
+// first k positions with r == T.  q: the lane's CSC position (COEF).
+template <bool COEF>
 struct SharedEmit {
   uint32_t out = 0, eqseen = 0;
   __device__ __forceinline__ void round(const SelectArgs& a, uint32_t i, uint32_t c, uint32_t n,
                                         bool valid, uint32_t r, uint32_t g, uint32_t T, uint32_t k,
-                                        uint64_t lt_mask) {
+                                        uint64_t lt_mask, uint64_t q) {
     const bool eq = valid && r == T;
     const uint64_t eqm = __ballot(eq);
     const bool keep = (valid && r < T) || (eq && eqseen + (uint32_t)__popcll(eqm & lt_mask) < k);
     const uint64_t km = __ballot(keep);
     const uint32_t slot = out + (uint32_t)__popcll(km & lt_mask);
-    if (keep && slot < n) {
-      a.ans[c + slot] = g;
-      a.edst[c + slot] = i;
-      a.marks[g] = 1;
-    }
+    if (keep && slot < n) keep_edge<COEF>(a, c + slot, i, g, q);
     out += (uint32_t)__popcll(km);
     eqseen += (uint32_t)__popcll(eqm);
   }
 };
 
-template <typename KeyFn>
+template <bool COEF, typename KeyFn>
 __device__ __forceinline__ void shared_select_regs(const SelectArgs& a, uint32_t i, uint64_t beg,
                                                    uint32_t deg, uint32_t n, uint32_t c, int lane,
                                                    const KeyFn& key) {
@@ -487,14 +485,15 @@ __device__ __forceinline__ void shared_select_regs(const SelectArgs& a, uint32_t
     for (int j = 0; j < kShKeys; ++j)
       if ((uint32_t)j < J && ((r[j] & bit) != 0u) != one) cand &= ~(1u << j);
   }
-  SharedEmit em;
+  SharedEmit<COEF> em;
 #pragma unroll
   for (int j = 0; j < kShKeys; ++j)
     if ((uint32_t)j < J)
-      em.round(a, i, c, n, ((have >> j) & 1u) != 0u, r[j], id[j], prefix, k, lt_mask);
+      em.round(a, i, c, n, ((have >> j) & 1u) != 0u, r[j], id[j], prefix, k, lt_mask,
+               beg + (uint32_t)j * kWave + (uint32_t)lane);
 }
 
-template <typename KeyFn>
+template <bool COEF, typename KeyFn>
 __device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t i, uint64_t beg,
                                                    uint32_t deg, uint32_t n, uint32_t c, int lane,
                                                    uint32_t* hist, const KeyFn& key) {
@@ -543,7 +542,7 @@ __device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t
     known |= 255u << shift;
     wave_lds_sync();  // the counters are read before the next pass zeroes them
   }
-  SharedEmit em;
+  SharedEmit<COEF> em;
   for (uint32_t p0 = 0; p0 < deg; p0 += kWave) {
     const uint32_t p = p0 + (uint32_t)lane;
     uint32_t g = 0u, r = 0u;
@@ -551,13 +550,13 @@ __device__ __forceinline__ void shared_select_hist(const SelectArgs& a, uint32_t
       g = a.grows[beg + p];
       r = key(p, g);
     }
-    em.round(a, i, c, n, p < deg, r, g, prefix, k, lt_mask);
+    em.round(a, i, c, n, p < deg, r, g, prefix, k, lt_mask, beg + p);
   }
 }
 
 // One wave per destination, grid-stride: copy, register select or histogram
 // select.  make_key(d, beg) builds the destination's key functor.
-template <typename MakeKey>
+template <bool COEF, typename MakeKey>
 __device__ __forceinline__ void select_by_key(const SelectArgs& a, uint32_t (*hist)[256],
                                               const MakeKey& make_key) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -571,22 +570,23 @@ __device__ __forceinline__ void select_by_key(const SelectArgs& a, uint32_t (*hi
     const uint32_t n = a.co[i + 1] - c;
     if (c + n > a.e_cap) continue;  // capacity overflow (flagged by count_scan)
     if (n == deg) {
-      copy_all(a, i, beg, deg, c, lane);
+      copy_all<COEF>(a, i, beg, deg, c, lane);
     } else if (n > 0) {
       const auto key = make_key(d, beg);
       if (deg <= kShRegMax)
-        shared_select_regs(a, i, beg, deg, n, c, lane, key);
+        shared_select_regs<COEF>(a, i, beg, deg, n, c, lane, key);
       else
-        shared_select_hist(a, i, beg, deg, n, c, lane, hist[w], key);
+        shared_select_hist<COEF>(a, i, beg, deg, n, c, lane, hist[w], key);
     }
   }
 }
 
 // PHILOX_SHARED: one wave per destination, grid-stride.
+template <bool COEF>
 __global__ __launch_bounds__(kSelThreads) void k_select_shared(SelectArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t hist[kSelWaves][256];
   const SharedKey key(a);
-  select_by_key(a, hist, [&](uint32_t, uint64_t) { return key; });
+  select_by_key<COEF>(a, hist, [&](uint32_t, uint64_t) { return key; });
 }
 
 // ---- weighted selection: Efraimidis-Spirakis keys -------------
@@ -620,9 +620,10 @@ struct WeightedKey {
   }
 };
 
+template <bool COEF>
 __global__ __launch_bounds__(kSelThreads) void k_select_weighted(SelectArgs a) {
   __shared__ __attribute__((aligned(16))) uint32_t hist[kSelWaves][256];
-  select_by_key(a, hist, [&](uint32_t d, uint64_t beg) {
+  select_by_key<COEF>(a, hist, [&](uint32_t d, uint64_t beg) {
     return WeightedKey{a.seed, a.batch_seq, a.layer, d, a.eprob + beg};
   });
 }
@@ -1759,6 +1760,10 @@ __device__ __forceinline__ void publish_sizes(const uint32_t* sizes, uint32_t* p
   if (pub && blockIdx.x == 0 && threadIdx.x < 4) pub[threadIdx.x] = sizes[threadIdx.x];
 }
 
+// COEF (nts_hip_sample_layer_coef): the selection left the edge's coefficient
+// in wf[k]; the finished weight is multiplied into it, one fp32 multiply after
+// the MEAN / MEAN_SAMPLED division.  Under NONE the coefficient stays as it is.
+template <bool COEF>
 __device__ __forceinline__ uint32_t relabel_one(const RelabelArgs& a, uint32_t k) {
   const uint32_t g = a.ans[k];
   const uint32_t r = a.src_index[g];
@@ -1771,16 +1776,18 @@ __device__ __forceinline__ uint32_t relabel_one(const RelabelArgs& a, uint32_t k
     float w = norm_degree(a.out_deg[g], ind);
     if (a.weight_type == NTS_WEIGHT_MEAN) w = mean_weight(w, ind);
     if (a.weight_type == NTS_WEIGHT_MEAN_SAMPLED) w = w / (float)(a.co[a.edst[k] + 1] - a.co[a.edst[k]]);
+    if constexpr (COEF) w = w * a.wf[k];
     a.wf[k] = w;
   }
   return r;
 }
 
+template <bool COEF>
 __global__ void k_relabel(RelabelArgs a) {
   publish_sizes(a.sizes, a.pub);
   const uint32_t e = a.sizes[1];
   for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < e; k += gridDim.x * blockDim.x)
-    relabel_one(a, k);
+    relabel_one<COEF>(a, k);
 }
 
 // UP_DEGREE weights: out = sampled edges of the src (counted by k_relabel),
@@ -2171,9 +2178,13 @@ using namespace nts_hip;
 // One hop.  `edge_prob` != nullptr: the weighted selection (k_select_weighted)
 // replaces the draw of rng_mode, which the caller passes as NTS_RNG_PHILOX
 // (stateless); everything around the selection is the same code.
+// `edge_coef` != nullptr (nts_hip_sample_layer_coef, which has refused what the
+// coefficient path does not cover): the COEF instantiations of the selection
+// and of k_relabel, and the weights always travel through the CSR transpose.
 static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanout, int layer,
                              uint64_t batch_seq, int rng_mode, int weight_type,
-                             nts_sampcsc_dev* o, const float* edge_prob) {
+                             nts_sampcsc_dev* o, const float* edge_prob,
+                             const float* edge_coef = nullptr) {
   NTS_CHECK_ARG(ctx && g && o, "NULL argument");
   NTS_CHECK_ARG(g->column_offset && g->row_indices, "graph not on device");
   NTS_CHECK_ARG((o->destination || o->v_cap == 0) && o->v_size && o->column_offset &&
@@ -2302,29 +2313,41 @@ static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanou
   a.batch_seq = batch_seq;
   a.seed = ctx->seed;
   a.eprob = edge_prob;
+  const bool coef = edge_coef != nullptr;
+  a.ecoef = edge_coef;
+  a.wf = coef ? o->edge_weight_forward : nullptr;
+  // the selection kernel K, its COEF instantiation where the coefficients ride along
+#define NTS_SELECT(K, ...)                         \
+  do {                                             \
+    if (coef)                                      \
+      hipLaunchKernelGGL(K<true>, __VA_ARGS__);    \
+    else                                           \
+      hipLaunchKernelGGL(K<false>, __VA_ARGS__);   \
+  } while (0)
   if (edge_prob) {
     const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves), 4096u));
-    hipLaunchKernelGGL(k_select_weighted, dim3(gs), dim3(kSelThreads), 0, st, a);
+    NTS_SELECT(k_select_weighted, dim3(gs), dim3(kSelThreads), 0, st, a);
   } else if (rng_mode == NTS_RNG_PHILOX) {
     if (fanout >= 0 && fanout <= kGrp) {
       const uint32_t gs =
           std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves * kGrpPerWave), 4096u));
-      hipLaunchKernelGGL(k_select_philox_g16, dim3(gs), dim3(kSelThreads), 0, st, a);
+      NTS_SELECT(k_select_philox_g16, dim3(gs), dim3(kSelThreads), 0, st, a);
     } else if (fanout < 0 || fanout <= kSetCap) {
       const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves), 4096u));
-      hipLaunchKernelGGL(k_select_philox, dim3(gs), dim3(kSelThreads), 0, st, a);
+      NTS_SELECT(k_select_philox, dim3(gs), dim3(kSelThreads), 0, st, a);
     } else {
       uint32_t cap = 1;
       while (cap < 2u * (uint32_t)fanout) cap <<= 1;
       const size_t lds = (size_t)cap * sizeof(uint32_t);
-      NTS_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_philox_big),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const void* big = coef ? reinterpret_cast<const void*>(&k_select_philox_big<true>)
+                             : reinterpret_cast<const void*>(&k_select_philox_big<false>);
+      NTS_HIP_TRY(hipFuncSetAttribute(big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const uint32_t gs = std::max(1u, std::min(o->v_cap, 2048u));
-      hipLaunchKernelGGL(k_select_philox_big, dim3(gs), dim3(kWave), lds, st, a, cap);
+      NTS_SELECT(k_select_philox_big, dim3(gs), dim3(kWave), lds, st, a, cap);
     }
   } else if (rng_mode == NTS_RNG_PHILOX_SHARED) {
     const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves), 4096u));
-    hipLaunchKernelGGL(k_select_shared, dim3(gs), dim3(kSelThreads), 0, st, a);
+    NTS_SELECT(k_select_shared, dim3(gs), dim3(kSelThreads), 0, st, a);
   } else {
     const int lem = rng_mode == NTS_RNG_MT19937_LEMIRE ? 1 : 0;
     constexpr int mt_dbg = 0;  // (the kernels' debug-dump argument: off)
@@ -2402,6 +2425,7 @@ static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanou
     const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves * kGrpPerWave), 4096u));
     hipLaunchKernelGGL(k_mt_rows, dim3(gs), dim3(kSelThreads), 0, st, a);
   }
+#undef NTS_SELECT
   NTS_LAUNCH_CHECK();
 
 frontier:
@@ -2450,7 +2474,10 @@ frontier:
                  weight_type,        o->row_indices, o->edge_weight_forward,
                  up ? t_up : nullptr, (up || csr) ? nullptr : o->sizes_host};
   if (up) NTS_HIP_TRY(hipMemsetAsync(t_up, 0, up_n * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_relabel, dim3(ge), dim3(256), 0, st, ra);
+  if (coef)
+    hipLaunchKernelGGL(k_relabel<true>, dim3(ge), dim3(256), 0, st, ra);
+  else
+    hipLaunchKernelGGL(k_relabel<false>, dim3(ge), dim3(256), 0, st, ra);
   NTS_LAUNCH_CHECK();
   if (up) {
     hipLaunchKernelGGL(k_up_weight, dim3(ge), dim3(256), 0, st, o->row_indices, o->edge_dst,
@@ -2472,7 +2499,7 @@ frontier:
       // one radix pass on the high H bits, then k_csr_bucket per 2^L sources
       const uint32_t H = std::min(9u, bits - 6), L = bits - H;
       const uint32_t* totals = nullptr;
-      const bool wpl = weight_type != NTS_WEIGHT_NONE && o->edge_weight_backward;
+      const bool wpl = (weight_type != NTS_WEIGHT_NONE || coef) && o->edge_weight_backward;
       RadixPayload pl;
       pl.p1_in = o->edge_dst;
       pl.p1_out = t_sdst;
@@ -2502,7 +2529,7 @@ frontier:
     NTS_RET(radix_sort_pairs(o->row_indices, nullptr, t_skey, t_seid, o->sizes + 1, o->e_cap,
                              bits, t_sort, st, ctx));
     hipLaunchKernelGGL(k_csr_finalize, dim3(ge), dim3(256), 0, st, t_skey, t_seid, o->edge_dst,
-                       weight_type == NTS_WEIGHT_NONE ? nullptr : o->edge_weight_forward,
+                       weight_type == NTS_WEIGHT_NONE && !coef ? nullptr : o->edge_weight_forward,
                        o->sizes, o->row_offset, o->column_indices, o->edge_weight_backward,
                        o->csr_edge_id, o->sizes_host);
     NTS_LAUNCH_CHECK();
@@ -2525,6 +2552,25 @@ extern "C" int nts_hip_sample_layer_weighted(nts_hip_ctx* ctx, const nts_graph_d
   NTS_CHECK_ARG(!o->omit_map, "weighted sampling with omit_map (PD cache) is not supported");
   return sample_layer_impl(ctx, g, fanout, layer, batch_seq, NTS_RNG_PHILOX, weight_type, o,
                            edge_prob);
+}
+
+extern "C" int nts_hip_sample_layer_coef(nts_hip_ctx* ctx, const nts_graph_dev* g,
+                                         const float* edge_prob, const float* edge_coef,
+                                         int fanout, int layer, uint64_t batch_seq, int rng_mode,
+                                         int weight_type, nts_sampcsc_dev* o) {
+  NTS_CHECK_ARG(ctx && g && o, "NULL argument");
+  NTS_CHECK_ARG(edge_coef, "edge_coef is NULL");
+  NTS_CHECK_ARG(rng_mode == NTS_RNG_PHILOX || rng_mode == NTS_RNG_PHILOX_SHARED,
+                "edge coefficients: rng_mode must be PHILOX or PHILOX_SHARED (no MT19937 mode)");
+  NTS_CHECK_ARG(!edge_prob || rng_mode == NTS_RNG_PHILOX,
+                "edge_prob (the weighted draw) with PHILOX_SHARED");
+  NTS_CHECK_ARG((weight_type & NTS_WEIGHT_UP_DEGREE) == 0,
+                "edge coefficients with NTS_WEIGHT_UP_DEGREE are not supported");
+  NTS_CHECK_ARG(!o->omit_map, "edge coefficients with omit_map (PD cache) are not supported");
+  NTS_CHECK_ARG(o->edge_weight_forward,
+                "edge coefficients need edge_weight_forward (under NTS_WEIGHT_NONE too)");
+  return sample_layer_impl(ctx, g, fanout, layer, batch_seq, rng_mode, weight_type, o, edge_prob,
+                           edge_coef);
 }
 
 extern "C" int nts_hip_weighted_keys(nts_hip_ctx* ctx, const nts_graph_dev* g,

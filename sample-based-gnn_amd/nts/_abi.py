@@ -68,6 +68,7 @@ EXPORTED = (
     "nts_hip_gatv2_forward", "nts_hip_gatv2_backward",
     "nts_hip_spmm_csc_fwd_h", "nts_hip_spmm_graph_fwd_h", "nts_hip_gather_rows_h",
     "nts_hip_sample_layer_weighted", "nts_hip_weighted_keys",
+    "nts_hip_sample_layer_coef", "nts_hip_spmm_graph_fwd_coef", "nts_hip_spmm_graph_fwd_coef_h",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -132,6 +133,13 @@ def lib() -> C.CDLL:
         # edge-weighted neighbour selection: edge_prob after the graph
         "nts_hip_sample_layer_weighted": ([P, C.POINTER(GraphDev), P, I, I, U64, I,
                                            C.POINTER(SampCSCDev)], I),
+        # edge coefficients: edge_prob (NULL: rng_mode's draw), edge_coef
+        "nts_hip_sample_layer_coef": ([P, C.POINTER(GraphDev), P, P, I, I, U64, I, I,
+                                       C.POINTER(SampCSCDev)], I),
+        "nts_hip_spmm_graph_fwd_coef": ([P, C.POINTER(GraphDev), P, U64, U64, I, I, P, U64, U32, P,
+                                         U64], I),
+        "nts_hip_spmm_graph_fwd_coef_h": ([P, C.POINTER(GraphDev), P, U64, U64, I, I, P, U64, U32,
+                                           P, U64], I),
         "nts_hip_weighted_keys": ([P, C.POINTER(GraphDev), P, P, U32, I, U64, P, P], I),
         "nts_hip_gather_rows": ([P, P, U64, P, P, U32, U32, P, U64], I),
         "nts_hip_gather_labels": ([P, P, P, P, U32, P], I),

@@ -403,6 +403,13 @@ class InputInfo:
     # replacement).  Needs EDGE_WEIGHT_FILE; Philox-sampled algorithms without
     # PD cache; not with SAMPLE_SHARED
     sample_weighted: int = 0
+    # EDGE_WEIGHT_AGG (this build's key): 1 = the edge weights are aggregation
+    # coefficients too: every layer computes Y[d] = sum_e c(e) a_e X[src(e)], c
+    # the algorithm's weight and a the edge's value (sampled training,
+    # evaluation and FULL_INFERENCE).  Needs EDGE_WEIGHT_FILE; Philox-sampled
+    # GCN / GraphSAGE algorithms without PD cache; not with ROOT_WEIGHT,
+    # AGGREGATOR:max or UP_DEGREE
+    edge_weight_agg: int = 0
     # SEED (this build's key): the driver's seed (sampler streams, dropout)
     seed: int = 2000
     extra: dict = field(default_factory=dict)
@@ -442,6 +449,7 @@ class InputInfo:
             "FEATURE_F16": ("feature_f16", int),
             "EDGE_WEIGHT_FILE": ("edge_weight_file", str),
             "SAMPLE_WEIGHTED": ("sample_weighted", int),
+            "EDGE_WEIGHT_AGG": ("edge_weight_agg", int),
             "SEED": ("seed", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():

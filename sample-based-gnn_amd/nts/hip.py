@@ -76,11 +76,24 @@ class HipContext:
 
     # ---- sampler -------------------------------------------------------------
     def sample_layer(self, graph: "DeviceGraph", lay: "LayerBuffers", fanout: int, layer: int,
-                     batch_seq: int, rng_mode: int, weight_type: int, edge_prob=None):
+                     batch_seq: int, rng_mode: int, weight_type: int, edge_prob=None,
+                     edge_coef=None):
         """`edge_prob` (float32 [E], CSC order): edge-weighted selection
-        (nts_hip_sample_layer_weighted); rng_mode is then not read."""
+        (nts_hip_sample_layer_weighted); without edge_coef rng_mode is
+        then not read (with edge_coef it must be NTS_RNG_PHILOX: the library
+        refuses edge_prob with NTS_RNG_PHILOX_SHARED).
+        `edge_coef` (float32 [E], CSC order): per-edge aggregation coefficients
+        (nts_hip_sample_layer_coef): edge_weight_forward[k] =
+        c(e_k) * edge_coef[q_k]; the draw is rng_mode's, or edge_prob's when given."""
         g = graph.as_struct()
         o = lay.as_struct()
+        if edge_coef is not None:
+            for t in (edge_coef, edge_prob):
+                assert t is None or (t.dtype == torch.float32 and t.numel() == graph.n_edges)
+            check(self.lib.nts_hip_sample_layer_coef(self.h, C.byref(g), ptr(edge_prob),
+                                                     ptr(edge_coef), fanout, layer, batch_seq,
+                                                     rng_mode, weight_type, C.byref(o)))
+            return
         if edge_prob is not None:
             assert edge_prob.dtype == torch.float32 and edge_prob.numel() == graph.n_edges
             check(self.lib.nts_hip_sample_layer_weighted(self.h, C.byref(g), ptr(edge_prob), fanout,
@@ -277,13 +290,22 @@ class HipContext:
                                             ptr(x), x.stride(0), ptr(row_map), F, ptr(y),
                                             y.stride(0)))
 
-    def spmm_graph_fwd(self, graph, x, y, weight_type, relu=False, v_begin=0, v_end=None):
+    def spmm_graph_fwd(self, graph, x, y, weight_type, relu=False, v_begin=0, v_end=None,
+                       edge_coef=None):
         """y[d] = (relu?)(sum over ALL in-edges of d of w(e) x[src(e)]) for
         v_begin <= d < v_end over the global CSC of `graph` (a DeviceGraph);
-        the weights come from its degrees (NTS_WEIGHT_SUM / MEAN / NONE)."""
+        the weights come from its degrees (NTS_WEIGHT_SUM / MEAN / NONE).
+        `edge_coef` (float32 [E], CSC order): edge e uses w(e) * edge_coef[e]
+        (nts_hip_spmm_graph_fwd_coef)."""
         g = graph.as_struct()
         if v_end is None:
             v_end = graph.n_vertices
+        if edge_coef is not None:
+            assert edge_coef.dtype == torch.float32 and edge_coef.numel() == graph.n_edges
+            check(self.lib.nts_hip_spmm_graph_fwd_coef(
+                self.h, C.byref(g), ptr(edge_coef), int(v_begin), int(v_end), int(weight_type),
+                int(bool(relu)), ptr(x), x.stride(0), x.shape[1], ptr(y), y.stride(0)))
+            return
         check(self.lib.nts_hip_spmm_graph_fwd(self.h, C.byref(g), int(v_begin), int(v_end),
                                               int(weight_type), int(bool(relu)), ptr(x),
                                               x.stride(0), x.shape[1], ptr(y), y.stride(0)))
@@ -296,11 +318,18 @@ class HipContext:
                                               ptr(xh), xh.stride(0), ptr(row_map), xh.shape[1],
                                               ptr(y), y.stride(0)))
 
-    def spmm_graph_fwd_h(self, graph, xh, y, weight_type, relu=False, v_begin=0, v_end=None):
-        """spmm_graph_fwd over a half table."""
+    def spmm_graph_fwd_h(self, graph, xh, y, weight_type, relu=False, v_begin=0, v_end=None,
+                         edge_coef=None):
+        """spmm_graph_fwd over a half table (edge_coef: nts_hip_spmm_graph_fwd_coef_h)."""
         g = graph.as_struct()
         if v_end is None:
             v_end = graph.n_vertices
+        if edge_coef is not None:
+            assert edge_coef.dtype == torch.float32 and edge_coef.numel() == graph.n_edges
+            check(self.lib.nts_hip_spmm_graph_fwd_coef_h(
+                self.h, C.byref(g), ptr(edge_coef), int(v_begin), int(v_end), int(weight_type),
+                int(bool(relu)), ptr(xh), xh.stride(0), xh.shape[1], ptr(y), y.stride(0)))
+            return
         check(self.lib.nts_hip_spmm_graph_fwd_h(self.h, C.byref(g), int(v_begin), int(v_end),
                                                 int(weight_type), int(bool(relu)), ptr(xh),
                                                 xh.stride(0), xh.shape[1], ptr(y), y.stride(0)))

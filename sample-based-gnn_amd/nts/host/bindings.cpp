@@ -92,9 +92,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::class_<PySampler>(m, "FastSampler")
       .def(py::init([](std::shared_ptr<FullyRepGraph> g, const torch::Tensor& seeds, int layers,
                        int batch, std::vector<int> fanout, int rng_mode, uint64_t seed,
-                       bool csr, int pipeline, bool weighted) {
-             TORCH_CHECK(!weighted || g->edge_prob.defined(),
-                         "weighted: the graph has no edge_prob");
+                       bool csr, int pipeline, bool weighted, bool coef) {
+             TORCH_CHECK(!(weighted || coef) || g->edge_prob.defined(),
+                         "weighted / coef: the graph has no edge_prob");
              auto p = new PySampler();
              TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
              p->cs = std::make_unique<NtsStream>(g->device, nullptr, seed);
@@ -104,11 +104,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                                   c, true);
              p->s->rng_mode = rng_mode;
              p->s->weighted = weighted;
+             p->s->coef = coef;
              return p;
            }),
            py::arg("graph"), py::arg("seeds"), py::arg("layers"), py::arg("batch_size"),
            py::arg("fanout"), py::arg("rng_mode") = (int)NTS_RNG_PHILOX, py::arg("seed") = 2000,
-           py::arg("csr") = true, py::arg("pipeline") = 1, py::arg("weighted") = false)
+           py::arg("csr") = true, py::arg("pipeline") = 1, py::arg("weighted") = false,
+           py::arg("coef") = false)
       // the split form (several slots in flight, finished in issue order)
       .def("issue",
            [](PySampler& p, int batch, int slot, WeightType w) {
@@ -162,11 +164,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       "sampler_throughput",
       [](std::shared_ptr<FullyRepGraph> g, const torch::Tensor& seeds, int batch,
          std::vector<int> fanout, WeightType w, int rng_mode, int n_batches,
-         std::vector<bool> csr, bool weighted) {
+         std::vector<bool> csr, bool weighted, bool coef) {
         SamplerRate r;
         {
           py::gil_scoped_release nogil;
-          r = sampler_throughput(g, to_ids(seeds), batch, fanout, w, rng_mode, n_batches, csr, weighted);
+          r = sampler_throughput(g, to_ids(seeds), batch, fanout, w, rng_mode, n_batches, csr, weighted,
+                                 coef);
         }
         py::dict d;
         d["seconds"] = r.seconds;
@@ -177,7 +180,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("graph"), py::arg("seeds"), py::arg("batch_size"), py::arg("fanout"),
       py::arg("weight_type") = WeightType::Sum, py::arg("rng_mode") = (int)NTS_RNG_PHILOX,
       py::arg("n_batches") = 16, py::arg("csr_layers") = std::vector<bool>(),
-      py::arg("weighted") = false);
+      py::arg("weighted") = false, py::arg("coef") = false);
 
   py::class_<Communicator, std::shared_ptr<Communicator>>(m, "Communicator")
       .def(py::init([](int n, int r, py::bytes uid, int dev) {
@@ -258,6 +261,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("layer_norm_eps", &GCNConfig::layer_norm_eps)
       .def_readwrite("feature_f16", &GCNConfig::feature_f16)
       .def_readwrite("weighted_sampling", &GCNConfig::weighted_sampling)
+      .def_readwrite("edge_weighted", &GCNConfig::edge_weighted)
       .def_readwrite("sampler_cus", &GCNConfig::sampler_cus)
       .def_readwrite("sampler_gate", &GCNConfig::sampler_gate)
       .def_readwrite("pad_features", &GCNConfig::pad_features)

@@ -395,11 +395,13 @@ void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
     o.sample_ans = dptr<uint32_t>(s->sample_ans);
     o.edge_dst = dptr<uint32_t>(s->edge_dst);
     o.source = dptr<uint32_t>(s->source);
-    o.edge_weight_forward = wt == NTS_WEIGHT_NONE ? nullptr : dptr<float>(s->edge_weight_forward);
+    o.edge_weight_forward =
+        wt == NTS_WEIGHT_NONE && !coef ? nullptr : dptr<float>(s->edge_weight_forward);
     o.row_offset = s->has_csr ? dptr<uint32_t>(s->row_offset) : nullptr;
     o.column_indices = s->has_csr ? dptr<uint32_t>(s->column_indices) : nullptr;
     o.edge_weight_backward =
-        (s->has_csr && wt != NTS_WEIGHT_NONE) ? dptr<float>(s->edge_weight_backward) : nullptr;
+        (s->has_csr && (wt != NTS_WEIGHT_NONE || coef)) ? dptr<float>(s->edge_weight_backward)
+                                                        : nullptr;
     o.sizes = dptr<uint32_t>(s->sizes);
     o.dst_local_id = dptr<uint32_t>(s->dst_local_id);  // undefined (NULL) unless merged
     o.csr_edge_id = dptr<uint32_t>(s->csr_edge_id);
@@ -413,7 +415,12 @@ void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
       o.omit_row = dptr<uint32_t>(s->omit_row);
     }
     const double tl = now_s();
-    if (weighted)
+    if (coef)
+      hip_check(nts_hip_sample_layer_coef(
+                    cs.ctx(), &g, weighted ? dptr<float>(whole_graph->edge_prob) : nullptr,
+                    dptr<float>(whole_graph->edge_prob), fanout[l], l, bseq, rng_mode, wt, &o),
+                "nts_hip_sample_layer_coef");
+    else if (weighted)
       hip_check(nts_hip_sample_layer_weighted(cs.ctx(), &g, dptr<float>(whole_graph->edge_prob),
                                               fanout[l], l, bseq, wt, &o),
                 "nts_hip_sample_layer_weighted");

@@ -242,10 +242,12 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // blocks every launch on that stream in the host for ~60 us).
   nslots_ = cfg.pipeline ? kSlots : 1;
   sampler = std::make_unique<FastSampler>(graph, train_nids, L, cfg.batch_size, cfg.fanout,
-                                          nslots_, csr, sample_weight() != WeightType::None,
+                                          nslots_, csr,
+                                          sample_weight() != WeightType::None || cfg.edge_weighted,
                                           cfg.gat || cfg.root_weight, max_aggr());
   sampler->rng_mode = cfg.rng_mode;
   sampler->weighted = cfg.weighted_sampling;  // (its refusals follow every other option's below)
+  sampler->coef = cfg.edge_weighted;          // (likewise)
   sampler->up_degree = cfg.up_degree;
   if (cfg.root_weight)  // the inverse of dst_local_id, for every hop with a graph-op backward
     for (auto* q : sampler->ssgs)
@@ -313,6 +315,24 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     TORCH_CHECK(!cfg.pd_cache, "weighted_sampling is not supported with pd_cache");
     TORCH_CHECK(!cfg.sample_gpu, "weighted_sampling is not supported with sample_gpu (the "
                                  "reference's mt19937 stream)");
+  }
+  if (cfg.edge_weighted) {  // (after every other option's refusals)
+    const std::pair<bool, const char*> conflicts[] = {
+        {!graph->edge_prob.defined(),
+         "a graph without edge_prob (from_edges(..., edge_weight) or from_csc(..., edge_prob))"},
+        {cfg.gat, "gat (attention layers use no edge weights)"},
+        {max_aggr(), "aggregator = max (it uses no edge weights)"},
+        {cfg.root_weight, "root_weight"},
+        {cfg.pd_cache, "pd_cache"},
+        {cfg.sample_gpu, "sample_gpu (the reference's mt19937 stream)"},
+        {cfg.up_degree, "up_degree"},
+        {is_mt_mode(cfg.rng_mode), "an MT19937 rng_mode"},
+        {!(cfg.cache_rate < 0.0), "cache_rate >= 0"},
+        {!cfg.deterministic_backward,
+         "deterministic_backward = false (the backward reads the CSR's weights)"},
+    };
+    for (const auto& c : conflicts)
+      TORCH_CHECK(!c.first, "edge_weighted is not supported with ", c.second);
   }
   for (int i = 0; i < nslots_; ++i) {
     TORCH_CHECK(hipEventCreateWithFlags(&ready_[i], hipEventDisableTiming) == hipSuccess,
@@ -922,10 +942,11 @@ std::unique_ptr<FastSampler> GCN_SAMPLE_ALLGPU_impl::eval_sampler(const std::vec
   const int L = (int)cfg.fanout.size();
   auto s = std::make_unique<FastSampler>(graph, ids, L, batch, cfg.fanout, 1,
                                          std::vector<bool>(L, cfg.gat),
-                                         sample_weight() != WeightType::None,
+                                         sample_weight() != WeightType::None || cfg.edge_weighted,
                                          cfg.gat || cfg.root_weight);
   s->rng_mode = cfg.rng_mode;
   s->weighted = cfg.weighted_sampling;
+  s->coef = cfg.edge_weighted;
   s->up_degree = cfg.up_degree;
   s->batch_seq = batch_seq;
   return s;
@@ -1093,7 +1114,20 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
       evs.push_back({a, b});
       (void)hipEventRecord(a, st);
     }
-    if (xr.dtype() == torch::kFloat16)  // feature_f16: layer 0 reads the half table
+    const float* coef = cfg.edge_weighted ? dptr<float>(graph->edge_prob) : nullptr;
+    if (coef && xr.dtype() == torch::kFloat16)  // edge_weighted: the _coef siblings
+      hip_check(nts_hip_spmm_graph_fwd_coef_h(cs->ctx(), &g, coef, 0, (uint64_t)V, wt, relu ? 1 : 0,
+                                              dptr<const uint16_t>(xr), (uint64_t)xr.stride(0),
+                                              (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                              (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd_coef_h");
+    else if (coef)
+      hip_check(nts_hip_spmm_graph_fwd_coef(cs->ctx(), &g, coef, 0, (uint64_t)V, wt, relu ? 1 : 0,
+                                            xr.data_ptr<float>(), (uint64_t)xr.stride(0),
+                                            (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                            (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd_coef");
+    else if (xr.dtype() == torch::kFloat16)  // feature_f16: layer 0 reads the half table
       hip_check(nts_hip_spmm_graph_fwd_h(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
                                          dptr<const uint16_t>(xr), (uint64_t)xr.stride(0),
                                          (uint32_t)xr.size(1), y.data_ptr<float>(),
@@ -1423,16 +1457,19 @@ void GCN_SAMPLE_ALLGPU_impl::reset_stats() {
 SamplerRate sampler_throughput(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& seeds,
                                int batch_size, const std::vector<int>& fanout, WeightType w,
                                int rng_mode, int n_batches, const std::vector<bool>& csr_layers,
-                               bool weighted) {
-  TORCH_CHECK(!weighted || g->edge_prob.defined(), "weighted: the graph has no edge_prob");
+                               bool weighted, bool coef) {
+  TORCH_CHECK(!(weighted || coef) || g->edge_prob.defined(),
+              "weighted / coef: the graph has no edge_prob");
   constexpr int kS = 3;
   TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
   NtsStream st(g->device, nullptr, 2000);
   auto guard = st.guard();
   const int L = (int)fanout.size();
-  FastSampler s(g, seeds, L, batch_size, fanout, kS, csr_layers, w != WeightType::None, false);
+  FastSampler s(g, seeds, L, batch_size, fanout, kS, csr_layers, w != WeightType::None || coef,
+                false);
   s.rng_mode = rng_mode;
   s.weighted = weighted;
+  s.coef = coef;
   uint64_t items = g->global_vertices;
   for (auto* x : s.ssg->sampled_sgs) items = std::max<uint64_t>({items, x->e_cap, x->v_cap});
   hip_check(nts_hip_ctx_reserve(st.ctx(), g->global_vertices, items), "nts_hip_ctx_reserve");

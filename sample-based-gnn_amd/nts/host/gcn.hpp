@@ -111,11 +111,25 @@ struct GCNConfig {
   // `fanout` of them by successive sampling without replacement with
   // probability proportional to the graph's edge_prob (Efraimidis-Spirakis
   // keys on a Philox stream of their own).  Only the draw changes: counts,
-  // frontier, CSR and the weight_type weights are the default sampler's, and
-  // edge_prob is no aggregation coefficient.  Every sampler the driver builds
+  // frontier, CSR and the weight_type weights are the default sampler's; the
+  // option alone does not make edge_prob an aggregation coefficient
+  // (edge_weighted does).  Every sampler the driver builds
   // (training, evaluate, forward_eval) uses it.  Needs a graph with edge_prob;
   // not with an MT19937 rng_mode, NTS_RNG_PHILOX_SHARED, pd_cache or sample_gpu.
   bool weighted_sampling = false;
+  // Edge weights as aggregation coefficients (DGL
+  // GraphConv(edge_weight=), PyG GCNConv(x, ei, edge_weight)): every layer's
+  // graph op is Y[d] = sum_e fl32(c(e) a_e) X[src(e)], a = the graph's edge_prob
+  // and c the weight of weight_type (WeightType::None: the coefficient alone, for
+  // a caller's own normalisation such as gcn_norm).  Every sampler the driver
+  // builds calls nts_hip_sample_layer_coef, and infer_full() / evaluate_full()
+  // the _coef graph kernels.  With or without weighted_sampling, either
+  // bottom-layer order, feature_f16, layer_norm, multi_label, PHILOX or
+  // PHILOX_SHARED, pipelined or not, data parallel.  Needs a graph with
+  // edge_prob; not with gat, aggregator = max, root_weight, pd_cache,
+  // sample_gpu, up_degree, an MT19937 rng_mode, cache_rate >= 0 or
+  // deterministic_backward = false.
+  bool edge_weighted = false;
   // pipelined sampler's stream priority: 1 = sampler stream high, 0 = both
   // normal, -1 = the training stream high (the sampler's blocks dispatched
   // after the training stream's), 2 = auto: high for the MT19937 stream (its
@@ -184,7 +198,7 @@ struct SamplerRate {
 SamplerRate sampler_throughput(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& seeds,
                                int batch_size, const std::vector<int>& fanout, WeightType w,
                                int rng_mode, int n_batches, const std::vector<bool>& csr_layers,
-                               bool weighted = false);
+                               bool weighted = false, bool coef = false);
 
 class GCN_SAMPLE_ALLGPU_impl {
  public:

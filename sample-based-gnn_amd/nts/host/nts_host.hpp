@@ -255,6 +255,9 @@ class FastSampler {
   // edge-weighted selection (nts_hip_sample_layer_weighted with
   // whole_graph->edge_prob) in place of rng_mode's draw
   bool weighted = false;
+  // edge_prob as aggregation coefficients too (nts_hip_sample_layer_coef,
+  // DESIGN §8r): the weights are built under WeightType::None as well
+  bool coef = false;
   bool up_degree = false;  // UP_DEGREE: weights from each sampled layer's own degrees
   uint64_t batch_seq = 0;  // keys the PHILOX / PHILOX_SHARED streams (one per sampled batch)
   // sample_gpu_fast_omit (core/ntsFastSampler.hpp:711-915): when set, the

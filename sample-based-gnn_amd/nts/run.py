@@ -47,8 +47,15 @@ EDGE_WEIGHT_FILE:path / SAMPLE_WEIGHTED:1 (Philox-sampled algorithms without PD
 cache, not with SAMPLE_SHARED): the file holds one little-endian fp32 per edge
 of EDGE_FILE (finite, in [2^-60, 2^60]); a destination with more neighbours
 than its fanout then keeps FANOUT of them with probability proportional to
-these weights (successive sampling without replacement).  The weights choose
-the neighbours only; the aggregation's coefficients do not change.
+these weights (successive sampling without replacement).  SAMPLE_WEIGHTED
+alone chooses the neighbours only; the aggregation's coefficients do not change.
+
+EDGE_WEIGHT_FILE:path / EDGE_WEIGHT_AGG:1 (Philox-sampled GCN / GraphSAGE
+algorithms without PD cache; not with ROOT_WEIGHT, AGGREGATOR:max or UP_DEGREE):
+the edge weights are aggregation coefficients: every layer computes
+Y[d] = sum_e c(e) a_e X[src(e)], c the algorithm's weight and a_e the edge's
+value, in sampled training, evaluation and FULL_INFERENCE.  With or without
+SAMPLE_WEIGHTED and SAMPLE_SHARED.
 
 GAT_ATTN_DROP:0.6 / GAT_FEAT_DROP:0.6 (GAT algorithms): dropout of the attention
 coefficients and of every layer's input while training, fused into the GAT
@@ -116,6 +123,29 @@ def load_inputs(info: dataloader.InputInfo, base: pathlib.Path, n_classes: int, 
     return src, dst, feats, labels, masks
 
 
+def refuse_edge_weight_agg(info: dataloader.InputInfo):
+    """EDGE_WEIGHT_AGG:1 against the rest of the cfg (the driver's table,
+    GCNConfig::edge_weighted, in cfg terms): SystemExit naming the key."""
+    algo = info.algorithm.upper()
+    if not info.edge_weight_agg or algo not in ALGORITHMS:
+        return
+    model, _, rng, _, place = ALGORITHMS[algo]
+    conflicts = (
+        (not info.edge_weight_file,
+         "without an EDGE_WEIGHT_FILE (one fp32 weight per edge)"),
+        (model == "gat", "with GAT algorithms (attention layers use no edge weights)"),
+        (info.aggregator == "max", "with AGGREGATOR:max (it uses no edge weights)"),
+        (bool(info.root_weight), "with ROOT_WEIGHT:1"),
+        (place == "pd", "with the PD-cache algorithms"),
+        (place == "sample_gpu", "with GCNSAMPLEGPU (the reference's mt19937 stream)"),
+        (rng == "mt", "with the mt19937-stream algorithms (Philox-sampled algorithms only)"),
+        (bool(info.up_degree), "with UP_DEGREE:1"),
+    )
+    for hit, why in conflicts:
+        if hit:
+            raise SystemExit(f"ALGORITHM {info.algorithm}: EDGE_WEIGHT_AGG is not supported {why}")
+
+
 def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, device, comm=None):
     from . import host, _abi
     algo = info.algorithm.upper()
@@ -123,6 +153,7 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         raise SystemExit(f"ALGORITHM {info.algorithm}: not supported by this build "
                          f"(supported: {', '.join(sorted(ALGORITHMS))})")
     model, weight, rng, bias, place = ALGORITHMS[algo]
+    refuse_edge_weight_agg(info)
     if info.multi_label and model == "gat":
         raise SystemExit(f"ALGORITHM {info.algorithm}: MULTI_LABEL is not supported with GAT "
                          "(GCN / GraphSAGE algorithms only)")
@@ -184,7 +215,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         layer_norm=bool(info.layer_norm), gat_attn_drop=info.gat_attn_drop,
         gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2),
         shared_sampling=bool(info.sample_shared), feature_f16=bool(info.feature_f16),
-        weighted_sampling=bool(info.sample_weighted), seed=info.seed)
+        weighted_sampling=bool(info.sample_weighted),
+        edge_weighted=bool(info.edge_weight_agg), seed=info.seed)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
@@ -217,6 +249,7 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
     from . import dist as ndist
     cfg_path = pathlib.Path(cfg_path)
     info = dataloader.InputInfo.from_cfg(cfg_path)
+    refuse_edge_weight_agg(info)  # before anything is loaded (build_driver repeats it)
     base = cfg_path.parent
     n_classes = info.layers[-1]
     epochs = info.epochs if epochs is None else epochs
