@@ -32,47 +32,13 @@ def ext():
     return _ext
 
 
-def check_gat_heads(layers, gat, gat_heads):
-    """gat_heads as a list of ints (empty: single-head), or a ValueError that
-    names the option: one entry >= 1 per layer, bottom first, with gat only;
-    a hidden layer's width is split into its heads, the last layer's heads
-    (of layers[-1] columns each) are averaged.  K heads of D columns need
-    K D <= 1024 when D is a multiple of 4, else K D <= 256 (the kernels' limit)."""
-    if gat_heads is None:
-        return []
-    heads = [int(k) for k in gat_heads]
-    layers = list(layers)
-    if not heads:
-        return []
-    if not gat:
-        raise ValueError("gat_heads is not supported without gat (attention layers only)")
-    if len(heads) != len(layers) - 1:
-        raise ValueError(f"gat_heads needs one entry per layer ({len(layers) - 1}), got {len(heads)}")
-    for l, k in enumerate(heads):
-        if k < 1:
-            raise ValueError(f"gat_heads[{l}] must be >= 1, got {k}")
-        last = l == len(heads) - 1
-        if not last and layers[l + 1] % k:
-            raise ValueError(f"gat_heads[{l}] = {k} does not divide layer width {layers[l + 1]}")
-        d = layers[l + 1] if last else layers[l + 1] // k
-        if k > 1 and k * d > (1024 if d % 4 == 0 else 256):
-            raise ValueError(f"gat_heads[{l}] = {k} heads of {d} columns: K D = {k * d} is outside "
-                             "the kernels' width limit (1024 when D is a multiple of 4, else 256)")
-    return heads
-
-
-def check_gat_drop(gat, **rates):
-    """gat_attn_drop / gat_feat_drop as floats, or a ValueError with the
-    driver's text: a rate in [0, 1), and none above 0 without gat."""
-    out = {}
-    for name, value in rates.items():
-        value = float(value)
-        if not 0.0 <= value < 1.0:
-            raise ValueError(f"{name} must be in [0, 1), got {value}")
-        if value != 0.0 and not gat:
-            raise ValueError(f"{name} is not supported without gat (attention layers only)")
-        out[name] = value
-    return out
+def _checked(rule, *args):
+    """one of the driver's own rules (nts/host/options.cpp) at the time the
+    config is made: its text, as a ValueError"""
+    try:
+        rule(*args)
+    except RuntimeError as e:
+        raise ValueError(str(e).splitlines()[0]) from None
 
 
 def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, drop_rate=0.5,
@@ -101,11 +67,13 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
         rng_mode = _abi.NTS_RNG_PHILOX_SHARED
     if aggregator not in ("sum", "max"):
         raise ValueError(f"aggregator must be 'sum' or 'max', got {aggregator!r}")
-    gat_heads = check_gat_heads(layers, gat, gat_heads)
-    gat_drop = check_gat_drop(gat, gat_attn_drop=gat_attn_drop, gat_feat_drop=gat_feat_drop)
-    if gat_v2 and not gat:
-        raise ValueError("gat_v2 is not supported without gat (attention layers only)")
     E = ext()
+    gat_heads = [int(k) for k in gat_heads or ()]  # empty: single-head
+    _checked(E.check_gat_heads, list(layers), bool(gat), gat_heads)
+    gat_drop = {"gat_attn_drop": float(gat_attn_drop), "gat_feat_drop": float(gat_feat_drop)}
+    for name, rate in gat_drop.items():
+        _checked(E.check_gat_drop, name, rate, bool(gat))
+    _checked(E.check_gat_v2, bool(gat_v2), bool(gat))
     c = E.GCNConfig()
     c.layer_size = list(layers)
     c.fanout = list(fanout)

@@ -2,6 +2,7 @@
 #include <torch/extension.h>
 
 #include "gcn.hpp"
+#include "options.hpp"
 
 namespace py = pybind11;
 using namespace nts;
@@ -276,6 +277,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("shuffle", &GCNConfig::shuffle)
       .def_readwrite("profile", &GCNConfig::profile)
       .def_readwrite("seed", &GCNConfig::seed);
+
+  // the constructor's option and shape rules on facts about its inputs: no
+  // tensor, no device (RuntimeError with the rule's text as its first line)
+  m.def(
+      "check_driver_options",
+      [](const GCNConfig& cfg, torch::ScalarType feature_dtype, bool feature_on_gpu,
+         int64_t feature_cols, std::vector<int64_t> label_shape, bool label_on_gpu,
+         int64_t n_vertices, bool has_edge_prob) {
+        check_driver_options(cfg, {feature_dtype, feature_on_gpu, feature_cols, std::move(label_shape),
+                                   label_on_gpu, n_vertices, has_edge_prob});
+      },
+      py::arg("cfg"), py::kw_only(), py::arg("feature_dtype"), py::arg("feature_on_gpu"),
+      py::arg("feature_cols"), py::arg("label_shape"), py::arg("label_on_gpu"),
+      py::arg("n_vertices"), py::arg("has_edge_prob"));
+  m.def("check_gat_heads", &check_gat_heads, py::arg("layer_size"), py::arg("gat"), py::arg("heads"));
+  m.def("check_gat_v2", &check_gat_v2, py::arg("gat_v2"), py::arg("gat"));
+  m.def("check_gat_drop", &check_gat_drop, py::arg("name"), py::arg("rate"), py::arg("gat"));
 
   py::class_<GCN_SAMPLE_ALLGPU_impl>(m, "GCN_SAMPLE_ALLGPU_impl")
       .def(py::init([](std::shared_ptr<FullyRepGraph> g, torch::Tensor feature,

@@ -7,6 +7,7 @@
 // [fused feature gather +] graph op -> vertexForward ... -> Loss ->
 // self_backward -> Update (all-reduce + Adam) -> zero_grad.
 #include "gcn.hpp"
+#include "options.hpp"
 
 #include <hip/hip_runtime_api.h>
 
@@ -62,88 +63,11 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                                                GCNConfig c, std::shared_ptr<Communicator> comm_)
     : graph(std::move(g)), F(std::move(feature)), L_GT(std::move(label)), cfg(std::move(c)),
       comm(std::move(comm_)) {
-  TORCH_CHECK(cfg.layer_size.size() >= 2, "need at least one layer");
-  TORCH_CHECK(cfg.fanout.size() == cfg.layer_size.size() - 1, "fanout per layer");
-  TORCH_CHECK(F.dtype() != torch::kFloat16 || cfg.feature_f16,
-              "a float16 feature table needs feature_f16 (FEATURE_F16:1): without it the driver "
-              "takes an fp32 table");
-  TORCH_CHECK(F.is_cuda() && (F.dtype() == torch::kFloat32 || F.dtype() == torch::kFloat16) &&
-                  F.size(1) == cfg.layer_size[0],
-              "feature table must be fp32 [V, layer_size[0]] on the GPU");
-  if (cfg.multi_label) {
-    TORCH_CHECK(!cfg.gat, "multi_label is not supported with GAT layers (GCN / GraphSAGE only)");
-    TORCH_CHECK(L_GT.dim() == 2, "multi_label needs a 2-D label tensor [V, C] of 0/1, got ",
-                L_GT.dim(), "-D");
-    TORCH_CHECK(L_GT.is_cuda() && L_GT.size(0) == (int64_t)graph->global_vertices &&
-                    L_GT.size(1) == cfg.layer_size.back(),
-                "multi_label: labels must be [V, layer_size.back()] on the GPU");
-  } else {
-    TORCH_CHECK(L_GT.dim() == 1, "labels must be int64 [V] (a [V, C] 0/1 label tensor needs "
-                                 "multi_label)");
-  }
-  // what root_weight and aggregator = max both refuse, in the order it is
-  // reported; tf_why: the option's own reason inside the transform_first text
-  auto refuse_conflicts = [&](const char* option, const char* tf_why) {
-    const std::pair<bool, std::string> conflicts[] = {
-        {cfg.gat, " is not supported with gat (GCN / GraphSAGE layers only)"},
-        {cfg.pd_cache, " is not supported with pd_cache"},
-        {cfg.sample_gpu, " is not supported with sample_gpu"},
-        {cfg.transform_first == 1, std::string(" is not supported with transform_first = 1 (") +
-                                       tf_why + "aggregate-first only)"},
-        {cfg.pair_table > 0, " is not supported with pair_table > 0"},
-        {!(cfg.cache_rate < 0.0), " is not supported with cache_rate >= 0"},
-        {!cfg.fused_gather, " is not supported with fused_gather = false"},
-        {!cfg.deterministic_backward,
-         " needs deterministic_backward (its backward runs over the CSR)"},
-    };
-    for (const auto& c : conflicts) TORCH_CHECK(!c.first, option, c.second);
-  };
-  if (cfg.root_weight) refuse_conflicts("root_weight", "");
-  TORCH_CHECK(cfg.aggregator == 0 || cfg.aggregator == 1, "aggregator must be 0 (sum) or 1 (max)");
-  if (max_aggr()) {
-    refuse_conflicts("aggregator = max", "a maximum does not commute with W: ");
-    TORCH_CHECK(!cfg.up_degree, "aggregator = max is not supported with up_degree (it takes no "
-                                "edge weights)");
-  }
-  if (!cfg.gat_heads.empty()) {
-    const size_t nl = cfg.layer_size.size() - 1;
-    TORCH_CHECK(cfg.gat, "gat_heads is not supported without gat (attention layers only)");
-    TORCH_CHECK(cfg.gat_heads.size() == nl, "gat_heads needs one entry per layer (", nl, "), got ",
-                cfg.gat_heads.size());
-    for (size_t l = 0; l < nl; ++l) {
-      const int64_t K = cfg.gat_heads[l], w = cfg.layer_size[l + 1];
-      TORCH_CHECK(K >= 1, "gat_heads[", l, "] must be >= 1, got ", K);
-      const bool last = l + 1 == nl;
-      TORCH_CHECK(last || w % K == 0, "gat_heads[", l, "] = ", K, " does not divide layer width ", w);
-      const int64_t D = last ? w : w / K, Fl = K * D;
-      TORCH_CHECK(K == 1 || Fl <= (D % 4 == 0 ? 1024 : 256), "gat_heads[", l, "] = ", K, " heads of ",
-                  D, " columns: K D = ", Fl, " is outside the kernels' width limit (1024 when D is a "
-                  "multiple of 4, else 256)");
-    }
-  }
-  TORCH_CHECK(!cfg.gat_v2 || cfg.gat, "gat_v2 is not supported without gat (attention layers only)");
-  if (cfg.layer_norm) {
-    TORCH_CHECK(!cfg.gat, "layer_norm is not supported with gat (GCN / GraphSAGE layers only)");
-    TORCH_CHECK(!cfg.pd_cache, "layer_norm is not supported with pd_cache");
-    TORCH_CHECK(cfg.transform_first != 1, "layer_norm is not supported with transform_first = 1 "
-                                          "(LayerNorm does not commute with A: aggregate-first only)");
-    TORCH_CHECK(cfg.pair_table <= 0, "layer_norm is not supported with pair_table > 0");
-    for (size_t l = 1; l + 1 < cfg.layer_size.size(); ++l)
-      TORCH_CHECK(cfg.layer_size[l] <= 1024, "layer_norm is not supported with a hidden width above "
-                                             "1024 (layer ", l - 1, ": ", cfg.layer_size[l], ")");
-  }
-  for (const auto& r : {std::make_pair("gat_attn_drop", cfg.gat_attn_drop),
-                        std::make_pair("gat_feat_drop", cfg.gat_feat_drop)}) {
-    TORCH_CHECK(r.second >= 0.0 && r.second < 1.0, r.first, " must be in [0, 1), got ", r.second);
-    TORCH_CHECK(r.second == 0.0 || cfg.gat, r.first,
-                " is not supported without gat (attention layers only)");
-  }
-  if (cfg.sample_gpu) {
-    TORCH_CHECK(!cfg.gat && !cfg.pd_cache, "GCN_SAMPLE_GPU: GCN / GraphSAGE layers");
-    TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX,
-                "GCN_SAMPLE_GPU samples with the reference's mt19937 stream (rng_mode MT19937)");
-    cfg.deterministic_backward = true;  // the CSR exists for every graph-op backward
-  }
+  check_driver_options(cfg, {F.scalar_type(), F.is_cuda(), F.dim() == 2 ? F.size(1) : -1,
+                             L_GT.sizes().vec(), L_GT.is_cuda(),
+                             (int64_t)graph->global_vertices, graph->edge_prob.defined()});
+  // (derived after the check: the rules above read the caller's value)
+  if (cfg.sample_gpu) cfg.deterministic_backward = true;  // the CSR exists for every backward
   // sampler_cus n > 0: the sampler's stream on n CUs, the training stream on
   // the others; n < 0: the sampler on |n| CUs, the training stream on all
   if (cfg.pipeline && cfg.sampler_cus > 0)
@@ -161,8 +85,8 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // +1% memory): a gathered row then spans the minimum number of cache lines
   // (19 instead of ~19.8 for 602 floats), ~2% less traffic in the bottom
   // aggregation, which reads every sampled row once per edge.
-  // (feature_f16: its refusals follow every other option's below, and the
-  // half table is laid out there; nothing here touches the table before)
+  // (feature_f16: the half table is laid out below, after the sampler is
+  // built; nothing here touches the table before)
   const bool f16 = cfg.feature_f16;
   if (!f16 && cfg.pad_features && F.size(1) >= 256 && F.size(1) % 32 != 0 && F.stride(1) == 1) {
     NtsVar Fp = row_padded_empty(F.size(0), F.size(1), graph->device);
@@ -170,7 +94,6 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
     F = Fp;
   }
   if (cfg.cache_rate >= 0.0 && !f16) {
-    TORCH_CHECK(cfg.cache_rate <= 1.0, "cache_rate must be in [0, 1]");
     const uint64_t V = graph->global_vertices;
     const uint64_t n_cache = std::min<uint64_t>(V, (uint64_t)(cfg.cache_rate * (double)V));
     fcache = std::make_unique<FeatureCache>(*cs, *graph, F, n_cache);
@@ -187,9 +110,6 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // rows, at the price of a GEMM over the src rows instead of the dst rows.
   const bool tf_ok = L >= 2 && !cfg.gat && !fcache && cfg.hip_gemm && cfg.fuse_activation &&
                      !cfg.pd_cache && !cfg.root_weight && !max_aggr() && !cfg.layer_norm;
-  if (cfg.transform_first == 1)
-    TORCH_CHECK(tf_ok, "transform_first needs >= 2 layers, the MFMA GEMMs with the fused "
-                       "activation, no GAT and no feature cache");
   // auto (-1): transform first where the first layer narrows the rows at
   // least 4x and its GEMMs run on the whole-row fp32-exact kernels
   // (csrc/gemmx3.hip, split-bf16) or the f16 pair tables (C2: 602 -> 128,
@@ -246,8 +166,8 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
                                           sample_weight() != WeightType::None || cfg.edge_weighted,
                                           cfg.gat || cfg.root_weight, max_aggr());
   sampler->rng_mode = cfg.rng_mode;
-  sampler->weighted = cfg.weighted_sampling;  // (its refusals follow every other option's below)
-  sampler->coef = cfg.edge_weighted;          // (likewise)
+  sampler->weighted = cfg.weighted_sampling;
+  sampler->coef = cfg.edge_weighted;
   sampler->up_degree = cfg.up_degree;
   if (cfg.root_weight)  // the inverse of dst_local_id, for every hop with a graph-op backward
     for (auto* q : sampler->ssgs)
@@ -277,63 +197,10 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   early_ = cfg.early_aggregate && cfg.fused_gather && !cfg.gat && !tf_ && !cfg.pd_cache;
   sampler->rerun_ok = !early_;  // (an MT re-run would leave the early aggregation stale)
   if (cfg.pd_cache) {
-    TORCH_CHECK(!cfg.gat && L >= 2 && cfg.hip_gemm && cfg.pd_super_batch >= 1 &&
-                    cfg.pd_rate >= 0.0,
-                "PD cache: GCN/GraphSAGE with >= 2 layers on the MFMA GEMMs");
     pd_cache_map_ = torch::full({(int64_t)graph->global_vertices}, -1, u32_opts(graph->device));
     pd_cache_loc_ = torch::zeros({(int64_t)graph->global_vertices}, u32_opts(graph->device));
   }
-  if (cfg.rng_mode == NTS_RNG_PHILOX_SHARED) {  // (after every other option check)
-    TORCH_CHECK(!cfg.sample_gpu, "shared sampling is not supported with sample_gpu (the "
-                                 "reference's mt19937 stream)");
-    TORCH_CHECK(!cfg.pd_cache, "shared sampling is not supported with pd_cache");
-  }
-  if (f16) {  // (after every other option's refusals)
-    const std::pair<bool, const char*> conflicts[] = {
-        {cfg.gat, "gat (GCN / GraphSAGE layers only)"},
-        {cfg.pd_cache, "pd_cache"},
-        {cfg.transform_first == 1,
-         "transform_first = 1 (the transform-first GEMMs gather fp32 rows: aggregate-first only)"},
-        {cfg.pair_table > 0, "pair_table > 0"},
-        {!(cfg.cache_rate < 0.0), "cache_rate >= 0"},
-        {cfg.root_weight, "root_weight"},
-        {max_aggr(), "aggregator = max"},
-    };
-    for (const auto& c : conflicts)
-      TORCH_CHECK(!c.first, "feature_f16 is not supported with ", c.second);
-    F = half_feature_table(F, graph->device);
-  }
-  if (cfg.weighted_sampling) {  // (after every other option's refusals)
-    TORCH_CHECK(graph->edge_prob.defined(),
-                "weighted_sampling needs a graph with edge_prob (from_edges(..., edge_weight) or "
-                "from_csc(..., edge_prob))");
-    TORCH_CHECK(!is_mt_mode(cfg.rng_mode), "weighted_sampling is not supported with an MT19937 "
-                "rng_mode (it draws from a Philox stream of its own)");
-    TORCH_CHECK(cfg.rng_mode != NTS_RNG_PHILOX_SHARED,
-                "weighted_sampling is not supported with rng_mode NTS_RNG_PHILOX_SHARED "
-                "(shared_sampling)");
-    TORCH_CHECK(!cfg.pd_cache, "weighted_sampling is not supported with pd_cache");
-    TORCH_CHECK(!cfg.sample_gpu, "weighted_sampling is not supported with sample_gpu (the "
-                                 "reference's mt19937 stream)");
-  }
-  if (cfg.edge_weighted) {  // (after every other option's refusals)
-    const std::pair<bool, const char*> conflicts[] = {
-        {!graph->edge_prob.defined(),
-         "a graph without edge_prob (from_edges(..., edge_weight) or from_csc(..., edge_prob))"},
-        {cfg.gat, "gat (attention layers use no edge weights)"},
-        {max_aggr(), "aggregator = max (it uses no edge weights)"},
-        {cfg.root_weight, "root_weight"},
-        {cfg.pd_cache, "pd_cache"},
-        {cfg.sample_gpu, "sample_gpu (the reference's mt19937 stream)"},
-        {cfg.up_degree, "up_degree"},
-        {is_mt_mode(cfg.rng_mode), "an MT19937 rng_mode"},
-        {!(cfg.cache_rate < 0.0), "cache_rate >= 0"},
-        {!cfg.deterministic_backward,
-         "deterministic_backward = false (the backward reads the CSR's weights)"},
-    };
-    for (const auto& c : conflicts)
-      TORCH_CHECK(!c.first, "edge_weighted is not supported with ", c.second);
-  }
+  if (f16) F = half_feature_table(F, graph->device);
   for (int i = 0; i < nslots_; ++i) {
     TORCH_CHECK(hipEventCreateWithFlags(&ready_[i], hipEventDisableTiming) == hipSuccess,
                 "hipEventCreate");

@@ -123,79 +123,75 @@ def load_inputs(info: dataloader.InputInfo, base: pathlib.Path, n_classes: int, 
     return src, dst, feats, labels, masks
 
 
-def refuse_edge_weight_agg(info: dataloader.InputInfo):
-    """EDGE_WEIGHT_AGG:1 against the rest of the cfg (the driver's table,
-    GCNConfig::edge_weighted, in cfg terms): SystemExit naming the key."""
-    algo = info.algorithm.upper()
-    if not info.edge_weight_agg or algo not in ALGORITHMS:
-        return
-    model, _, rng, _, place = ALGORITHMS[algo]
-    conflicts = (
-        (not info.edge_weight_file,
-         "without an EDGE_WEIGHT_FILE (one fp32 weight per edge)"),
-        (model == "gat", "with GAT algorithms (attention layers use no edge weights)"),
-        (info.aggregator == "max", "with AGGREGATOR:max (it uses no edge weights)"),
-        (bool(info.root_weight), "with ROOT_WEIGHT:1"),
-        (place == "pd", "with the PD-cache algorithms"),
-        (place == "sample_gpu", "with GCNSAMPLEGPU (the reference's mt19937 stream)"),
-        (rng == "mt", "with the mt19937-stream algorithms (Philox-sampled algorithms only)"),
-        (bool(info.up_degree), "with UP_DEGREE:1"),
+def refuse_cfg(info: dataloader.InputInfo):
+    """Every refusal the cfg alone decides (the driver's rules in cfg terms),
+    before anything is loaded: SystemExit with the text of the first row that
+    holds.  A new key's rows go at the end."""
+    model, _, rng, _, place = ALGORITHMS.get(info.algorithm.upper(), (None,) * 5)
+    gat, gcn, pd, mt = model == "gat", model == "gcn", place == "pd", rng == "mt"
+    agg, weighted = bool(info.edge_weight_agg), bool(info.sample_weighted)
+    rows = (
+        (model is None,
+         f"not supported by this build (supported: {', '.join(sorted(ALGORITHMS))})"),
+        (agg and not info.edge_weight_file,
+         "EDGE_WEIGHT_AGG is not supported without an EDGE_WEIGHT_FILE (one fp32 weight per edge)"),
+        (agg and gat,
+         "EDGE_WEIGHT_AGG is not supported with GAT algorithms (attention layers use no edge "
+         "weights)"),
+        (agg and info.aggregator == "max",
+         "EDGE_WEIGHT_AGG is not supported with AGGREGATOR:max (it uses no edge weights)"),
+        (agg and info.root_weight, "EDGE_WEIGHT_AGG is not supported with ROOT_WEIGHT:1"),
+        (agg and pd, "EDGE_WEIGHT_AGG is not supported with the PD-cache algorithms"),
+        (agg and place == "sample_gpu",
+         "EDGE_WEIGHT_AGG is not supported with GCNSAMPLEGPU (the reference's mt19937 stream)"),
+        (agg and mt,
+         "EDGE_WEIGHT_AGG is not supported with the mt19937-stream algorithms (Philox-sampled "
+         "algorithms only)"),
+        (agg and info.up_degree, "EDGE_WEIGHT_AGG is not supported with UP_DEGREE:1"),
+        (info.multi_label and gat,
+         "MULTI_LABEL is not supported with GAT (GCN / GraphSAGE algorithms only)"),
+        (info.root_weight and (gat or place is not None),
+         "ROOT_WEIGHT is not supported with GAT, PD-cache or GCN_SAMPLE_GPU algorithms"),
+        (info.gat_heads and gcn,
+         "GAT_HEADS is not supported with GCN / GraphSAGE algorithms (GAT only)"),
+        (info.gat_v2 and gcn, "GAT_V2 is not supported with GCN / GraphSAGE algorithms (GAT only)"),
+        (info.gat_v2 and info.full_inference,
+         "FULL_INFERENCE is not supported with GAT_V2 (full-neighbour inference for GATv2 is not "
+         "built)"),
+        (info.gat_attn_drop and gcn,
+         "GAT_ATTN_DROP is not supported with GCN / GraphSAGE algorithms (GAT only; they read "
+         "DROP_RATE)"),
+        (info.gat_feat_drop and gcn,
+         "GAT_FEAT_DROP is not supported with GCN / GraphSAGE algorithms (GAT only; they read "
+         "DROP_RATE)"),
+        (info.aggregator == "max" and (gat or place is not None),
+         "AGGREGATOR:max is not supported with GAT, PD-cache or GCN_SAMPLE_GPU algorithms"),
+        (info.layer_norm and (gat or pd),
+         "LAYER_NORM is not supported with GAT or PD-cache algorithms (GCN / GraphSAGE layers "
+         "only)"),
+        (info.sample_shared and (mt or pd),
+         "SAMPLE_SHARED is not supported with the mt19937-stream or PD-cache algorithms "
+         "(Philox-sampled algorithms only)"),
+        (info.feature_f16 and (gat or pd),
+         "FEATURE_F16 is not supported with GAT or PD-cache algorithms (the sum aggregation of "
+         "GCN / GraphSAGE only)"),
+        (weighted and not info.edge_weight_file,
+         "SAMPLE_WEIGHTED is not supported without an EDGE_WEIGHT_FILE (one fp32 weight per edge)"),
+        (weighted and (mt or pd),
+         "SAMPLE_WEIGHTED is not supported with the mt19937-stream or PD-cache algorithms "
+         "(Philox-sampled algorithms only)"),
+        (weighted and info.sample_shared,
+         "SAMPLE_WEIGHTED is not supported with SAMPLE_SHARED:1 (one selection rule per job)"),
     )
-    for hit, why in conflicts:
+    for hit, text in rows:
         if hit:
-            raise SystemExit(f"ALGORITHM {info.algorithm}: EDGE_WEIGHT_AGG is not supported {why}")
+            raise SystemExit(f"ALGORITHM {info.algorithm}: {text}")
 
 
 def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, device, comm=None):
     from . import host, _abi
-    algo = info.algorithm.upper()
-    if algo not in ALGORITHMS:
-        raise SystemExit(f"ALGORITHM {info.algorithm}: not supported by this build "
-                         f"(supported: {', '.join(sorted(ALGORITHMS))})")
-    model, weight, rng, bias, place = ALGORITHMS[algo]
-    refuse_edge_weight_agg(info)
-    if info.multi_label and model == "gat":
-        raise SystemExit(f"ALGORITHM {info.algorithm}: MULTI_LABEL is not supported with GAT "
-                         "(GCN / GraphSAGE algorithms only)")
-    if info.root_weight and (model == "gat" or place is not None):
-        raise SystemExit(f"ALGORITHM {info.algorithm}: ROOT_WEIGHT is not supported with GAT, "
-                         "PD-cache or GCN_SAMPLE_GPU algorithms")
-    if info.gat_heads and model != "gat":
-        raise SystemExit(f"ALGORITHM {info.algorithm}: GAT_HEADS is not supported with GCN / "
-                         "GraphSAGE algorithms (GAT only)")
-    if info.gat_v2 and model != "gat":
-        raise SystemExit(f"ALGORITHM {info.algorithm}: GAT_V2 is not supported with GCN / "
-                         "GraphSAGE algorithms (GAT only)")
-    if info.gat_v2 and info.full_inference:
-        raise SystemExit(f"ALGORITHM {info.algorithm}: FULL_INFERENCE is not supported with GAT_V2 "
-                         "(full-neighbour inference for GATv2 is not built)")
-    for key, rate in (("GAT_ATTN_DROP", info.gat_attn_drop), ("GAT_FEAT_DROP", info.gat_feat_drop)):
-        if rate and model != "gat":
-            raise SystemExit(f"ALGORITHM {info.algorithm}: {key} is not supported with GCN / "
-                             "GraphSAGE algorithms (GAT only; they read DROP_RATE)")
-    if info.aggregator == "max" and (model == "gat" or place is not None):
-        raise SystemExit(f"ALGORITHM {info.algorithm}: AGGREGATOR:max is not supported with GAT, "
-                         "PD-cache or GCN_SAMPLE_GPU algorithms")
-    if info.layer_norm and (model == "gat" or place == "pd"):
-        raise SystemExit(f"ALGORITHM {info.algorithm}: LAYER_NORM is not supported with GAT or "
-                         "PD-cache algorithms (GCN / GraphSAGE layers only)")
-    if info.sample_shared and (rng == "mt" or place == "pd"):
-        raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_SHARED is not supported with the "
-                         "mt19937-stream or PD-cache algorithms (Philox-sampled algorithms only)")
-    if info.feature_f16 and (model == "gat" or place == "pd"):
-        raise SystemExit(f"ALGORITHM {info.algorithm}: FEATURE_F16 is not supported with GAT or "
-                         "PD-cache algorithms (the sum aggregation of GCN / GraphSAGE only)")
-    if info.sample_weighted:
-        if not info.edge_weight_file:
-            raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_WEIGHTED is not supported "
-                             "without an EDGE_WEIGHT_FILE (one fp32 weight per edge)")
-        if rng == "mt" or place == "pd":
-            raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_WEIGHTED is not supported with "
-                             "the mt19937-stream or PD-cache algorithms (Philox-sampled "
-                             "algorithms only)")
-        if info.sample_shared:
-            raise SystemExit(f"ALGORITHM {info.algorithm}: SAMPLE_WEIGHTED is not supported with "
-                             "SAMPLE_SHARED:1 (one selection rule per job)")
+    refuse_cfg(info)  # (run() has already; a direct caller has not)
+    model, weight, rng, bias, place = ALGORITHMS[info.algorithm.upper()]
     if weight == "mean" and info.extra.get("MEAN_WEIGHT", "").lower() == "gpu":
         weight = "mean-sampled"
     cache_rate = -1.0
@@ -249,7 +245,7 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
     from . import dist as ndist
     cfg_path = pathlib.Path(cfg_path)
     info = dataloader.InputInfo.from_cfg(cfg_path)
-    refuse_edge_weight_agg(info)  # before anything is loaded (build_driver repeats it)
+    refuse_cfg(info)  # before anything is loaded
     base = cfg_path.parent
     n_classes = info.layers[-1]
     epochs = info.epochs if epochs is None else epochs

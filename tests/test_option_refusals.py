@@ -78,3 +78,14 @@ def test_unknown_aggregator_is_refused_after_root_weight(build):
         cfg.aggregator = 2
     assert build(two) == "aggregator must be 0 (sum) or 1 (max)"
     assert build(two, root_weight=True, pd_cache=True) == ROOT_REFUSALS["pd_cache"]
+
+
+def test_a_refused_job_allocates_nothing(build):
+    """edge_weighted's refusals are the last of the pass, and the pass runs
+    before the streams, the arenas and the sampler's slots are made"""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    assert build(edge_weighted=True).startswith(
+        "edge_weighted is not supported with a graph without edge_prob")
+    assert torch.cuda.max_memory_allocated() == before
