@@ -613,6 +613,60 @@ int nts_hip_ln_act_bwd(nts_hip_ctx *ctx, uint64_t rows, uint32_t feature_size, c
                        const float *mean, const float *rstd, const float *gamma, float scale,
                        float *dz, uint64_t lddz, float *dgamma, float *dbeta);
 
+/* ---- BatchNorm + relu + dropout of a hidden layer (no reference counterpart) */
+/* Training forward, torch.nn.BatchNorm1d's semantics over [rows x feature_size]:
+ * per column c, n = rows,
+ *   mu = mean_r z[r,c],  var = mean_r (z[r,c] - mu)^2 (biased),
+ *   rstd = 1 / sqrt(var + eps),  xh = (z - mu) rstd,
+ *   y = keep ? relu(gamma[c] xh + beta[c]) / (1 - p) : 0,
+ *   running_mean[c] <- (1 - momentum) running_mean[c] + momentum mu,
+ *   running_var[c]  <- (1 - momentum) running_var[c]  + momentum var n / (n - 1),
+ * with the keep bits, the float scale and the p >= 1 rule of
+ * nts_hip_relu_dropout_f32 for the same (seed, offset, row, col).  mean / rstd
+ * [feature_size] receive mu and rstd for the backward.  running_mean /
+ * running_var may be NULL (no update); rows == 1 leaves them untouched (the
+ * unbiased variance does not exist) and gives var = 0, xh = 0.
+ * The variance is never E[z^2] - mu^2: z is read once by a statistics kernel in
+ * which a block owns a contiguous run of rows whose length depends on `rows`
+ * alone, each thread keeps a Welford (count, mean, M2) over its rows in row
+ * order, and the partials are merged by Chan's formula in a fixed order (the
+ * threads of a column, then the blocks, by a second kernel whose one thread
+ * per column also updates the running statistics).  A third, elementwise
+ * kernel reads z and writes y: 12 feature_size bytes per row in all.  No
+ * atomics: two calls give the same bytes.  A column constant over the rows has
+ * var = 0 and xh = 0 exactly.
+ * 1 <= feature_size <= 1024.  float4 where feature_size % 4 == 0, every
+ * pointer is 16-byte aligned and both pitches are multiples of 4; scalar
+ * otherwise.  A wider row returns NTS_ERR_INVALID and writes nothing;
+ * rows == 0 succeeds and writes nothing. */
+int nts_hip_bn_act_fwd(nts_hip_ctx *ctx, uint64_t rows, uint32_t feature_size, const float *z,
+                       uint64_t ldz, const float *gamma, const float *beta, float eps,
+                       float momentum, float p, uint64_t seed, uint64_t offset, float *y,
+                       uint64_t ldy, float *mean, float *rstd, float *running_mean,
+                       float *running_var);
+/* Eval mode, one elementwise pass that updates nothing:
+ *   y = relu(gamma (z - running_mean) / sqrt(running_var + eps) + beta). */
+int nts_hip_bn_act_eval(nts_hip_ctx *ctx, uint64_t rows, uint32_t feature_size, const float *z,
+                        uint64_t ldz, const float *gamma, const float *beta,
+                        const float *running_mean, const float *running_var, float eps, float *y,
+                        uint64_t ldy);
+/* The training forward's backward, from its y, z, mean and rstd (scale =
+ * 1 / (1 - p), 0 for p >= 1):  g = dy [y > 0] scale,
+ *   dbeta[c] = sum_r g,  dgamma[c] = sum_r g xh,
+ *   dz = gamma rstd (g - dbeta / n - xh dgamma / n).
+ * One reduction pass over (dy, y, z) in the statistics kernel's tiling writes
+ * per-block partials (sum g, sum g (z - mean) rstd, sum (z - mean)), which a
+ * second kernel sums in block order (nts_hip_ln_act_bwd's order); one
+ * elementwise pass then writes dz: 28 feature_size bytes per row.  The third
+ * sum recovers what rounding the saved mean to a float dropped, d = mean_r
+ * (z - mean): forward and backward centre with it, xh = ((z - mean) - d) rstd.  No atomics: two calls give the same bytes.
+ * rows == 0 writes zeros to dgamma / dbeta and nothing else.  Width limit,
+ * float4 rule and refusal as the forward's. */
+int nts_hip_bn_act_bwd(nts_hip_ctx *ctx, uint64_t rows, uint32_t feature_size, const float *dy,
+                       uint64_t lddy, const float *y, uint64_t ldy, const float *z, uint64_t ldz,
+                       const float *mean, const float *rstd, const float *gamma, float scale,
+                       float *dz, uint64_t lddz, float *dgamma, float *dbeta);
+
 /* ---- GAT layer on a merged src/dst sampled block ------------------------- */
 /* The GAT_SAMPLE_ALL_GPU layer (toolkits/GAT_SAMPLE_ALL_GPU.hpp:308-391:
  * BatchGPUSrcDstScatterOp -> leaky_relu(msg . W_att, 0.2) -> BatchGPUEdgeSoftMax

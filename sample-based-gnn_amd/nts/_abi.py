@@ -69,6 +69,7 @@ EXPORTED = (
     "nts_hip_spmm_csc_fwd_h", "nts_hip_spmm_graph_fwd_h", "nts_hip_gather_rows_h",
     "nts_hip_sample_layer_weighted", "nts_hip_weighted_keys",
     "nts_hip_sample_layer_coef", "nts_hip_spmm_graph_fwd_coef", "nts_hip_spmm_graph_fwd_coef_h",
+    "nts_hip_bn_act_fwd", "nts_hip_bn_act_eval", "nts_hip_bn_act_bwd",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -228,6 +229,9 @@ def lib() -> C.CDLL:
         "nts_hip_gat_graph_fwd": ([P, C.POINTER(GraphDev), U64, U64, P, U64, U32, U32, P, P, U64, I], I),
         "nts_hip_ln_act_fwd": ([P, U64, U32, P, U64, P, P, F, F, U64, U64, P, U64, P, P], I),
         "nts_hip_ln_act_bwd": ([P, U64, U32, P, U64, P, U64, P, U64, P, P, P, F, P, U64, P, P], I),
+        "nts_hip_bn_act_fwd": ([P, U64, U32, P, U64, P, P, F, F, F, U64, U64, P, U64, P, P, P, P], I),
+        "nts_hip_bn_act_eval": ([P, U64, U32, P, U64, P, P, P, P, F, P, U64], I),
+        "nts_hip_bn_act_bwd": ([P, U64, U32, P, U64, P, U64, P, U64, P, P, P, F, P, U64, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -369,6 +369,10 @@ class InputInfo:
     # LAYER_NORM (this build's key): LayerNorm on every hidden layer, fused with
     # its relu and dropout (GCN / GraphSAGE algorithms without PD cache)
     layer_norm: int = 0
+    # BATCH_NORM (this build's key): BatchNorm1d on every hidden layer, fused with
+    # its relu and dropout; running statistics for evaluation (GCN / GraphSAGE
+    # algorithms without PD cache; not with LAYER_NORM)
+    batch_norm: int = 0
     # GAT_HEADS (this build's key): attention heads per layer, bottom first,
     # dash-separated like LAYERS (8-1); hidden layers concatenate their heads
     # (LAYERS keeps the concatenated width), the last layer averages them.
@@ -441,6 +445,7 @@ class InputInfo:
             "ROOT_WEIGHT": ("root_weight", int),
             "AGGREGATOR": ("aggregator", _aggregator),
             "LAYER_NORM": ("layer_norm", int),
+            "BATCH_NORM": ("batch_norm", int),
             "GAT_HEADS": ("gat_heads", _gat_heads),
             "GAT_ATTN_DROP": ("gat_attn_drop", float),
             "GAT_FEAT_DROP": ("gat_feat_drop", float),

@@ -549,6 +549,30 @@ class HipContext:
                                           ptr(gamma), float(scale), ptr(dz), dz.stride(0),
                                           ptr(dgamma), ptr(dbeta)))
 
+    def bn_act_fwd(self, z, gamma, beta, y, mean, rstd, eps=1e-5, momentum=0.1, p=0.0, seed=0,
+                   offset=0, running_mean=None, running_var=None):
+        """y = dropout(relu(BatchNorm(z))) from the batch's statistics; mean / rstd [F] are
+        saved for the backward, running_mean / running_var [F] updated when given."""
+        rows, F = z.shape
+        check(self.lib.nts_hip_bn_act_fwd(self.h, rows, F, ptr(z), z.stride(0), ptr(gamma),
+                                          ptr(beta), float(eps), float(momentum), float(p),
+                                          int(seed), int(offset), ptr(y), y.stride(0), ptr(mean),
+                                          ptr(rstd), ptr(running_mean), ptr(running_var)))
+
+    def bn_act_eval(self, z, gamma, beta, running_mean, running_var, y, eps=1e-5):
+        """y = relu(BatchNorm(z)) from the running statistics; nothing is updated."""
+        rows, F = z.shape
+        check(self.lib.nts_hip_bn_act_eval(self.h, rows, F, ptr(z), z.stride(0), ptr(gamma),
+                                           ptr(beta), ptr(running_mean), ptr(running_var),
+                                           float(eps), ptr(y), y.stride(0)))
+
+    def bn_act_bwd(self, dy, y, z, mean, rstd, gamma, scale, dz, dgamma, dbeta):
+        rows, F = z.shape
+        check(self.lib.nts_hip_bn_act_bwd(self.h, rows, F, ptr(dy), dy.stride(0), ptr(y),
+                                          y.stride(0), ptr(z), z.stride(0), ptr(mean), ptr(rstd),
+                                          ptr(gamma), float(scale), ptr(dz), dz.stride(0),
+                                          ptr(dgamma), ptr(dbeta)))
+
     def gemm_gather(self, A, rows, B, C):
         """C = A[rows] @ B (rows: int32 device tensor of row ids)."""
         M, K, N = rows.numel(), A.shape[1], B.shape[1]

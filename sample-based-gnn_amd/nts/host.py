@@ -52,7 +52,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                multi_label=False, root_weight=False, aggregator="sum", epsilon=1e-9,
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
                gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False,
-               weighted_sampling=False, edge_weighted=False):
+               weighted_sampling=False, edge_weighted=False, batch_norm=False,
+               batch_norm_eps=1e-5, batch_norm_momentum=0.1):
     if weighted_sampling:  # neighbours drawn in proportion to the graph's edge_prob
         if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
             raise ValueError("weighted_sampling is not supported with an MT19937 rng_mode (it "
@@ -122,6 +123,10 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
         c.weighted_sampling = True
     if edge_weighted:  # edge_prob as aggregation coefficients; refusals: the driver
         c.edge_weighted = True
+    if batch_norm:  # BatchNorm on the hidden layers; refusals: the driver
+        c.batch_norm = True
+    c.batch_norm_eps = float(batch_norm_eps)
+    c.batch_norm_momentum = float(batch_norm_momentum)
     c.pd_cache = bool(pd_cache)
     c.pd_rate = float(pd_rate)
     c.pd_super_batch = int(pd_super_batch)

@@ -260,6 +260,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("aggregator", &GCNConfig::aggregator)
       .def_readwrite("layer_norm", &GCNConfig::layer_norm)
       .def_readwrite("layer_norm_eps", &GCNConfig::layer_norm_eps)
+      .def_readwrite("batch_norm", &GCNConfig::batch_norm)
+      .def_readwrite("batch_norm_eps", &GCNConfig::batch_norm_eps)
+      .def_readwrite("batch_norm_momentum", &GCNConfig::batch_norm_momentum)
       .def_readwrite("feature_f16", &GCNConfig::feature_f16)
       .def_readwrite("weighted_sampling", &GCNConfig::weighted_sampling)
       .def_readwrite("edge_weighted", &GCNConfig::edge_weighted)
@@ -349,6 +352,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("nids"))
       .def_readonly("full_agg_ms", &GCN_SAMPLE_ALLGPU_impl::full_agg_ms)
       .def("weights", &GCN_SAMPLE_ALLGPU_impl::weights)
+      .def("norm_stats", &GCN_SAMPLE_ALLGPU_impl::norm_stats)
+      .def("set_norm_stats", &GCN_SAMPLE_ALLGPU_impl::set_norm_stats)
       .def("reset_stats", &GCN_SAMPLE_ALLGPU_impl::reset_stats)
       .def("set_diag_reuse_sample", &GCN_SAMPLE_ALLGPU_impl::set_diag_reuse_sample)
       .def("resolve_profile",

@@ -1361,6 +1361,75 @@ NtsVar hip_ln_act(const NtsVar& z, const NtsVar& gamma, const NtsVar& beta, doub
                            reinterpret_cast<int64_t>(cs), train);
 }
 
+// dropout(relu(BatchNorm(z))) from the batch's statistics (nts_hip_bn_act_fwd:
+// statistics, running-buffer update and the apply pass); backward dz, dgamma,
+// dbeta in a reduction and an apply pass (nts_hip_bn_act_bwd).
+struct HipBnActFn : public torch::autograd::Function<HipBnActFn> {
+  static NtsVar forward(AutogradContext* ctx, NtsVar z, NtsVar gamma, NtsVar beta,
+                        NtsVar running_mean, NtsVar running_var, double eps, double momentum,
+                        double p, int64_t seed, int64_t offset, int64_t cs_ptr) {
+    auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
+    NtsVar zc = row_major(z), gc = gamma.contiguous(), bc = beta.contiguous();
+    const int64_t M = zc.size(0), N = zc.size(1);
+    TORCH_CHECK(gc.numel() == N && bc.numel() == N, "hip_bn_act: shape mismatch");
+    NtsVar y = torch::empty({M, N}, zc.options());
+    NtsVar mean = torch::empty({N}, zc.options()), rstd = torch::empty({N}, zc.options());
+    hip_check(nts_hip_bn_act_fwd(cs->ctx(), (uint64_t)M, (uint32_t)N, zc.data_ptr<float>(),
+                                 (uint64_t)zc.stride(0), gc.data_ptr<float>(),
+                                 bc.data_ptr<float>(), (float)eps, (float)momentum, (float)p,
+                                 (uint64_t)seed, (uint64_t)offset, y.data_ptr<float>(), (uint64_t)N,
+                                 mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                                 running_mean.data_ptr<float>(), running_var.data_ptr<float>()),
+              "nts_hip_bn_act_fwd");
+    ctx->save_for_backward({zc, y, mean, rstd, gc});
+    ctx->saved_data["cs"] = cs_ptr;
+    ctx->saved_data["scale"] = p < 1.0 ? (double)(1.0f / (1.0f - (float)p)) : 0.0;
+    return y;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    NtsVar z = saved[0], y = saved[1], mean = saved[2], rstd = saved[3], gamma = saved[4];
+    auto* cs = reinterpret_cast<NtsStream*>(ctx->saved_data["cs"].toInt());
+    NtsVar g = grads[0].contiguous();
+    const int64_t M = y.size(0), N = y.size(1);
+    NtsVar dz = torch::empty({M, N}, y.options());
+    NtsVar dgamma = torch::empty({N}, y.options()), dbeta = torch::empty({N}, y.options());
+    hip_check(nts_hip_bn_act_bwd(cs->ctx(), (uint64_t)M, (uint32_t)N, g.data_ptr<float>(),
+                                 (uint64_t)N, y.data_ptr<float>(), (uint64_t)N,
+                                 z.data_ptr<float>(), (uint64_t)z.stride(0),
+                                 mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                                 gamma.data_ptr<float>(),
+                                 (float)ctx->saved_data["scale"].toDouble(), dz.data_ptr<float>(),
+                                 (uint64_t)N, dgamma.data_ptr<float>(), dbeta.data_ptr<float>()),
+              "nts_hip_bn_act_bwd");
+    return {dz,       dgamma,   dbeta,    NtsVar(), NtsVar(), NtsVar(),
+            NtsVar(), NtsVar(), NtsVar(), NtsVar(), NtsVar()};
+  }
+};
+
+NtsVar hip_bn_act(const NtsVar& z, const NtsVar& gamma, const NtsVar& beta,
+                  const NtsVar& running_mean, const NtsVar& running_var, bool train, double eps,
+                  double momentum, double p, uint64_t seed, uint64_t offset, NtsStream* cs) {
+  const int64_t N = z.size(1);
+  TORCH_CHECK(running_mean.is_contiguous() && running_var.is_contiguous() &&
+                  running_mean.numel() == N && running_var.numel() == N,
+              "hip_bn_act: running statistics must be contiguous [F]");
+  if (train)
+    return HipBnActFn::apply(z, gamma, beta, running_mean, running_var, eps, momentum, p,
+                             (int64_t)seed, (int64_t)offset, reinterpret_cast<int64_t>(cs));
+  // eval: the running statistics, one elementwise pass, no graph
+  torch::NoGradGuard ng;
+  NtsVar zc = row_major(z), gc = gamma.contiguous(), bc = beta.contiguous();
+  TORCH_CHECK(gc.numel() == N && bc.numel() == N, "hip_bn_act: shape mismatch");
+  NtsVar y = torch::empty({zc.size(0), N}, zc.options());
+  hip_check(nts_hip_bn_act_eval(cs->ctx(), (uint64_t)zc.size(0), (uint32_t)N, zc.data_ptr<float>(),
+                                (uint64_t)zc.stride(0), gc.data_ptr<float>(), bc.data_ptr<float>(),
+                                running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
+                                (float)eps, y.data_ptr<float>(), (uint64_t)N),
+            "nts_hip_bn_act_eval");
+  return y;
+}
+
 void set_bottom_gemm_hooks(std::function<void()> after_fwd_gemm,
                            std::function<void()> before_bwd_gemm) {
   g_after_fwd_gemm = std::move(after_fwd_gemm);

@@ -109,7 +109,8 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // (a table that stays in the Infinity Cache) instead of F_in-wide feature
   // rows, at the price of a GEMM over the src rows instead of the dst rows.
   const bool tf_ok = L >= 2 && !cfg.gat && !fcache && cfg.hip_gemm && cfg.fuse_activation &&
-                     !cfg.pd_cache && !cfg.root_weight && !max_aggr() && !cfg.layer_norm;
+                     !cfg.pd_cache && !cfg.root_weight && !max_aggr() && !cfg.layer_norm &&
+                     !cfg.batch_norm;
   // auto (-1): transform first where the first layer narrows the rows at
   // least 4x and its GEMMs run on the whole-row fp32-exact kernels
   // (csrc/gemmx3.hip, split-bf16) or the f16 pair tables (C2: 602 -> 128,
@@ -348,7 +349,7 @@ void GCN_SAMPLE_ALLGPU_impl::init_nn() {
   }
   if (cfg.hip_gemm)
     for (auto* p : P) p->cs = cs.get();
-  if (cfg.layer_norm)  // gamma = 1, beta = 0 per hidden layer; never decayed
+  if (cfg.layer_norm || cfg.batch_norm)  // gamma = 1, beta = 0 per hidden layer; never decayed
     for (size_t i = 0; i + 2 < cfg.layer_size.size(); ++i)
       for (float init : {1.f, 0.f}) {
         auto* q = new Parameter(1, (size_t)cfg.layer_size[i + 1], cfg.learn_rate, cfg.beta1,
@@ -359,6 +360,10 @@ void GCN_SAMPLE_ALLGPU_impl::init_nn() {
         q->V = torch::zeros_like(q->W).set_requires_grad(false);
         LN.push_back(q);
       }
+  if (cfg.batch_norm)  // running_mean = 0, running_var = 1 per hidden layer
+    for (size_t i = 0; i + 2 < cfg.layer_size.size(); ++i)
+      for (float init : {0.f, 1.f})
+        BN.push_back(torch::full({(int64_t)cfg.layer_size[i + 1]}, init, f32_opts(graph->device)));
   int64_t n = 0;
   for (auto* p : params()) n += p->W.numel();
   grad_bucket = torch::zeros({n}, f32_opts(graph->device));
@@ -390,6 +395,23 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::weights() {
   return out;
 }
 
+std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::norm_stats() {
+  auto guard = cs->guard();
+  std::vector<NtsVar> out;
+  for (const auto& b : BN) out.push_back(b.clone());
+  cs->synchronize();
+  return out;
+}
+
+void GCN_SAMPLE_ALLGPU_impl::set_norm_stats(const std::vector<NtsVar>& stats) {
+  auto guard = cs->guard();
+  TORCH_CHECK(stats.size() == BN.size(), "running_mean and running_var of every hidden layer "
+                                         "(the list of norm_stats(): ", BN.size(), " tensors), got ",
+              stats.size());
+  torch::NoGradGuard ng;
+  for (size_t i = 0; i < BN.size(); ++i) BN[i].copy_(stats[i].view_as(BN[i]));
+}
+
 // vertexForward (toolkits/GCN_SAMPLE_GPU.hpp:252-266): hidden layers
 // dropout(relu(XW)), the last layer log_softmax(XW).
 NtsVar GCN_SAMPLE_ALLGPU_impl::vertexForward(int l, NtsVar& a) {
@@ -398,6 +420,9 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::vertexForward(int l, NtsVar& a) {
     return cfg.multi_label ? P[l]->forward(a) : P[l]->forward(a).log_softmax(1);
   if (cfg.layer_norm)  // the plain GEMM, then LayerNorm + relu + dropout in one pass
     return layer_norm_act(l, P[l]->forward(a), drop_rate(), dropout_calls_++);
+  if (cfg.batch_norm)  // the plain GEMM, then BatchNorm + relu + dropout; eval draws no offset
+    return batch_norm_act(l, P[l]->forward(a), drop_rate(),
+                          ctx.is_train() ? dropout_calls_++ : 0);
   if (cfg.hip_gemm && cfg.fuse_activation)
     return hip_linear_act(a, P[l]->W, drop_rate(), dropout_key(), dropout_calls_++, cs.get(),
                           cfg.pair_table > 0);
@@ -1024,19 +1049,23 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
       const NtsVar& W = P[l]->W;
       // layer_norm: the hidden layer's activation is the fused LayerNorm pass
       // over A X W, whichever way the (linear) product was formed
-      const bool ln = cfg.layer_norm && !last;
+      // batch_norm: the eval pass on the running statistics, in the same places
+      const bool ln = (cfg.layer_norm || cfg.batch_norm) && !last;
+      auto norm_act = [&](const NtsVar& Z) {
+        return cfg.batch_norm ? batch_norm_act(l, Z, 0.0, 0) : layer_norm_act(l, Z, 0.0, 0);
+      };
       // (feature_f16: layer 0 aggregates first, from the half table: no fp32 copy of it)
       const bool half_in = X.dtype() == torch::kFloat16;
       if (!cfg.root_weight && !max_aggr() && !half_in && W.size(0) > W.size(1)) {  // transform first: act(A (X W)), the relu in the kernel
         NtsVar H = P[l]->forward(X);
         NtsVar Y = aggregate(H, !last && !ln);
-        X = ln ? layer_norm_act(l, Y, 0.0, 0) : last && !cfg.multi_label ? Y.log_softmax(1) : Y;
+        X = ln ? norm_act(Y) : last && !cfg.multi_label ? Y.log_softmax(1) : Y;
       } else {  // aggregate first: act((A X) W)
         NtsVar Y = aggregate(X, false);
         if (last)
           X = cfg.multi_label ? P[l]->forward(Y) : P[l]->forward(Y).log_softmax(1);
         else if (ln)
-          X = layer_norm_act(l, P[l]->forward(Y), 0.0, 0);
+          X = norm_act(P[l]->forward(Y));
         else if (cfg.hip_gemm && cfg.fuse_activation)  // p = 0: no mask, no offset drawn
           X = hip_linear_act(Y, W, 0.0, 0, 0, cs.get(), false);
         else

@@ -93,6 +93,23 @@ struct GCNConfig {
   // transform_first = 1, pair_table > 0 or a hidden width above 1024.
   bool layer_norm = false;
   float layer_norm_eps = 1e-5f;
+  // BatchNorm on every hidden layer (no reference counterpart),
+  // torch.nn.BatchNorm1d's semantics: layer l < L-1 is
+  // X' = dropout(relu(BatchNorm((A X) W_l; gamma_l, beta_l))) over the plain
+  // GEMM's output (nts_hip_bn_act_*; fuse_activation has no effect there), the
+  // statistics taken over the rows of the layer's block in this batch; the
+  // last layer is unchanged.  gamma_l (ones) and beta_l (zeros) are parameters
+  // as under layer_norm (Adam steps without weight decay, after the W's in
+  // weights()); running_mean_l (zeros) and running_var_l (ones) are buffers
+  // (norm_stats()) that training moves by batch_norm_momentum and that
+  // evaluate(), forward_eval() and infer_full() read without updating.  Per
+  // rank under data parallelism (no SyncBatchNorm; nothing joins the
+  // all-reduce).  Aggregate-first only (transform_first = -1 resolves to 0).
+  // Not with gat, pd_cache, transform_first = 1, pair_table > 0, layer_norm or
+  // a hidden width above 1024.
+  bool batch_norm = false;
+  float batch_norm_eps = 1e-5f;
+  float batch_norm_momentum = 0.1f;
   // f16 feature table: the table is kept in HBM as IEEE half and
   // every gather of it (the bottom aggregation, early or in the step; the row
   // gather of fused_gather = false; infer_full()'s layer 0) widens the rows to
@@ -269,8 +286,14 @@ class GCN_SAMPLE_ALLGPU_impl {
   std::pair<std::vector<uint32_t>, std::vector<uint32_t>> presample();
   void set_presample(const std::vector<uint32_t>& counts, const std::vector<uint32_t>& ids);
   uint64_t pd_hits = 0;  // bottom-layer dsts served from the PD cache (host count, sampled batches)
-  // [W_0 .. W_{L-1}], then with cfg.layer_norm [gamma_0, beta_0, gamma_1, beta_1, ...]
+  // [W_0 .. W_{L-1}], then with cfg.layer_norm or cfg.batch_norm
+  // [gamma_0, beta_0, gamma_1, beta_1, ...]
   std::vector<NtsVar> weights();
+  // cfg.batch_norm: the running statistics of the hidden layers,
+  // [running_mean_0, running_var_0, running_mean_1, ...] (copies; empty without
+  // the option), and their replacement by a list of the same shapes
+  std::vector<NtsVar> norm_stats();
+  void set_norm_stats(const std::vector<NtsVar>& stats);
   void reset_stats();
   void resolve_profile() { prof.resolve(); }
 
@@ -283,9 +306,12 @@ class GCN_SAMPLE_ALLGPU_impl {
   std::unique_ptr<FastSampler> sampler;
   std::unique_ptr<FeatureCache> fcache;  // two-tier feature table (cache_rate)
   std::vector<Parameter*> P;
-  // cfg.layer_norm: gamma_0, beta_0, gamma_1, beta_1, ... of the hidden layers
-  // (apart from P, whose size is the layer count)
+  // cfg.layer_norm or cfg.batch_norm: gamma_0, beta_0, gamma_1, beta_1, ... of
+  // the hidden layers (apart from P, whose size is the layer count)
   std::vector<Parameter*> LN;
+  // cfg.batch_norm: running_mean_0, running_var_0, running_mean_1, ... (buffers:
+  // no gradient, no Adam step, not in the gradient bucket or the all-reduce)
+  std::vector<NtsVar> BN;
   ctx::NtsContext ctx;
   // statistics
   double sample_time = 0, train_time = 0;
@@ -325,6 +351,13 @@ class GCN_SAMPLE_ALLGPU_impl {
   NtsVar layer_norm_act(int l, const NtsVar& Z, double p, uint64_t offset) {
     return hip_ln_act(Z, LN[2 * (size_t)l]->W, LN[2 * (size_t)l + 1]->W, cfg.layer_norm_eps, p,
                       dropout_key(), offset, cs.get());
+  }
+  // hidden layer l's BatchNorm + relu + dropout: in training mode the batch's
+  // statistics (and the buffers move), otherwise the running statistics
+  NtsVar batch_norm_act(int l, const NtsVar& Z, double p, uint64_t offset) {
+    return hip_bn_act(Z, LN[2 * (size_t)l]->W, LN[2 * (size_t)l + 1]->W, BN[2 * (size_t)l],
+                      BN[2 * (size_t)l + 1], ctx.is_train(), cfg.batch_norm_eps,
+                      cfg.batch_norm_momentum, p, dropout_key(), offset, cs.get());
   }
   void Update();
   bool defer_ = false;            // overlap_allreduce in effect

@@ -602,6 +602,14 @@ NtsVar hip_relu_dropout(const NtsVar& x, double p, uint64_t seed, uint64_t offse
 // nothing otherwise (eval / inference)
 NtsVar hip_ln_act(const NtsVar& z, const NtsVar& gamma, const NtsVar& beta, double eps, double p,
                   uint64_t seed, uint64_t offset, NtsStream* cs);
+// dropout(relu(BatchNorm(z; gamma, beta, eps)), p) as one autograd op
+// (nts_hip_bn_act_*, the same mask keys).  train: the batch's statistics, the
+// running buffers [F] updated in place by `momentum`, and z, y, mean, rstd and
+// gamma saved for the backward (gradients for z, gamma and beta).  Otherwise
+// the eval kernel on the running buffers: no dropout, nothing saved or updated.
+NtsVar hip_bn_act(const NtsVar& z, const NtsVar& gamma, const NtsVar& beta,
+                  const NtsVar& running_mean, const NtsVar& running_var, bool train, double eps,
+                  double momentum, double p, uint64_t seed, uint64_t offset, NtsStream* cs);
 
 // Transform-first bottom layer (nts_hip.h): X1 = dropout(relu(A (X[source] W)))
 // on the layer's sampled block `sg` (its CSR is needed for the backward);

@@ -162,6 +162,21 @@ void check_driver_options(const GCNConfig& cfg, const DriverInputs& in) {
             {!(cfg.cache_rate < 0.0), "cache_rate >= 0"},
             {!cfg.deterministic_backward,
              "deterministic_backward = false (the backward reads the CSR's weights)"}});
+  // (transform_first = 1 passes the tf_ok row above: this table's own text reports it)
+  if (cfg.batch_norm) {
+    std::vector<Refusal> rows = {
+        {cfg.gat, "gat (GCN / GraphSAGE layers only)"},
+        {cfg.pd_cache, "pd_cache"},
+        {cfg.transform_first == 1,
+         "transform_first = 1 (BatchNorm does not commute with A: aggregate-first only)"},
+        {cfg.pair_table > 0, "pair_table > 0"},
+        {cfg.layer_norm, "layer_norm (one normalisation per hidden layer)"},
+    };
+    for (size_t l = 1; l + 1 < cfg.layer_size.size(); ++l)
+      rows.push_back({cfg.layer_size[l] > 1024, c10::str("a hidden width above 1024 (layer ", l - 1,
+                                                         ": ", cfg.layer_size[l], ")")});
+    refuse("batch_norm is not supported with ", rows);
+  }
 }
 
 }  // namespace nts

@@ -61,6 +61,12 @@ GAT_ATTN_DROP:0.6 / GAT_FEAT_DROP:0.6 (GAT algorithms): dropout of the attention
 coefficients and of every layer's input while training, fused into the GAT
 kernels.  DROP_RATE is not read by a GAT job (as in the reference).
 
+BATCH_NORM:1 (GCN / GraphSAGE algorithms without PD cache; not with
+LAYER_NORM): every hidden layer is dropout(relu(BatchNorm1d(.))) with the
+statistics of the batch's rows while training and the running statistics
+(momentum 0.1) in the evaluation passes and under FULL_INFERENCE; a gamma and a
+beta per hidden layer are trained without weight decay.
+
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
 """
@@ -182,6 +188,11 @@ def refuse_cfg(info: dataloader.InputInfo):
          "(Philox-sampled algorithms only)"),
         (weighted and info.sample_shared,
          "SAMPLE_WEIGHTED is not supported with SAMPLE_SHARED:1 (one selection rule per job)"),
+        (info.batch_norm and (gat or pd),
+         "BATCH_NORM is not supported with GAT or PD-cache algorithms (GCN / GraphSAGE layers "
+         "only)"),
+        (info.batch_norm and info.layer_norm,
+         "BATCH_NORM is not supported with LAYER_NORM:1 (one normalisation per hidden layer)"),
     )
     for hit, text in rows:
         if hit:
@@ -212,7 +223,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         gat_feat_drop=info.gat_feat_drop, gat_v2=bool(info.gat_v2),
         shared_sampling=bool(info.sample_shared), feature_f16=bool(info.feature_f16),
         weighted_sampling=bool(info.sample_weighted),
-        edge_weighted=bool(info.edge_weight_agg), seed=info.seed)
+        edge_weighted=bool(info.edge_weight_agg), seed=info.seed,
+        batch_norm=bool(info.batch_norm))
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
