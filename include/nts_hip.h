@@ -49,7 +49,9 @@ extern "C" {
                                       nts_hip_spmm_csc_fwd_act_bits,
                                       nts_hip_spmm_csr_bwd_postmask_bits);
                                   11: MT19937 re-run of a short stream (nts_hip_mt_budget_scale,
-                                      nts_hip_mt_checkpoint, nts_hip_mt_rewind) */
+                                      nts_hip_mt_checkpoint, nts_hip_mt_rewind);
+                                      later entry points (nts_hip_lp_* among them) are
+                                      additions: no struct or existing signature changed */
 
 /* status codes */
 #define NTS_OK 0
@@ -1018,6 +1020,70 @@ int nts_hip_linear_bce_train(nts_hip_ctx *ctx, const float *Y, uint64_t ldy, int
                              const float *W, int C, const uint32_t *label_bits, uint32_t wpr,
                              const uint32_t *index, float *loss, float *dY, float *dW,
                              uint32_t *counts);
+
+/* ---- link prediction (csrc/linkpred.hip; no counterpart in the reference) --
+ * The semantics of DGL's as_edge_prediction_sampler with negative_sampler.Uniform
+ * and of PyG's LinkNeighborLoader, on the device.
+ *
+ * nts_hip_lp_batch: the pairs and the seed set of one batch.  pos_src / pos_dst
+ * [B] hold the global ids (< n_vertices) of the positive edges.  Negative
+ * (i, k), k < K, keeps the head pos_src[i]; its tail is
+ *   x    = word k % 4 of Philox4x32-10(counter = (k / 4, i, 0x20000000, lo32(batch_seq)),
+ *                                      key = (lo32(seed), hi32(seed) ^ hi32(batch_seq)))
+ *   tail = (uint64(x) * n_vertices) >> 32
+ * i.e. the sampler's counter layout with a layer tag of its own beside
+ * 0x80000000 (PHILOX_SHARED) and 0x40000000 (weighted).  Negatives are NOT
+ * filtered against the graph's true edges (a negative may be a real edge or a
+ * self pair); the tail's bias from uniform is at most n_vertices / 2^32.
+ * Pairs are numbered p < B for the positives, then B + i K + k: P = B (1 + K).
+ * Outputs (device, caller-owned):
+ *   destination [v_cap]   the distinct endpoint ids, ascending; entries past
+ *                         *v_size are not written
+ *   v_size                device scalar: their count
+ *   pair_u, pair_v [P]    the two ends of every pair as rows of destination
+ *   inc_offset [v_cap+1], inc_slot [2 P]   the incidence CSR over those rows:
+ *                         slot 2p is the u-end and 2p + 1 the v-end of pair p,
+ *                         each row's slots ascending (a pair with u == v has both
+ *                         slots on one row); rows past *v_size are empty
+ *                         (offset 2 P).
+ * destination / v_size are what nts_sampcsc_dev takes as a layer's input.
+ * Scratch comes from the context arena; nts_hip_ctx_reserve(V, 8 P) beforehand
+ * keeps the call allocation-free.
+ * NTS_ERR_INVALID, before any write: a NULL pointer, K < 1, B == 0,
+ * v_cap < 2 P, P > 2^30, n_vertices outside 1..2^32. */
+int nts_hip_lp_batch(nts_hip_ctx *ctx, const uint32_t *pos_src, const uint32_t *pos_dst,
+                     uint32_t B, uint32_t K, uint64_t n_vertices, uint64_t batch_seq,
+                     uint32_t v_cap, uint32_t *destination, uint32_t *v_size, uint32_t *pair_u,
+                     uint32_t *pair_v, uint32_t *inc_offset, uint32_t *inc_slot);
+/* Dot-product scores and the mean sigmoid BCE of the P = B (1 + K) pairs:
+ *   score[p] = <H[pair_u[p], 0:D], H[pair_v[p], 0:D]>   H fp32 [rows x ldh], 1 <= D <= 1024
+ *   loss     = mean_p (max(s, 0) - s y + log1p(exp(-|s|))),   y = 1 for p < B, else 0.
+ * mrr != NULL: a device pair of floats, mrr[0] += sum_i 1 / rank_i and
+ * mrr[1] += B, with rank_i = 1 + #{k : score(neg i,k) >= score(pos i)} (ties
+ * count against the positive); MRR = mrr[0] / mrr[1].  Both sums are fp32 in
+ * a fixed order: consecutive runs of 16 positives summed ascending into one
+ * partial each, the partials summed ascending.  NULL: no MRR counting.
+ * 16-byte row loads when D % 4 == 0, ldh % 4 == 0 and H is 16-byte aligned,
+ * scalar loads otherwise.
+ * NTS_ERR_INVALID, before any write: a NULL pointer (mrr apart), D outside
+ * 1..1024, ldh < D, B == 0, K == 0. */
+int nts_hip_lp_bce_fwd(nts_hip_ctx *ctx, const float *H, uint64_t ldh, uint32_t D,
+                       const uint32_t *pair_u, const uint32_t *pair_v, uint32_t B, uint32_t K,
+                       float *score, float *loss, float *mrr);
+/* Training call: the same scores, loss and counter (bit-identical to
+ * nts_hip_lp_bce_fwd) AND the gradient for an upstream gradient of exactly 1:
+ *   g_p = (sigmoid(s_p) - y_p) / P
+ *   dH[r, 0:D] = sum over row r's incidence slots, in ascending slot order, of
+ *                g_pair * H[other end of the pair, 0:D]        for r < *v_size
+ * (inc_offset / inc_slot / v_size from nts_hip_lp_batch).  A gather over the
+ * incidence CSR: no floating-point atomics, two runs give the same bits.  Rows
+ * r >= *v_size of dH, and columns >= D, are not touched.
+ * Also NTS_ERR_INVALID: lddh < D, v_cap == 0. */
+int nts_hip_lp_bce_train(nts_hip_ctx *ctx, const float *H, uint64_t ldh, uint32_t D,
+                         const uint32_t *pair_u, const uint32_t *pair_v, uint32_t B, uint32_t K,
+                         const uint32_t *inc_offset, const uint32_t *inc_slot,
+                         const uint32_t *v_size, uint32_t v_cap, float *score, float *loss,
+                         float *dH, uint64_t lddh, float *mrr);
 
 /* ---- GraphSAGE root weight (csrc/aggregate.hip; no counterpart in the reference) --
  * The graph op of X' = act([A X | X_dst] W), W = [W_n; W_s] stacked on K.

@@ -70,6 +70,7 @@ EXPORTED = (
     "nts_hip_sample_layer_weighted", "nts_hip_weighted_keys",
     "nts_hip_sample_layer_coef", "nts_hip_spmm_graph_fwd_coef", "nts_hip_spmm_graph_fwd_coef_h",
     "nts_hip_bn_act_fwd", "nts_hip_bn_act_eval", "nts_hip_bn_act_bwd",
+    "nts_hip_lp_batch", "nts_hip_lp_bce_fwd", "nts_hip_lp_bce_train",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -232,6 +233,10 @@ def lib() -> C.CDLL:
         "nts_hip_bn_act_fwd": ([P, U64, U32, P, U64, P, P, F, F, F, U64, U64, P, U64, P, P, P, P], I),
         "nts_hip_bn_act_eval": ([P, U64, U32, P, U64, P, P, P, P, F, P, U64], I),
         "nts_hip_bn_act_bwd": ([P, U64, U32, P, U64, P, U64, P, U64, P, P, P, F, P, U64, P, P], I),
+        # link prediction
+        "nts_hip_lp_batch": ([P, P, P, U32, U32, U64, U64, U32, P, P, P, P, P, P], I),
+        "nts_hip_lp_bce_fwd": ([P, P, U64, U32, P, P, U32, U32, P, P, P], I),
+        "nts_hip_lp_bce_train": ([P, P, U64, U32, P, P, U32, U32, P, P, P, U32, P, P, P, U64, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

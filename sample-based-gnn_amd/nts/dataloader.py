@@ -416,6 +416,12 @@ class InputInfo:
     edge_weight_agg: int = 0
     # SEED (this build's key): the driver's seed (sampler streams, dropout)
     seed: int = 2000
+    # NEG_PER_POS / VAL_EDGE_RATE (this build's keys, ALGORITHM:LINKPREDSAMPLE):
+    # uniform negatives drawn per positive edge of a batch, and the share of the
+    # edge list (chosen by SEED) held out of the training pairs for the
+    # validation MRR.  Held-out edges stay in the message-passing graph
+    neg_per_pos: int = 1
+    val_edge_rate: float = 0.1
     extra: dict = field(default_factory=dict)
 
     @property
@@ -456,6 +462,8 @@ class InputInfo:
             "SAMPLE_WEIGHTED": ("sample_weighted", int),
             "EDGE_WEIGHT_AGG": ("edge_weight_agg", int),
             "SEED": ("seed", int),
+            "NEG_PER_POS": ("neg_per_pos", int),
+            "VAL_EDGE_RATE": ("val_edge_rate", float),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

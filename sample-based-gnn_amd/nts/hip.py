@@ -718,6 +718,30 @@ class HipContext:
                                                 ptr(index), ptr(loss), ptr(dY), ptr(dW),
                                                 ptr(counts)))
 
+    def lp_batch(self, pos_src, pos_dst, K, n_vertices, batch_seq, destination, v_size, pair_u,
+                 pair_v, inc_offset, inc_slot):
+        """One link-prediction batch: K Philox negatives per
+        positive, the distinct endpoints (ascending) as `destination`/`v_size`,
+        the pairs as rows of it and the incidence CSR.  int32 device tensors."""
+        check(self.lib.nts_hip_lp_batch(self.h, ptr(pos_src), ptr(pos_dst), pos_src.numel(), K,
+                                        n_vertices, batch_seq, destination.numel(),
+                                        ptr(destination), ptr(v_size), ptr(pair_u), ptr(pair_v),
+                                        ptr(inc_offset), ptr(inc_slot)))
+
+    def lp_bce_fwd(self, H, D, pair_u, pair_v, B, K, score, loss, mrr=None):
+        """score[p] = <H[pair_u[p], :D], H[pair_v[p], :D]>, the mean sigmoid BCE
+        (targets 1 for p < B) and, with `mrr` (float32 [2]), += (sum 1/rank, B)."""
+        check(self.lib.nts_hip_lp_bce_fwd(self.h, ptr(H), H.stride(0), D, ptr(pair_u), ptr(pair_v),
+                                          B, K, ptr(score), ptr(loss), ptr(mrr)))
+
+    def lp_bce_train(self, H, D, pair_u, pair_v, B, K, inc_offset, inc_slot, v_size, score, loss,
+                     dH, mrr=None):
+        """The same, and dH (rows < *v_size) gathered over the incidence CSR."""
+        check(self.lib.nts_hip_lp_bce_train(self.h, ptr(H), H.stride(0), D, ptr(pair_u),
+                                            ptr(pair_v), B, K, ptr(inc_offset), ptr(inc_slot),
+                                            ptr(v_size), inc_offset.numel() - 1, ptr(score),
+                                            ptr(loss), ptr(dH), dH.stride(0), ptr(mrr)))
+
     def adam(self, w, g, m, v, alpha, beta1, beta2, eps, wd, beta1_t, beta2_t, bias_correction):
         check(self.lib.nts_hip_adam(self.h, ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), alpha,
                                     beta1, beta2, eps, wd, beta1_t, beta2_t, int(bias_correction)))

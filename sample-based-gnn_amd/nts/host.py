@@ -32,11 +32,11 @@ def ext():
     return _ext
 
 
-def _checked(rule, *args):
+def _checked(rule, *args, **kwargs):
     """one of the driver's own rules (nts/host/options.cpp) at the time the
     config is made: its text, as a ValueError"""
     try:
-        rule(*args)
+        rule(*args, **kwargs)
     except RuntimeError as e:
         raise ValueError(str(e).splitlines()[0]) from None
 
@@ -53,7 +53,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
                gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False,
                weighted_sampling=False, edge_weighted=False, batch_norm=False,
-               batch_norm_eps=1e-5, batch_norm_momentum=0.1):
+               batch_norm_eps=1e-5, batch_norm_momentum=0.1, neg_per_pos=1):
     if weighted_sampling:  # neighbours drawn in proportion to the graph's edge_prob
         if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
             raise ValueError("weighted_sampling is not supported with an MT19937 rng_mode (it "
@@ -133,4 +133,20 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.shuffle = bool(shuffle)
     c.profile = bool(profile)
     c.seed = int(seed)
+    c.neg_per_pos = int(neg_per_pos)  # LinkPredictor only; no other driver reads it
     return c
+
+
+def link_predictor(graph, feature, train_edges, cfg):
+    """A LinkPredictor: `feature` fp32 [V, layers[0]] on the GPU,
+    `train_edges` int64 [2, n] on the host, `cfg` from gcn_config(...,
+    neg_per_pos=K).  Its option rules (check_link_pred_options) run before
+    anything is built; their text comes back as a ValueError."""
+    E = ext()
+    train_edges = torch.as_tensor(train_edges)
+    _checked(E.check_link_pred_options, cfg, **dict(
+        feature_dtype=feature.dtype, feature_on_gpu=feature.is_cuda,
+        feature_cols=feature.shape[1] if feature.dim() == 2 else -1,
+        edge_shape=list(train_edges.shape), edges_on_host=not train_edges.is_cuda,
+        n_vertices=int(graph.global_vertices), has_edge_prob=graph.edge_prob is not None))
+    return E.LinkPredictor(graph, feature, train_edges.to(torch.int64), cfg)

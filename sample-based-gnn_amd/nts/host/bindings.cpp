@@ -2,6 +2,7 @@
 #include <torch/extension.h>
 
 #include "gcn.hpp"
+#include "linkpred.hpp"
 #include "options.hpp"
 
 namespace py = pybind11;
@@ -154,6 +155,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            })
       .def_property("batch_seq", [](PySampler& p) { return p.s->batch_seq; },
                     [](PySampler& p, uint64_t v) { p.s->batch_seq = v; })
+      // the issue path seeded from device buffers (link prediction)
+      .def("issue_dev",
+           [](PySampler& p, const torch::Tensor& dest, const torch::Tensor& v_size, VertexId hint,
+              int slot, WeightType w) {
+             auto guard = p.cs->guard();
+             TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
+             p.s->issue_gpu_sample_dev(dest, v_size, hint, slot, *p.cs, w);
+           },
+           py::arg("dest"), py::arg("v_size"), py::arg("v_cap_live_hint"), py::arg("slot") = 0,
+           py::arg("weight_type") = WeightType::Sum)
       .def_property_readonly("work_offset", [](PySampler& p) { return p.s->work_offset; })
       .def_property_readonly("sampled_edges", [](PySampler& p) { return p.s->sampled_edges; });
 
@@ -279,7 +290,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("fuse_activation", &GCNConfig::fuse_activation)
       .def_readwrite("shuffle", &GCNConfig::shuffle)
       .def_readwrite("profile", &GCNConfig::profile)
-      .def_readwrite("seed", &GCNConfig::seed);
+      .def_readwrite("seed", &GCNConfig::seed)
+      .def_readwrite("neg_per_pos", &GCNConfig::neg_per_pos);
 
   // the constructor's option and shape rules on facts about its inputs: no
   // tensor, no device (RuntimeError with the rule's text as its first line)
@@ -297,6 +309,62 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("check_gat_heads", &check_gat_heads, py::arg("layer_size"), py::arg("gat"), py::arg("heads"));
   m.def("check_gat_v2", &check_gat_v2, py::arg("gat_v2"), py::arg("gat"));
   m.def("check_gat_drop", &check_gat_drop, py::arg("name"), py::arg("rate"), py::arg("gat"));
+
+  m.def(
+      "check_link_pred_options",
+      [](const GCNConfig& cfg, torch::ScalarType feature_dtype, bool feature_on_gpu,
+         int64_t feature_cols, std::vector<int64_t> edge_shape, bool edges_on_host,
+         int64_t n_vertices, bool has_edge_prob) {
+        check_link_pred_options(cfg, {feature_dtype, feature_on_gpu, feature_cols,
+                                      std::move(edge_shape), edges_on_host, n_vertices,
+                                      has_edge_prob});
+      },
+      py::arg("cfg"), py::kw_only(), py::arg("feature_dtype"), py::arg("feature_on_gpu"),
+      py::arg("feature_cols"), py::arg("edge_shape"), py::arg("edges_on_host"),
+      py::arg("n_vertices"), py::arg("has_edge_prob"));
+
+  // link prediction
+  py::class_<LinkPredictor>(m, "LinkPredictor")
+      .def(py::init([](std::shared_ptr<FullyRepGraph> g, torch::Tensor feature,
+                       const torch::Tensor& train_edges, GCNConfig cfg) {
+             return new LinkPredictor(g, feature, train_edges, cfg);
+           }),
+           py::arg("graph"), py::arg("feature"), py::arg("train_edges"), py::arg("cfg"))
+      .def("train_batch", &LinkPredictor::train_batch, py::call_guard<py::gil_scoped_release>())
+      .def("run_epoch", &LinkPredictor::run_epoch, py::call_guard<py::gil_scoped_release>())
+      .def("sample_not_finished", &LinkPredictor::has_batch)
+      .def("restart", &LinkPredictor::restart)
+      .def("weights", &LinkPredictor::weights)
+      .def("set_weights", &LinkPredictor::set_weights)
+      .def("evaluate", &LinkPredictor::evaluate, py::arg("edges"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("synchronize", &LinkPredictor::synchronize)
+      .def_property_readonly("loss", [](LinkPredictor& d) { return d.loss; })
+      .def_readonly("batches", &LinkPredictor::batches)
+      .def_readonly("train_seq", &LinkPredictor::train_seq)
+      // the last training step: its pair arrays and sampled blocks (tests)
+      .def("last_batch", [](LinkPredictor& d) {
+        TORCH_CHECK(d.last_sg, "last_batch before the first train_batch");
+        d.synchronize();
+        const LpBatch& b = d.batch;
+        const int64_t P = (int64_t)b.B * (1 + (int64_t)b.K);
+        const int64_t v = d.last_sg->sampled_sgs[0]->v_size;
+        py::dict o;
+        o["B"] = b.B;
+        o["K"] = b.K;
+        o["batch_seq"] = b.batch_seq;
+        o["pos_src"] = b.pos_src.narrow(0, 0, b.B);
+        o["pos_dst"] = b.pos_dst.narrow(0, 0, b.B);
+        o["v_size"] = v;
+        o["destination"] = b.destination.narrow(0, 0, v);
+        o["pair_u"] = b.pair_u.narrow(0, 0, P);
+        o["pair_v"] = b.pair_v.narrow(0, 0, P);
+        o["inc_offset"] = b.inc_offset.narrow(0, 0, v + 1);
+        o["inc_slot"] = b.inc_slot.narrow(0, 0, 2 * P);
+        o["score"] = b.score.narrow(0, 0, P);
+        o["layers"] = layers_of(d.last_sg);
+        return o;
+      });
 
   py::class_<GCN_SAMPLE_ALLGPU_impl>(m, "GCN_SAMPLE_ALLGPU_impl")
       .def(py::init([](std::shared_ptr<FullyRepGraph> g, torch::Tensor feature,

@@ -367,6 +367,54 @@ void FastSampler::issue_gpu_sample(int batch_size, int ssg_id, NtsStream& cs, We
   all_time += now_s() - t0;
 }
 
+// The same issue with the layer-0 destinations taken from the caller's device
+// buffers: `dest` holds the ids and *v_size_dev their count, both written by
+// work already enqueued on `cs` (a link-prediction batch's distinct endpoints,
+// nts_hip_lp_batch).  Nothing of sample_nids / work_offset is read or moved.
+void FastSampler::issue_gpu_sample_dev(const torch::Tensor& dest, const torch::Tensor& v_size_dev,
+                                       VertexId v_cap_live_hint, int ssg_id, NtsStream& cs,
+                                       WeightType w) {
+  double t0 = now_s();
+  TORCH_CHECK(!is_mt_mode(rng_mode), "issue_gpu_sample_dev: the MT19937 modes replay a host-ordered "
+              "stream (Philox and Philox-shared only)");
+  TORCH_CHECK(!omit_map, "issue_gpu_sample_dev is not supported with omit_map");
+  TORCH_CHECK(ssg_id >= 0 && ssg_id < (int)ssgs.size(), "ssg_id out of range");
+  TORCH_CHECK(dest.defined() && dest.is_cuda() && dest.scalar_type() == torch::kInt32 &&
+                  dest.is_contiguous() && v_size_dev.defined() && v_size_dev.is_cuda() &&
+                  v_size_dev.scalar_type() == torch::kInt32 && v_size_dev.numel() >= 1,
+              "issue_gpu_sample_dev: dest and v_size must be int32 device tensors");
+  TORCH_CHECK(v_cap_live_hint >= 1 && v_cap_live_hint <= batch_cap_ &&
+                  (int64_t)v_cap_live_hint <= dest.numel(),
+              "issue_gpu_sample_dev: the destination bound must be in 1..min(capacity, dest size)");
+  ssg = ssgs[ssg_id];
+  hipStream_t st = (hipStream_t)cs.stream();
+  if (ssgs.size() > 1) hip_rt(hipEventSynchronize(ssg->consumed), "hipEventSynchronize");
+  hip_rt(hipStreamWaitEvent(st, ssg->consumed, 0), "hipStreamWaitEvent");
+  int wt = w == WeightType::Sum           ? NTS_WEIGHT_SUM
+           : w == WeightType::Mean        ? NTS_WEIGHT_MEAN
+           : w == WeightType::MeanSampled ? NTS_WEIGHT_MEAN_SAMPLED
+                                          : NTS_WEIGHT_NONE;
+  if (up_degree && wt != NTS_WEIGHT_NONE) wt |= NTS_WEIGHT_UP_DEGREE;
+  IssueRec& r = recs_[ssg_id];
+  r.offset = 0;
+  r.actual = v_cap_live_hint;
+  r.batch_seq = batch_seq;
+  r.wt = wt;
+  r.omit_map = nullptr;
+  r.omit_key = 0;
+  r.omit_loc = nullptr;
+  r.cs = &cs;
+  r.dev_dest = dest;
+  r.dev_vsz = v_size_dev;
+  issued_.push_back(ssg_id);
+  enqueue_layers(ssg_id, r);
+  r.dev_dest = torch::Tensor();  // (the layer keeps its own view; nothing re-runs a Philox batch)
+  r.dev_vsz = torch::Tensor();
+  ssg->pending_batch = (int)v_cap_live_hint;
+  ++batch_seq;
+  all_time += now_s() - t0;
+}
+
 // the batch's sampling kernels (every layer) on the record's stream
 void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
   ssg = ssgs[ssg_id];
@@ -376,12 +424,13 @@ void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
   const int wt = r.wt;
   const VertexId actual = r.actual;
   const uint64_t bseq = r.batch_seq;
-  const VertexId* dst = dptr<VertexId>(dev_nids_) + r.offset;
+  const bool from_dev = r.dev_dest.defined();  // issue_gpu_sample_dev
+  const VertexId* dst = from_dev ? dptr<VertexId>(r.dev_dest) : dptr<VertexId>(dev_nids_) + r.offset;
   sampCSC* s0 = ssg->sampled_sgs[0];
   // layer-0 v_size as a device scalar without a per-batch memset: entry
   // `actual` of the device table 0..batch_cap
   (void)s0;
-  const VertexId* vsz = dptr<VertexId>(dev_iota_) + actual;
+  const VertexId* vsz = from_dev ? dptr<VertexId>(r.dev_vsz) : dptr<VertexId>(dev_iota_) + actual;
   for (int l = 0; l < layer; ++l) {
     sampCSC* s = ssg->sampled_sgs[l];
     nts_sampcsc_dev o{};
@@ -430,7 +479,8 @@ void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
     if (host_profile()) fprintf(stderr, "[host] sample_layer %d: %.1f us\n", l, (now_s() - tl) * 1e6);
     // the reference keeps the destination as a view of the previous source
     if (l == 0)
-      s->destination = dev_nids_.narrow(0, r.offset, std::max<int64_t>(actual, 0));
+      s->destination = from_dev ? r.dev_dest
+                                : dev_nids_.narrow(0, r.offset, std::max<int64_t>(actual, 0));
     else
       s->destination = ssg->sampled_sgs[l - 1]->source;
     dst = o.source;
@@ -1259,6 +1309,52 @@ struct HipLinearBceFn : public torch::autograd::Function<HipLinearBceFn> {
   }
 };
 }  // namespace
+
+namespace {
+struct HipLpBceFn : public torch::autograd::Function<HipLpBceFn> {
+  static NtsVar forward(AutogradContext* ctx, NtsVar h, int64_t pairs_ptr, NtsVar score,
+                        int64_t cs_ptr, bool train, int64_t mrr_ptr) {
+    const auto& pr = *reinterpret_cast<const LpPairs*>(pairs_ptr);
+    auto* cs = reinterpret_cast<NtsStream*>(cs_ptr);
+    auto* mrr = reinterpret_cast<float*>(mrr_ptr);
+    NtsVar hc = row_major(h);
+    const int64_t n = hc.size(0), D = hc.size(1);
+    const int64_t P = (int64_t)pr.B * (1 + (int64_t)pr.K);
+    TORCH_CHECK(score.is_cuda() && score.scalar_type() == torch::kFloat32 && score.numel() >= P,
+                "hip_lp_bce: score must hold one float per pair");
+    NtsVar loss = torch::empty({}, hc.options());
+    if (train) {
+      NtsVar dH = torch::empty({n, D}, hc.options());
+      hip_check(nts_hip_lp_bce_train(cs->ctx(), hc.data_ptr<float>(), (uint64_t)hc.stride(0),
+                                     (uint32_t)D, pr.pair_u, pr.pair_v, pr.B, pr.K, pr.inc_offset,
+                                     pr.inc_slot, pr.v_size, (uint32_t)n, score.data_ptr<float>(),
+                                     loss.data_ptr<float>(), dH.data_ptr<float>(), (uint64_t)D, mrr),
+                "nts_hip_lp_bce_train");
+      ctx->saved_data["dH"] = dH;
+    } else {
+      hip_check(nts_hip_lp_bce_fwd(cs->ctx(), hc.data_ptr<float>(), (uint64_t)hc.stride(0),
+                                   (uint32_t)D, pr.pair_u, pr.pair_v, pr.B, pr.K,
+                                   score.data_ptr<float>(), loss.data_ptr<float>(), mrr),
+                "nts_hip_lp_bce_fwd");
+    }
+    return loss;
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    TORCH_CHECK(ctx->saved_data.count("dH"), "hip_lp_bce: backward without a training forward");
+    NtsVar g = grads[0];
+    NtsVar dH = ctx->saved_data["dH"].toTensor();
+    if (g.data_ptr() != unit_scalar(g.device()).data_ptr()) dH = dH * g;  // d loss != the unit seed
+    ctx->saved_data.erase("dH");
+    return {dH, NtsVar(), NtsVar(), NtsVar(), NtsVar(), NtsVar()};
+  }
+};
+}  // namespace
+
+NtsVar hip_lp_bce(const NtsVar& h, const LpPairs& pairs, NtsVar& score, NtsStream* cs, float* mrr) {
+  const bool train = torch::GradMode::is_enabled() && h.requires_grad();
+  return HipLpBceFn::apply(h, reinterpret_cast<int64_t>(&pairs), score,
+                           reinterpret_cast<int64_t>(cs), train, reinterpret_cast<int64_t>(mrr));
+}
 
 NtsVar hip_linear_act(const NtsVar& x, const NtsVar& W, double p, uint64_t seed, uint64_t offset,
                       NtsStream* cs, bool pair_split) {

@@ -201,6 +201,9 @@ struct GCNConfig {
   double pd_rate = 0.2;
   int pd_super_batch = 4;
   int64_t seed = 2000;
+  // LinkPredictor only (nts/host/linkpred.hpp): uniform negatives
+  // drawn per positive edge of a batch.  No node-classification driver reads it.
+  int neg_per_pos = 1;
 };
 
 // Sampler-only throughput of the GPU sampler (SURVEY §8d "sampler-only"

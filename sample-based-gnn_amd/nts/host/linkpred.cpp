@@ -1,0 +1,230 @@
+// LinkPredictor: link prediction composed from the NtsContext ops.
+#include "linkpred.hpp"
+
+#include <algorithm>
+#include <random>
+
+namespace nts {
+
+namespace {
+constexpr uint64_t kEvalSeq = uint64_t(1) << 40;  // the evaluation stream, as in the GCN driver
+
+// int64 [2, n] host edges -> (heads, tails) as int32 device tensors
+std::pair<NtsVar, NtsVar> edges_to_device(const NtsVar& edges, int64_t n_vertices, int device,
+                                          const std::vector<int64_t>* order) {
+  TORCH_CHECK(edges.defined() && !edges.is_cuda() && edges.dim() == 2 && edges.size(0) == 2 &&
+                  edges.size(1) >= 1 && edges.scalar_type() == torch::kInt64,
+              "edges must be int64 [2, n] on the host, n >= 1");
+  NtsVar e = edges.contiguous();
+  TORCH_CHECK(e.min().item<int64_t>() >= 0 && e.max().item<int64_t>() < n_vertices,
+              "edge endpoints must be vertex ids in [0, V)");
+  if (order) e = e.index_select(1, torch::from_blob((void*)order->data(), {(int64_t)order->size()},
+                                                    torch::kInt64));
+  NtsVar d = e.to(torch::kInt32).to(torch::Device(torch::kCUDA, device));
+  return {d[0].contiguous(), d[1].contiguous()};
+}
+}  // namespace
+
+void LpBatch::alloc(int64_t b_cap, int K_, int device) {
+  const int64_t P = b_cap * (1 + (int64_t)K_);
+  pos_src = torch::empty({b_cap}, u32_opts(device));
+  pos_dst = torch::empty({b_cap}, u32_opts(device));
+  destination = torch::empty({2 * P}, u32_opts(device));
+  v_size = torch::zeros({1}, u32_opts(device));
+  pair_u = torch::empty({P}, u32_opts(device));
+  pair_v = torch::empty({P}, u32_opts(device));
+  score = torch::empty({P}, f32_opts(device));
+  inc_offset = torch::empty({2 * P + 1}, u32_opts(device));
+  inc_slot = torch::empty({2 * P}, u32_opts(device));
+  K = (uint32_t)K_;
+}
+
+LinkPredictor::LinkPredictor(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
+                             const NtsVar& train_edges, GCNConfig c)
+    : graph(std::move(g)), F(std::move(feature)), cfg(std::move(c)) {
+  check_link_pred_options(cfg, {F.scalar_type(), F.is_cuda(), F.dim() == 2 ? F.size(1) : -1,
+                                train_edges.sizes().vec(), !train_edges.is_cuda(),
+                                (int64_t)graph->global_vertices, graph->edge_prob.defined()});
+  cs = std::make_unique<NtsStream>(graph->device, nullptr, (uint64_t)cfg.seed);
+  hip_check(nts_hip_ctx_set_gemm_mode(cs->ctx(), cfg.gemm_mode), "nts_hip_ctx_set_gemm_mode");
+  // inputs were produced on other streams: order them before our stream
+  TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
+  auto guard = cs->guard();
+  n_train_ = train_edges.size(1);
+  std::vector<int64_t> order((size_t)n_train_);
+  for (int64_t i = 0; i < n_train_; ++i) order[(size_t)i] = i;
+  if (cfg.shuffle) {  // shuffle_vec's generator, as the GCN driver shuffles its seeds
+    std::mt19937 gen(2000);
+    std::shuffle(order.begin(), order.end(), gen);
+  }
+  std::tie(train_src_, train_dst_) =
+      edges_to_device(train_edges, (int64_t)graph->global_vertices, graph->device, &order);
+  sampler = make_sampler();
+  batch.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device);
+  // size the scratch arena once so the training loop never allocates
+  const uint64_t pairs_cap = (uint64_t)cfg.batch_size * (1 + (uint64_t)cfg.neg_per_pos);
+  uint64_t items = std::max<uint64_t>(graph->global_vertices, 8 * pairs_cap);
+  for (auto* s : sampler->ssg->sampled_sgs) items = std::max<uint64_t>({items, s->e_cap, s->v_cap});
+  hip_check(nts_hip_ctx_reserve(cs->ctx(), graph->global_vertices, items), "nts_hip_ctx_reserve");
+  for (size_t i = 0; i + 1 < cfg.layer_size.size(); ++i) {
+    P.push_back(new Parameter((size_t)cfg.layer_size[i], (size_t)cfg.layer_size[i + 1],
+                                    cfg.learn_rate, cfg.beta1, cfg.beta2, cfg.epsilon,
+                                    cfg.weight_decay, graph->device, cfg.seed + (int64_t)i));
+    if (cfg.hip_gemm) P.back()->cs = cs.get();
+  }
+  cs->synchronize();
+}
+
+LinkPredictor::~LinkPredictor() {
+  for (auto* p : P) delete p;
+}
+
+// one slot whose layer-0 capacity is the most endpoints a batch can have;
+// CSR transposes where a graph-op backward runs (every hop but the outermost)
+std::unique_ptr<FastSampler> LinkPredictor::make_sampler() const {
+  const int L = (int)cfg.fanout.size();
+  const int64_t P = (int64_t)cfg.batch_size * (1 + (int64_t)cfg.neg_per_pos);
+  std::vector<bool> csr(L, true);
+  csr[L - 1] = false;
+  auto s = std::make_unique<FastSampler>(graph, std::vector<VertexId>(), L, (int)(2 * P), cfg.fanout,
+                                         1, csr,
+                                         cfg.weight_type != WeightType::None || cfg.edge_weighted);
+  s->rng_mode = cfg.rng_mode;
+  s->weighted = cfg.weighted_sampling;
+  s->coef = cfg.edge_weighted;
+  s->up_degree = cfg.up_degree;
+  return s;
+}
+
+SampledSubgraph* LinkPredictor::build(LpBatch& b, FastSampler& s, const NtsVar& src,
+                                      const NtsVar& dst, int64_t off, int64_t B, uint64_t seq) {
+  b.B = (uint32_t)B;
+  b.batch_seq = seq;
+  b.pos_src.narrow(0, 0, B).copy_(src.narrow(0, off, B));
+  b.pos_dst.narrow(0, 0, B).copy_(dst.narrow(0, off, B));
+  hip_check(nts_hip_lp_batch(cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B,
+                             b.K, graph->global_vertices, seq, (uint32_t)b.destination.numel(),
+                             dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size),
+                             dptr<uint32_t>(b.pair_u), dptr<uint32_t>(b.pair_v),
+                             dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot)),
+            "nts_hip_lp_batch");
+  b.pairs = {dptr<uint32_t>(b.pair_u),   dptr<uint32_t>(b.pair_v), dptr<uint32_t>(b.inc_offset),
+             dptr<uint32_t>(b.inc_slot), dptr<uint32_t>(b.v_size), b.B,
+             b.K};
+  const uint64_t P = (uint64_t)b.B * (1 + (uint64_t)b.K);
+  s.batch_seq = seq;
+  s.issue_gpu_sample_dev(b.destination, b.v_size, (VertexId)(2 * P), 0, *cs, cfg.weight_type);
+  return s.finish_gpu_sample(0);
+}
+
+NtsVar LinkPredictor::forward(SampledSubgraph* sg, LpBatch& b, float* mrr) {
+  const int L = (int)P.size();
+  const double p = ctx.is_train() ? (double)cfg.drop_rate : 0.0;
+  NtsVar X, out;
+  for (int l = 0; l < L; ++l) {
+    const int hop = L - 1 - l;
+    const bool bottom = l == 0;  // gathers its rows from the feature table
+    NtsVar Y = ctx.runGraphOp<op::SingleGPUAllSampleGraphOp>(bottom ? F : X, sg, graph.get(), hop,
+                                                             cs.get(), bottom, nullptr, AggKind{},
+                                                             false);
+    if (l < L - 1) {
+      const uint64_t off = ctx.is_train() ? dropout_calls_++ : 0;
+      X = ctx.runVertexForward(
+          [&](NtsVar& a) {
+            if (cfg.hip_gemm && cfg.fuse_activation)
+              return hip_linear_act(a, P[l]->W, p, dropout_key(), off, cs.get(), false);
+            return hip_relu_dropout(P[l]->forward(a), p, dropout_key(), off, cs.get());
+          },
+          Y);
+    } else {  // the embedding and the pairs' loss, one autograd segment
+      out = ctx.runVertexForward(
+          [&](NtsVar& a) { return hip_lp_bce(P[l]->forward(a), b.pairs, b.score, cs.get(), mrr); }, Y);
+    }
+  }
+  return out;
+}
+
+float LinkPredictor::train_batch() {
+  auto guard = cs->guard();
+  TORCH_CHECK(has_batch(), "train_batch: the pass is over (restart())");
+  const int64_t B = std::min<int64_t>(cfg.batch_size, n_train_ - offset_);
+  SampledSubgraph* sg = build(batch, *sampler, train_src_, train_dst_, offset_, B, train_seq);
+  offset_ += B;
+  ++train_seq;
+  last_sg = sg;
+  ctx.train();
+  loss = forward(sg, batch, nullptr);
+  ctx.self_backward(false);
+  for (auto* p : P) {
+    if (cfg.bias_correction) p->learnC2C_with_decay_Adam(*cs);
+    else p->learn_local_with_decay_Adam(*cs);
+    p->next();
+  }
+  for (auto* p : P) p->zero_grad();
+  TORCH_CHECK(hipEventRecord(sg->consumed, (hipStream_t)cs->stream()) == hipSuccess,
+              "hipEventRecord");
+  ++batches;
+  return loss.item<float>();
+}
+
+float LinkPredictor::run_epoch() {
+  double sum = 0;
+  int64_t n = 0;
+  while (has_batch()) {
+    sum += train_batch();
+    ++n;
+  }
+  return n ? (float)(sum / (double)n) : 0.f;
+}
+
+std::vector<NtsVar> LinkPredictor::weights() {
+  auto guard = cs->guard();
+  std::vector<NtsVar> out;
+  for (auto* p : P) out.push_back(p->W.detach().clone());
+  cs->synchronize();
+  return out;
+}
+
+void LinkPredictor::set_weights(const std::vector<NtsVar>& ws) {
+  auto guard = cs->guard();
+  TORCH_CHECK(ws.size() == P.size(), "one tensor per layer");
+  torch::NoGradGuard ng;
+  for (size_t i = 0; i < P.size(); ++i) P[i]->W.copy_(ws[i].view_as(P[i]->W));
+  cs->synchronize();
+}
+
+double LinkPredictor::evaluate(const NtsVar& edges) {
+  auto guard = cs->guard();
+  NtsVar src, dst;
+  std::tie(src, dst) = edges_to_device(edges, (int64_t)graph->global_vertices, graph->device, nullptr);
+  const int64_t m = src.size(0);
+  // a sampler and a batch of their own: the training slot, its batch_seq and
+  // last_batch() stay as the last training step left them
+  auto es = make_sampler();
+  LpBatch eb;
+  eb.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device);
+  NtsVar counter = torch::zeros({2}, f32_opts(graph->device));
+  const bool was_train = ctx.is_train();
+  ctx.eval();
+  double rr = 0, n = 0;
+  {
+    torch::NoGradGuard ng;
+    uint64_t seq = kEvalSeq;
+    for (int64_t off = 0; off < m; off += cfg.batch_size, ++seq) {
+      const int64_t B = std::min<int64_t>(cfg.batch_size, m - off);
+      SampledSubgraph* sg = build(eb, *es, src, dst, off, B, seq);
+      counter.zero_();
+      forward(sg, eb, counter.data_ptr<float>());
+      TORCH_CHECK(hipEventRecord(sg->consumed, (hipStream_t)cs->stream()) == hipSuccess,
+                  "hipEventRecord");
+      NtsVar h = counter.cpu();  // per batch: the fp32 sums stay short, the total is a double
+      rr += (double)h[0].item<float>();
+      n += (double)h[1].item<float>();
+    }
+  }
+  cs->synchronize();
+  if (was_train) ctx.train();
+  return n > 0 ? rr / n : 0.0;
+}
+
+}  // namespace nts

@@ -285,6 +285,16 @@ class FastSampler {
   // event (recorded by the trainer) — issue makes `cs` wait for it.
   void issue_gpu_sample(int batch_size, int ssg_id, NtsStream& cs, WeightType w);
   SampledSubgraph* finish_gpu_sample(int ssg_id);
+  // The issue path with the layer-0 destinations in the caller's device
+  // buffers (link prediction): `dest` int32 [>= hint] holds the
+  // ids, v_size_dev[0] their live count, both produced by work enqueued on
+  // `cs` before the call; v_cap_live_hint bounds that count (<= the sampler's
+  // batch capacity).  finish_gpu_sample publishes the live count as layer 0's
+  // v_size.  Philox and Philox-shared draws, weighted and coefficient draws as
+  // issue_gpu_sample; refuses the MT19937 modes and omit_map.  sample_nids and
+  // work_offset are neither read nor moved; batch_seq advances by one.
+  void issue_gpu_sample_dev(const torch::Tensor& dest, const torch::Tensor& v_size_dev,
+                            VertexId v_cap_live_hint, int ssg_id, NtsStream& cs, WeightType w);
   // MT19937 modes: a batch whose word stream fell short is sampled again
   // from its checkpoint with larger bounds (finish_gpu_sample does it; the
   // batches issued behind it are re-run too).  rerun_ok = false when work
@@ -320,6 +330,7 @@ class FastSampler {
     const uint32_t* omit_loc = nullptr;
     NtsStream* cs = nullptr;
     torch::Tensor mt_ckpt;  // device u32 [625]: the generator before the batch
+    torch::Tensor dev_dest, dev_vsz;  // issue_gpu_sample_dev: the caller's layer-0 ids and count
   };
   std::vector<IssueRec> recs_;
   std::deque<int> issued_;  // slots issued and not yet finished, in issue order
@@ -632,6 +643,19 @@ void set_bottom_gemm_hooks(std::function<void()> after_fwd_gemm,
 NtsVar hip_bottom_transform(const NtsVar& table, const NtsVar& W, sampCSC* sg, double p,
                             uint64_t seed, uint64_t offset, NtsStream* cs, KernelProfiler* prof,
                             float* h_out = nullptr, const PairTable* pairs = nullptr);
+
+// Link-prediction loss (nts_hip_lp_bce_fwd / _train): the mean
+// sigmoid BCE of the dot-product scores of h's rows over the pairs of a batch
+// built by nts_hip_lp_batch.  h [rows, D] holds one row per distinct endpoint
+// (rows == the batch's live v_size).  Under grad mode with h requiring grad the
+// training entry runs and autograd returns its gathered dH.  score [P] receives
+// the scores; mrr != NULL: the device counter pair of nts_hip_lp_bce_fwd.
+struct LpPairs {
+  const uint32_t *pair_u, *pair_v, *inc_offset, *inc_slot, *v_size;
+  uint32_t B, K;
+};
+NtsVar hip_lp_bce(const NtsVar& h, const LpPairs& pairs, NtsVar& score, NtsStream* cs,
+                  float* mrr = nullptr);
 
 struct Parameter {
   NtsVar W, M, V;

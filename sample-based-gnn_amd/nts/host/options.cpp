@@ -179,4 +179,40 @@ void check_driver_options(const GCNConfig& cfg, const DriverInputs& in) {
   }
 }
 
+void check_link_pred_options(const GCNConfig& cfg, const LinkPredInputs& in) {
+  refuse("", {{cfg.layer_size.size() < 2, "need at least one layer"},
+              {cfg.fanout.size() != cfg.layer_size.size() - 1, "fanout per layer"}});
+  refuse("link prediction ",
+         {{cfg.neg_per_pos < 1, c10::str("needs neg_per_pos >= 1, got ", cfg.neg_per_pos)},
+          {cfg.batch_size < 1, c10::str("needs batch_size >= 1, got ", cfg.batch_size)},
+          {cfg.gat, "is not supported with gat (GCN / GraphSAGE layers only)"},
+          {cfg.aggregator != 0, "is not supported with aggregator = max (the sum aggregator only)"},
+          {cfg.root_weight, "is not supported with root_weight"},
+          {cfg.pd_cache, "is not supported with pd_cache"},
+          {cfg.sample_gpu, "is not supported with sample_gpu (the reference's mt19937 stream)"},
+          {is_mt_mode(cfg.rng_mode),
+           "is not supported with an MT19937 rng_mode (the seeds are device-side: Philox and "
+           "Philox-shared only)"},
+          {!(cfg.cache_rate < 0.0), "is not supported with cache_rate >= 0"},
+          {cfg.multi_label, "is not supported with multi_label (it has no label tensor)"},
+          {cfg.layer_norm, "is not supported with layer_norm"},
+          {cfg.batch_norm, "is not supported with batch_norm"},
+          {cfg.feature_f16, "is not supported with feature_f16"},
+          {cfg.transform_first == 1,
+           "is not supported with transform_first = 1 (aggregate-first only)"},
+          {cfg.pair_table > 0, "is not supported with pair_table > 0"},
+          {cfg.layer_size.back() > 1024,
+           c10::str("takes an embedding width of at most 1024, got ", cfg.layer_size.back())},
+          {(cfg.weighted_sampling || cfg.edge_weighted) && !in.has_edge_prob,
+           "with weighted_sampling / edge_weighted needs a graph with edge_prob"}});
+  refuse("", {{!(in.feature_on_gpu && in.feature_dtype == torch::kFloat32 &&
+                 in.feature_cols == cfg.layer_size[0]),
+               "feature table must be fp32 [V, layer_size[0]] on the GPU"},
+              {!(in.edges_on_host && in.edge_shape.size() == 2 && in.edge_shape[0] == 2 &&
+                 in.edge_shape[1] >= 1),
+               "train_edges must be int64 [2, n] on the host, n >= 1"},
+              {(int64_t)cfg.batch_size * (1 + (int64_t)std::max(cfg.neg_per_pos, 1)) > (1ll << 28),
+               "link prediction: batch_size x (1 + neg_per_pos) above 2^28 pairs"}});
+}
+
 }  // namespace nts

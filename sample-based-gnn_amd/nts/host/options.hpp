@@ -22,6 +22,22 @@ struct DriverInputs {
 // at the end of the pass: the report order is the source order.
 void check_driver_options(const GCNConfig& cfg, const DriverInputs& in);
 
+// Link prediction (LinkPredictor): what its rules read of the
+// constructor's inputs, and every refusal of a (cfg, inputs) pair before
+// anything is built.  This first version takes GCN / GraphSAGE layers with the
+// sum aggregator on an fp32 table; each option it does not take has a text of
+// its own.  check_driver_options is not involved.
+struct LinkPredInputs {
+  torch::ScalarType feature_dtype = torch::kFloat32;
+  bool feature_on_gpu = true;
+  int64_t feature_cols = 0;         // -1: the table is not 2-D
+  std::vector<int64_t> edge_shape;  // train_edges' sizes: [2, n]
+  bool edges_on_host = true;
+  int64_t n_vertices = 0;
+  bool has_edge_prob = false;
+};
+void check_link_pred_options(const GCNConfig& cfg, const LinkPredInputs& in);
+
 // the rules nts.host.gcn_config also applies, each at its place in the pass
 void check_gat_heads(const std::vector<int>& layer_size, bool gat, const std::vector<int>& heads);
 void check_gat_v2(bool gat_v2, bool gat);

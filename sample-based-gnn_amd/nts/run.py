@@ -67,6 +67,16 @@ statistics of the batch's rows while training and the running statistics
 (momentum 0.1) in the evaluation passes and under FULL_INFERENCE; a gamma and a
 beta per hidden layer are trained without weight decay.
 
+ALGORITHM:LINKPREDSAMPLE (no reference counterpart): link
+prediction with L GCN layers (sum aggregator, Philox sampler; SAMPLE_SHARED:1
+is taken).  LAYERS' last width is the embedding; a batch is BATCH_SIZE edges of
+EDGE_FILE plus NEG_PER_POS:k (default 1) uniform negatives per edge; the loss
+is the sigmoid BCE of the pairs' dot products.  VAL_EDGE_RATE:r (default 0.1) of
+the edge list, chosen by SEED, is held out of the training pairs and scored
+after every epoch (`Epoch e: Loss: .. Val MRR: ..`, each positive ranked
+against its own negatives).  The held-out edges are NOT removed from the
+message-passing graph.  LABEL_FILE and MASK_FILE are not used.
+
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
 """
@@ -97,6 +107,9 @@ ALGORITHMS = {
     "GSSAMPLEPDCACHE": ("gcn", "mean", "philox", False, "pd"),
     "GATSAMPLEALLGPU": ("gat", "none", "philox", False, None),
 }
+
+
+LINK_PRED = "LINKPREDSAMPLE"  # its own runner (run_link_pred); not a row of the table above
 
 
 def _path(base: pathlib.Path, p: str) -> pathlib.Path:
@@ -228,6 +241,76 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
+def refuse_link_pred_cfg(info: dataloader.InputInfo):
+    """what the cfg alone decides for ALGORITHM:LINKPREDSAMPLE, before anything is loaded"""
+    rows = (
+        (info.neg_per_pos < 1, f"NEG_PER_POS must be >= 1, got {info.neg_per_pos}"),
+        (not 0.0 <= info.val_edge_rate < 1.0,
+         f"VAL_EDGE_RATE must be in [0, 1), got {info.val_edge_rate}"),
+        (len(info.layers) < 2 or len(info.fanout) != len(info.layers) - 1,
+         "LAYERS needs at least one layer and FANOUT one entry per layer"),
+        (bool(info.multi_label or info.root_weight or info.layer_norm or info.batch_norm
+              or info.feature_f16 or info.gat_heads or info.gat_v2 or info.full_inference
+              or info.aggregator != "sum" or info.sample_weighted or info.edge_weight_agg),
+         "takes GCN layers with the sum aggregator only (of the model keys, SAMPLE_SHARED alone)"),
+        (int(os.environ.get("WORLD_SIZE", "1")) > 1, "is not data parallel (one process)"),
+    )
+    for hit, text in rows:
+        if hit:
+            raise SystemExit(f"ALGORITHM {info.algorithm}: {text}")
+
+
+def split_edges(n_edges: int, rate: float, seed: int):
+    """(train, validation) positions of the edge list: a permutation by `seed`,
+    its first floor(rate * n) positions held out"""
+    perm = np.random.default_rng(seed).permutation(n_edges)
+    n_val = int(rate * n_edges)
+    return np.sort(perm[n_val:]), np.sort(perm[:n_val])
+
+
+def run_link_pred(info: dataloader.InputInfo, base: pathlib.Path, epochs=None, device=0,
+                  out=print) -> dict:
+    from . import host
+    refuse_link_pred_cfg(info)  # before anything is loaded
+    epochs = info.epochs if epochs is None else epochs
+    torch.cuda.set_device(device)
+    dev = torch.device("cuda", device)
+    E = host.ext()
+    t0 = time.time()
+    src, dst, feats, _, _ = load_inputs(info, base, info.layers[-1], device=dev)
+    G = E.FullyRepGraph.from_edges(src, dst, info.vertices)  # every edge: held-out ones too
+    feat = torch.from_numpy(feats).to(dev)
+    edges = torch.stack([src.cpu().to(torch.int64), dst.cpu().to(torch.int64)])
+    tr, va = split_edges(edges.shape[1], info.val_edge_rate, info.seed)
+    train_edges, val_edges = edges[:, torch.from_numpy(tr)], edges[:, torch.from_numpy(va)]
+    cfg = host.gcn_config(info.layers, info.fanout, info.batch_size, learn_rate=info.learn_rate,
+                          weight_decay=info.weight_decay, drop_rate=info.drop_rate,
+                          shared_sampling=bool(info.sample_shared), pipeline=False, shuffle=True,
+                          seed=info.seed, neg_per_pos=info.neg_per_pos)
+    drv = host.link_predictor(G, feat, train_edges, cfg)
+    out(f"link prediction: {train_edges.shape[1]} training edges, {val_edges.shape[1]} held out "
+        f"(kept in the message-passing graph), {info.neg_per_pos} negative(s) per positive; "
+        f"loaded in {time.time() - t0:.2f}s")
+    res = {"algorithm": info.algorithm, "n_train_edges": int(train_edges.shape[1]),
+           "n_val_edges": int(val_edges.shape[1]), "epochs": []}
+    if val_edges.shape[1]:
+        res["val_mrr_init"] = drv.evaluate(val_edges)
+        out(f"Before training: Val MRR: {res['val_mrr_init']:.6f}")
+    for e in range(epochs):
+        drv.restart()
+        t1 = time.time()
+        loss = drv.run_epoch()
+        row = {"epoch": e, "loss": float(loss), "seconds": time.time() - t1}
+        line = f"Epoch {e}: Loss: {loss:.6f}"
+        if val_edges.shape[1]:
+            row["val_mrr"] = drv.evaluate(val_edges)
+            line += f" Val MRR: {row['val_mrr']:.6f}"
+        out(line)
+        res["epochs"].append(row)
+    res["driver"] = drv
+    return res
+
+
 def pd_presample_file(drv, info, base, out=print, rank=0, world=1):
     """PRE_SAMPLE_FILE (core/ntsBaseOp.hpp:427-497): read the hot vertices of
     every super-batch if the file exists, else keep the device preSample the
@@ -257,6 +340,8 @@ def run(cfg_path, epochs=None, device=0, out=print) -> dict:
     from . import dist as ndist
     cfg_path = pathlib.Path(cfg_path)
     info = dataloader.InputInfo.from_cfg(cfg_path)
+    if info.algorithm.upper() == LINK_PRED:  # its own task and report
+        return run_link_pred(info, cfg_path.parent, epochs, device, out)
     refuse_cfg(info)  # before anything is loaded
     base = cfg_path.parent
     n_classes = info.layers[-1]
