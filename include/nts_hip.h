@@ -1085,6 +1085,65 @@ int nts_hip_lp_bce_train(nts_hip_ctx *ctx, const float *H, uint64_t ldh, uint32_
                          const uint32_t *v_size, uint32_t v_cap, float *score, float *loss,
                          float *dH, uint64_t lddh, float *mrr);
 
+/* Target-edge exclusion and filtered negatives (DGL's
+ * as_edge_prediction_sampler(exclude = 'self' | 'reverse_id')).
+ *
+ * nts_hip_lp_exclude_keys: the batch's excluded edges as a sorted table.  A
+ * positive (pos_src[i], pos_dst[i]) is the graph edge src = pos_src[i] ->
+ * dst = pos_dst[i] of the CSC keyed by destination, its key
+ * (uint64(dst) << 32) | src; with reverse != 0 the key of the edge turned round
+ * (dst = pos_src[i], src = pos_dst[i]) is added.  keys_out[0 .. *n_keys_dev)
+ * receives the DISTINCT keys ascending (a repeated positive, a positive whose
+ * reverse is in the batch too and a self pair under reverse collapse);
+ * entries past the count are not written.  Ids must be < n_vertices <= 2^32:
+ * the two stable radix sorts (low word, then high word) run over
+ * ceil(log2 n_vertices) bits each.  Integer work only: two runs give the same
+ * bytes.  Scratch from the context arena, never more than nts_hip_lp_batch
+ * takes for the same B.
+ * NTS_ERR_INVALID, before any write: a NULL pointer, B == 0, B > 2^30,
+ * n_vertices outside 1..2^32, key_cap < (reverse ? 2 B : B). */
+int nts_hip_lp_exclude_keys(nts_hip_ctx *ctx, const uint32_t *pos_src, const uint32_t *pos_dst,
+                            uint32_t B, int reverse, uint64_t n_vertices, uint32_t key_cap,
+                            uint64_t *keys_out, uint32_t *n_keys_dev);
+/* Applies the table to one sampled block, after selection: the block's
+ * structure is not touched.  With e = min(sizes[1], e_cap) read on the device:
+ *   CSC edge k < e:  key (destination[edge_dst[k]], sample_ans[k]);
+ *   CSR slot s < e (row_offset != NULL; column_indices, source and
+ *                    edge_weight_backward are then needed):
+ *                    key (destination[column_indices[s]], source[row of s]);
+ * a key in the table sets the edge's coefficient (edge_weight_forward[k],
+ * edge_weight_backward[s]) to exactly 0.0f; any other edge keeps its value when
+ * had_weights != 0 and is set to 1.0f otherwise (the sampler writes no weights
+ * under NTS_WEIGHT_NONE without coefficients).  *excluded_count_dev += the
+ * number of CSC edges set to 0 (the caller zeroes it).  Edges and slots past
+ * the live sizes, and every array of a block whose overflow flag (sizes[3])
+ * is set, are neither read nor written.  keys / n_keys_dev as written by
+ * nts_hip_lp_exclude_keys (*n_keys_dev == 0: nothing is excluded).
+ * NTS_ERR_INVALID, before any write: a NULL pointer, a block without
+ * edge_weight_forward, row_offset without the three CSR arrays. */
+int nts_hip_lp_mask_block(nts_hip_ctx *ctx, const nts_sampcsc_dev *block, const uint64_t *keys,
+                          const uint32_t *n_keys_dev, int had_weights,
+                          uint32_t *excluded_count_dev);
+/* nts_hip_lp_batch with negatives filtered against the graph.  sorted_rows
+ * [E]: graph->row_indices sorted ascending within each destination's segment.
+ * Negative (i, k) of head u = pos_src[i] tries t = 0 .. 15: the candidate is
+ * nts_hip_lp_batch's tail with the counter word 0x20000000 | t (t = 0: the
+ * unfiltered draw), rejected when it equals u or the graph holds an edge
+ * between the two in either direction (a binary search of u in the
+ * candidate's segment and of the candidate in u's).  The first accepted
+ * candidate is taken; when all 16 are rejected the 16th is kept and
+ * *unresolved_dev += 1 (the caller zeroes it).  Everything else is
+ * nts_hip_lp_batch: a batch none of whose t = 0 candidates is rejected gives
+ * the same bytes.
+ * Also NTS_ERR_INVALID: graph, graph->column_offset, sorted_rows or
+ * unresolved_dev NULL, graph->n_vertices != n_vertices. */
+int nts_hip_lp_batch_filtered(nts_hip_ctx *ctx, const uint32_t *pos_src, const uint32_t *pos_dst,
+                              uint32_t B, uint32_t K, uint64_t n_vertices, uint64_t batch_seq,
+                              uint32_t v_cap, uint32_t *destination, uint32_t *v_size,
+                              uint32_t *pair_u, uint32_t *pair_v, uint32_t *inc_offset,
+                              uint32_t *inc_slot, const nts_graph_dev *graph,
+                              const uint32_t *sorted_rows, uint32_t *unresolved_dev);
+
 /* ---- GraphSAGE root weight (csrc/aggregate.hip; no counterpart in the reference) --
  * The graph op of X' = act([A X | X_dst] W), W = [W_n; W_s] stacked on K.
  *

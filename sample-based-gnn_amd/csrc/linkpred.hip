@@ -1,7 +1,9 @@
 // Link prediction: the batch builder (positive pairs, uniform
 // negatives, the distinct endpoints as the seed set, the incidence CSR of the
 // pairs over those seeds) and the fused dot-product scorer + sigmoid BCE loss
-// with its gathered, atomic-free backward.  No counterpart in the reference
+// with its gathered, atomic-free backward; §8u: the key table of a batch's
+// target edges, the mask that gives them the coefficient 0 in the sampled
+// blocks, and negatives filtered against the graph.  No counterpart in the reference
 // (its toolkits are node classifiers); the semantics follow DGL's
 // as_edge_prediction_sampler + negative_sampler.Uniform and PyG's
 // LinkNeighborLoader.
@@ -10,18 +12,40 @@
 namespace nts_hip {
 
 constexpr uint32_t kLpLayerTag = 0x20000000u;  // next to 0x80000000 (shared), 0x40000000 (weighted)
+constexpr uint32_t kLpTries = 16;  // draws per filtered negative (tags kLpLayerTag | 0..15)
 constexpr int kLpThreads = 256;
 constexpr int kLpPosPerBlock = 16;  // positives (with their negatives) per block of the loss kernels
 
 // ---------------------------------------------------------------------------
 // batch construction
 // ---------------------------------------------------------------------------
-// keys[2p] / keys[2p + 1] = the global ids of pair p's two ends
+// x in rows[beg, end), a segment sorted ascending
+__device__ __forceinline__ bool lp_row_has(const uint32_t* __restrict__ rows, uint64_t beg,
+                                           uint64_t end, uint32_t x) {
+  while (beg < end) {
+    const uint64_t mid = beg + ((end - beg) >> 1);
+    const uint32_t r = rows[mid];
+    if (r == x) return true;
+    if (r < x) beg = mid + 1;
+    else end = mid;
+  }
+  return false;
+}
+
+// keys[2p] / keys[2p + 1] = the global ids of pair p's two ends.  FILTER
+// (DESIGN §8u): up to kLpTries draws, try t under the tag kLpLayerTag | t (t = 0
+// is the unfiltered draw); a tail w is rejected when w == u or the graph holds
+// u -> w or w -> u (srows: row_indices sorted within each destination's
+// segment); the first accepted one is taken, else the last is kept and counted.
+template <bool FILTER>
 __global__ __launch_bounds__(kLpThreads) void k_lp_pairs(const uint32_t* __restrict__ pos_src,
                                                          const uint32_t* __restrict__ pos_dst,
                                                          uint32_t B, uint32_t K, uint64_t V,
                                                          uint64_t seed, uint64_t batch_seq,
-                                                         uint32_t* __restrict__ keys) {
+                                                         uint32_t* __restrict__ keys,
+                                                         const uint64_t* __restrict__ goff,
+                                                         const uint32_t* __restrict__ srows,
+                                                         uint32_t* __restrict__ unresolved) {
   const uint32_t P = B * (1u + K);
   const uint32_t p = blockIdx.x * kLpThreads + threadIdx.x;
   if (p >= P) return;
@@ -32,13 +56,22 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_pairs(const uint32_t* __restr
   } else {
     const uint32_t q = p - B, i = q / K, k = q - i * K;
     u = pos_src[i];
-    // the sampler's counter layout (philox_word, sampler.hip) under the tag
-    const uint4 c = make_uint4(k >> 2, i, kLpLayerTag, (uint32_t)batch_seq);
     const uint2 key = make_uint2((uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(batch_seq >> 32));
-    const uint4 r = philox4x32_10(c, key);
     const uint32_t j = k & 3u;
-    const uint32_t x = j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w));
-    v = (uint32_t)(((uint64_t)x * V) >> 32);
+    const uint32_t tries = FILTER ? kLpTries : 1u;
+    bool ok = false;
+    for (uint32_t t = 0; t < tries && !ok; ++t) {
+      // the sampler's counter layout (philox_word, sampler.hip) under the tag
+      const uint4 c = make_uint4(k >> 2, i, kLpLayerTag | t, (uint32_t)batch_seq);
+      const uint4 r = philox4x32_10(c, key);
+      const uint32_t x = j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w));
+      v = (uint32_t)(((uint64_t)x * V) >> 32);
+      if constexpr (FILTER)
+        ok = v != u && !lp_row_has(srows, goff[v], goff[(uint64_t)v + 1], u) &&
+             !lp_row_has(srows, goff[u], goff[(uint64_t)u + 1], v);
+    }
+    if constexpr (FILTER)
+      if (!ok) atomicAdd(unresolved, 1u);
   }
   keys[2 * (uint64_t)p] = u;
   keys[2 * (uint64_t)p + 1] = v;
@@ -74,6 +107,119 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_finish(
   }
   const uint32_t slot = inc_slot[i];
   ((slot & 1u) ? pair_v : pair_u)[slot >> 1] = local;
+}
+
+// ---------------------------------------------------------------------------
+// target-edge exclusion
+// ---------------------------------------------------------------------------
+// item i < B: the positive (src, dst) as (lo, hi) = (pos_src, pos_dst); item
+// B + i (reverse): the same edge turned round
+__global__ __launch_bounds__(kLpThreads) void k_lp_excl_ends(const uint32_t* __restrict__ pos_src,
+                                                             const uint32_t* __restrict__ pos_dst,
+                                                             uint32_t B, uint32_t n,
+                                                             uint32_t* __restrict__ lo,
+                                                             uint32_t* __restrict__ hi) {
+  const uint32_t i = blockIdx.x * kLpThreads + threadIdx.x;
+  if (i >= n) return;
+  const bool rev = i >= B;
+  const uint32_t j = rev ? i - B : i;
+  const uint32_t s = pos_src[j], d = pos_dst[j];
+  lo[i] = rev ? d : s;
+  hi[i] = rev ? s : d;
+}
+
+__global__ __launch_bounds__(kLpThreads) void k_lp_excl_gather(const uint32_t* __restrict__ in,
+                                                               const uint32_t* __restrict__ idx,
+                                                               uint32_t n, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * kLpThreads + threadIdx.x;
+  if (i < n) out[i] = in[idx[i]];
+}
+
+// flag[i] = 1 where sorted item i opens a new (hi, lo) key
+__global__ __launch_bounds__(kLpThreads) void k_lp_excl_heads(const uint32_t* __restrict__ hi,
+                                                              const uint32_t* __restrict__ lo,
+                                                              uint32_t n, uint32_t* __restrict__ flag) {
+  const uint32_t i = blockIdx.x * kLpThreads + threadIdx.x;
+  if (i < n) flag[i] = (i == 0 || hi[i] != hi[i - 1] || lo[i] != lo[i - 1]) ? 1u : 0u;
+}
+
+// the distinct keys in ascending order and their count (rank: the exclusive
+// scan of the flags); nothing past the count is written
+__global__ __launch_bounds__(kLpThreads) void k_lp_excl_finish(
+    const uint32_t* __restrict__ hi, const uint32_t* __restrict__ lo,
+    const uint32_t* __restrict__ rank, uint32_t n, uint64_t* __restrict__ keys_out,
+    uint32_t* __restrict__ n_keys) {
+  const uint32_t i = blockIdx.x * kLpThreads + threadIdx.x;
+  if (i == 0) *n_keys = rank[n];
+  if (i >= n) return;
+  if (i == 0 || hi[i] != hi[i - 1] || lo[i] != lo[i - 1])
+    keys_out[rank[i]] = ((uint64_t)hi[i] << 32) | (uint64_t)lo[i];
+}
+
+// key in keys[0, n), ascending and distinct
+__device__ __forceinline__ bool lp_key_hit(const uint64_t* __restrict__ keys, uint32_t n,
+                                           uint64_t key) {
+  uint32_t beg = 0, end = n;
+  while (beg < end) {
+    const uint32_t mid = beg + ((end - beg) >> 1);
+    const uint64_t k = keys[mid];
+    if (k == key) return true;
+    if (k < key) beg = mid + 1;
+    else end = mid;
+  }
+  return false;
+}
+
+// One thread per live CSC edge (blockIdx.y == 0) or CSR slot (blockIdx.y ==
+// 1): its (global dst, global src) looked up in the key table (at most 2 B
+// 8-byte keys, cache resident); a hit's coefficient becomes 0, a miss keeps
+// its value (had_weights) or becomes 1.  A CSR slot finds its row by a binary
+// search of row_offset over the live rows.  A block with its overflow flag
+// set, and everything past the live sizes, is neither read nor written.
+__global__ __launch_bounds__(kLpThreads) void k_lp_mask(
+    const uint32_t* __restrict__ sizes, uint32_t v_cap, uint32_t e_cap, uint32_t s_cap,
+    const uint32_t* __restrict__ destination, const uint32_t* __restrict__ edge_dst,
+    const uint32_t* __restrict__ sample_ans, const uint32_t* __restrict__ source,
+    const uint32_t* __restrict__ row_offset, const uint32_t* __restrict__ column_indices,
+    float* __restrict__ w_fwd, float* __restrict__ w_bwd, const uint64_t* __restrict__ keys,
+    const uint32_t* __restrict__ n_keys_dev, int had_weights, uint32_t* __restrict__ excluded) {
+  if (sizes[3] != 0) return;  // (uniform: every thread of the grid leaves)
+  const uint32_t e_live = min(sizes[1], e_cap), n_keys = *n_keys_dev;
+  const uint32_t i = blockIdx.x * kLpThreads + threadIdx.x;
+  const bool csr = blockIdx.y == 1;
+  bool live = i < e_live, hit = false;
+  uint32_t d = 0, s = 0;
+  if (live && !csr) {
+    const uint32_t dl = edge_dst[i];
+    live = dl < v_cap;
+    if (live) {
+      d = destination[dl];
+      s = sample_ans[i];
+    }
+  } else if (live) {
+    // the row r with row_offset[r] <= i < row_offset[r + 1], r < the live rows
+    const uint32_t rows = min(sizes[2], s_cap);
+    uint32_t beg = 0, end = rows;
+    while (beg < end) {
+      const uint32_t mid = beg + ((end - beg) >> 1);
+      if (row_offset[mid + 1] <= i) beg = mid + 1;
+      else end = mid;
+    }
+    const uint32_t dl = column_indices[i];
+    live = beg < rows && row_offset[beg] <= i && dl < v_cap;
+    if (live) {
+      d = destination[dl];
+      s = source[beg];
+    }
+  }
+  if (live) {
+    hit = lp_key_hit(keys, n_keys, ((uint64_t)d << 32) | (uint64_t)s);
+    float* w = csr ? w_bwd : w_fwd;
+    if (hit) w[i] = 0.0f;
+    else if (!had_weights) w[i] = 1.0f;
+  }
+  const int cnt = __syncthreads_count(hit && !csr);
+  if (threadIdx.x == 0 && cnt) atomicAdd(excluded, (uint32_t)cnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -292,10 +438,13 @@ using namespace nts_hip;
 
 extern "C" {
 
-int nts_hip_lp_batch(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* pos_dst, uint32_t B,
-                     uint32_t K, uint64_t n_vertices, uint64_t batch_seq, uint32_t v_cap,
-                     uint32_t* destination, uint32_t* v_size, uint32_t* pair_u, uint32_t* pair_v,
-                     uint32_t* inc_offset, uint32_t* inc_slot) {
+// the body of nts_hip_lp_batch and nts_hip_lp_batch_filtered (goff != NULL:
+// the redraw rule of k_lp_pairs<true>)
+static int lp_batch(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* pos_dst, uint32_t B,
+                    uint32_t K, uint64_t n_vertices, uint64_t batch_seq, uint32_t v_cap,
+                    uint32_t* destination, uint32_t* v_size, uint32_t* pair_u, uint32_t* pair_v,
+                    uint32_t* inc_offset, uint32_t* inc_slot, const uint64_t* goff,
+                    const uint32_t* srows, uint32_t* unresolved) {
   NTS_CHECK_ARG(ctx, "ctx is NULL");
   NTS_CHECK_ARG(pos_src && pos_dst && destination && v_size && pair_u && pair_v && inc_offset &&
                     inc_slot,
@@ -316,8 +465,14 @@ int nts_hip_lp_batch(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* 
   uint32_t* rank = flag + n_al;
   void* rtmp = rank + n_al;
   hipStream_t st = ctx->stream;
-  hipLaunchKernelGGL(k_lp_pairs, dim3(ceil_div(P64, kLpThreads)), dim3(kLpThreads), 0, st, pos_src,
-                     pos_dst, B, K, n_vertices, ctx->seed, batch_seq, keys);
+  if (goff)
+    hipLaunchKernelGGL(k_lp_pairs<true>, dim3(ceil_div(P64, kLpThreads)), dim3(kLpThreads), 0, st,
+                       pos_src, pos_dst, B, K, n_vertices, ctx->seed, batch_seq, keys, goff, srows,
+                       unresolved);
+  else
+    hipLaunchKernelGGL(k_lp_pairs<false>, dim3(ceil_div(P64, kLpThreads)), dim3(kLpThreads), 0, st,
+                       pos_src, pos_dst, B, K, n_vertices, ctx->seed, batch_seq, keys, nullptr,
+                       nullptr, nullptr);
   NTS_LAUNCH_CHECK();
   // stable: the slots of one endpoint stay in ascending order
   NTS_RET(radix_sort_pairs(keys, nullptr, skeys, inc_slot, nullptr, n, ceil_log2(n_vertices), rtmp,
@@ -330,6 +485,90 @@ int nts_hip_lp_batch(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* 
   hipLaunchKernelGGL(k_lp_finish, dim3(ceil_div(span, kLpThreads)), dim3(kLpThreads), 0, st,
                      (const uint32_t*)skeys, (const uint32_t*)rank, (const uint32_t*)inc_slot, n,
                      v_cap, destination, v_size, pair_u, pair_v, inc_offset);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
+int nts_hip_lp_batch(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* pos_dst, uint32_t B,
+                     uint32_t K, uint64_t n_vertices, uint64_t batch_seq, uint32_t v_cap,
+                     uint32_t* destination, uint32_t* v_size, uint32_t* pair_u, uint32_t* pair_v,
+                     uint32_t* inc_offset, uint32_t* inc_slot) {
+  return lp_batch(ctx, pos_src, pos_dst, B, K, n_vertices, batch_seq, v_cap, destination, v_size,
+                  pair_u, pair_v, inc_offset, inc_slot, nullptr, nullptr, nullptr);
+}
+
+int nts_hip_lp_batch_filtered(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* pos_dst,
+                              uint32_t B, uint32_t K, uint64_t n_vertices, uint64_t batch_seq,
+                              uint32_t v_cap, uint32_t* destination, uint32_t* v_size,
+                              uint32_t* pair_u, uint32_t* pair_v, uint32_t* inc_offset,
+                              uint32_t* inc_slot, const nts_graph_dev* graph,
+                              const uint32_t* sorted_rows, uint32_t* unresolved_dev) {
+  NTS_CHECK_ARG(graph && graph->column_offset && sorted_rows && unresolved_dev, "NULL pointer");
+  NTS_CHECK_ARG(graph->n_vertices == n_vertices, "graph->n_vertices != n_vertices");
+  return lp_batch(ctx, pos_src, pos_dst, B, K, n_vertices, batch_seq, v_cap, destination, v_size,
+                  pair_u, pair_v, inc_offset, inc_slot, graph->column_offset, sorted_rows,
+                  unresolved_dev);
+}
+
+int nts_hip_lp_exclude_keys(nts_hip_ctx* ctx, const uint32_t* pos_src, const uint32_t* pos_dst,
+                            uint32_t B, int reverse, uint64_t n_vertices, uint32_t key_cap,
+                            uint64_t* keys_out, uint32_t* n_keys_dev) {
+  NTS_CHECK_ARG(ctx, "ctx is NULL");
+  NTS_CHECK_ARG(pos_src && pos_dst && keys_out && n_keys_dev, "NULL pointer");
+  NTS_CHECK_ARG(B >= 1, "B == 0");
+  NTS_CHECK_ARG(B <= (1u << 30), "more than 2^30 positives");
+  NTS_CHECK_ARG(n_vertices >= 1 && n_vertices <= (1ull << 32), "n_vertices must be in 1..2^32");
+  const uint32_t n = reverse ? 2 * B : B;
+  NTS_CHECK_ARG(key_cap >= n, "key_cap < B (2 B with reverse)");
+  // scratch: four [n] arrays, each reused once its first content is dead | radix temporaries
+  const size_t n_al = ((size_t)n + 64) / 64 * 64;
+  NTS_RET(ensure_scratch(ctx, 4 * n_al * sizeof(uint32_t) + radix_tmp_bytes(n)));
+  uint32_t* a0 = (uint32_t*)ctx->scratch;  // lo, then hi in lo order, then the head flags
+  uint32_t* a1 = a0 + n_al;                // hi, then hi sorted
+  uint32_t* a2 = a1 + n_al;                // lo sorted, then rank[n + 1]
+  uint32_t* a3 = a2 + n_al;                // the first sort's order, then lo in (hi, lo) order
+  void* rtmp = a3 + n_al;
+  hipStream_t st = ctx->stream;
+  const dim3 grid(ceil_div(n, kLpThreads)), block(kLpThreads);
+  const uint32_t bits = ceil_log2(n_vertices);
+  hipLaunchKernelGGL(k_lp_excl_ends, grid, block, 0, st, pos_src, pos_dst, B, n, a0, a1);
+  NTS_LAUNCH_CHECK();
+  // two stable sorts, the low word first, give the 64-bit order
+  NTS_RET(radix_sort_pairs(a0, nullptr, a2, a3, nullptr, n, bits, rtmp, st, ctx));
+  hipLaunchKernelGGL(k_lp_excl_gather, grid, block, 0, st, (const uint32_t*)a1, (const uint32_t*)a3,
+                     n, a0);
+  NTS_LAUNCH_CHECK();
+  NTS_RET(radix_sort_pairs(a0, a2, a1, a3, nullptr, n, bits, rtmp, st, ctx));
+  hipLaunchKernelGGL(k_lp_excl_heads, grid, block, 0, st, (const uint32_t*)a1, (const uint32_t*)a3,
+                     n, a0);
+  NTS_LAUNCH_CHECK();
+  NTS_RET(scan1_exclusive(ctx, a0, a2, nullptr, n, st));
+  hipLaunchKernelGGL(k_lp_excl_finish, grid, block, 0, st, (const uint32_t*)a1, (const uint32_t*)a3,
+                     (const uint32_t*)a2, n, keys_out, n_keys_dev);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
+int nts_hip_lp_mask_block(nts_hip_ctx* ctx, const nts_sampcsc_dev* block, const uint64_t* keys,
+                          const uint32_t* n_keys_dev, int had_weights,
+                          uint32_t* excluded_count_dev) {
+  NTS_CHECK_ARG(ctx, "ctx is NULL");
+  NTS_CHECK_ARG(block && keys && n_keys_dev && excluded_count_dev, "NULL pointer");
+  NTS_CHECK_ARG(block->edge_weight_forward, "the block has no edge_weight_forward");
+  NTS_CHECK_ARG(block->destination && block->sizes && block->edge_dst && block->sample_ans,
+                "NULL pointer in the block");
+  const bool csr = block->row_offset != nullptr;
+  NTS_CHECK_ARG(!csr || (block->column_indices && block->source && block->edge_weight_backward),
+                "a block with row_offset needs column_indices, source and edge_weight_backward");
+  if (block->e_cap == 0) return NTS_OK;
+  hipLaunchKernelGGL(k_lp_mask, dim3(ceil_div(block->e_cap, kLpThreads), csr ? 2 : 1),
+                     dim3(kLpThreads), 0, ctx->stream, (const uint32_t*)block->sizes, block->v_cap,
+                     block->e_cap, block->s_cap, block->destination,
+                     (const uint32_t*)block->edge_dst, (const uint32_t*)block->sample_ans,
+                     (const uint32_t*)block->source, (const uint32_t*)block->row_offset,
+                     (const uint32_t*)block->column_indices, block->edge_weight_forward,
+                     block->edge_weight_backward, keys, n_keys_dev, had_weights,
+                     excluded_count_dev);
   NTS_LAUNCH_CHECK();
   return NTS_OK;
 }

@@ -71,6 +71,7 @@ EXPORTED = (
     "nts_hip_sample_layer_coef", "nts_hip_spmm_graph_fwd_coef", "nts_hip_spmm_graph_fwd_coef_h",
     "nts_hip_bn_act_fwd", "nts_hip_bn_act_eval", "nts_hip_bn_act_bwd",
     "nts_hip_lp_batch", "nts_hip_lp_bce_fwd", "nts_hip_lp_bce_train",
+    "nts_hip_lp_exclude_keys", "nts_hip_lp_mask_block", "nts_hip_lp_batch_filtered",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -237,6 +238,11 @@ def lib() -> C.CDLL:
         "nts_hip_lp_batch": ([P, P, P, U32, U32, U64, U64, U32, P, P, P, P, P, P], I),
         "nts_hip_lp_bce_fwd": ([P, P, U64, U32, P, P, U32, U32, P, P, P], I),
         "nts_hip_lp_bce_train": ([P, P, U64, U32, P, P, U32, U32, P, P, P, U32, P, P, P, U64, P], I),
+        # target-edge exclusion, filtered negatives
+        "nts_hip_lp_exclude_keys": ([P, P, P, U32, I, U64, U32, P, P], I),
+        "nts_hip_lp_mask_block": ([P, C.POINTER(SampCSCDev), P, P, I, P], I),
+        "nts_hip_lp_batch_filtered": ([P, P, P, U32, U32, U64, U64, U32, P, P, P, P, P, P,
+                                       C.POINTER(GraphDev), P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -422,6 +422,15 @@ class InputInfo:
     # validation MRR.  Held-out edges stay in the message-passing graph
     neg_per_pos: int = 1
     val_edge_rate: float = 0.1
+    # LP_EXCLUDE / LP_FILTER_NEG / LP_HOLDOUT_REMOVE (this build's keys,
+    # ALGORITHM:LINKPREDSAMPLE).  LP_EXCLUDE:none|self|reverse: a
+    # batch's positive edges (reverse: turned round as well) carry no message in
+    # its own sampled blocks.  LP_FILTER_NEG:1: a negative that is a self pair or
+    # a graph edge is drawn again.  LP_HOLDOUT_REMOVE:1: the held-out edges, and
+    # their reverses where the edge file has them, leave the message-passing graph
+    lp_exclude: str = "none"
+    lp_filter_neg: int = 0
+    lp_holdout_remove: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -464,6 +473,9 @@ class InputInfo:
             "SEED": ("seed", int),
             "NEG_PER_POS": ("neg_per_pos", int),
             "VAL_EDGE_RATE": ("val_edge_rate", float),
+            "LP_EXCLUDE": ("lp_exclude", lambda s: s.lower()),
+            "LP_FILTER_NEG": ("lp_filter_neg", int),
+            "LP_HOLDOUT_REMOVE": ("lp_holdout_remove", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -728,6 +728,35 @@ class HipContext:
                                         ptr(destination), ptr(v_size), ptr(pair_u), ptr(pair_v),
                                         ptr(inc_offset), ptr(inc_slot)))
 
+    def lp_batch_filtered(self, graph: "DeviceGraph", sorted_rows, pos_src, pos_dst, K, batch_seq,
+                          destination, v_size, pair_u, pair_v, inc_offset, inc_slot, unresolved):
+        """lp_batch with every negative that is a self pair or an edge of `graph`
+        in either direction drawn again, up to 16 times.
+        sorted_rows: graph.row_indices ascending within each destination;
+        unresolved (int32 [1]) += the negatives still rejected at the 16th draw."""
+        g = graph.as_struct()
+        check(self.lib.nts_hip_lp_batch_filtered(
+            self.h, ptr(pos_src), ptr(pos_dst), pos_src.numel(), K, graph.n_vertices, batch_seq,
+            destination.numel(), ptr(destination), ptr(v_size), ptr(pair_u), ptr(pair_v),
+            ptr(inc_offset), ptr(inc_slot), C.byref(g), ptr(sorted_rows), ptr(unresolved)))
+
+    def lp_exclude_keys(self, pos_src, pos_dst, reverse, n_vertices, keys_out, n_keys):
+        """The distinct keys (dst << 32 | src) of the batch's positive edges
+        (and, with `reverse`, of the edges turned round), ascending, into
+        keys_out (int64) and their count into n_keys (int32 [1])."""
+        check(self.lib.nts_hip_lp_exclude_keys(self.h, ptr(pos_src), ptr(pos_dst), pos_src.numel(),
+                                               int(bool(reverse)), n_vertices, keys_out.numel(),
+                                               ptr(keys_out), ptr(n_keys)))
+
+    def lp_mask_block(self, lay: "LayerBuffers", keys, n_keys, had_weights, excluded):
+        """Coefficient 0 for every live edge of the block (CSC and, where built,
+        CSR) whose (global dst, global src) is in the key table; other edges
+        keep their value (had_weights) or get 1; excluded (int32 [1]) += the
+        CSC edges hit."""
+        o = lay.as_struct()
+        check(self.lib.nts_hip_lp_mask_block(self.h, C.byref(o), ptr(keys), ptr(n_keys),
+                                             int(bool(had_weights)), ptr(excluded)))
+
     def lp_bce_fwd(self, H, D, pair_u, pair_v, B, K, score, loss, mrr=None):
         """score[p] = <H[pair_u[p], :D], H[pair_v[p], :D]>, the mean sigmoid BCE
         (targets 1 for p < B) and, with `mrr` (float32 [2]), += (sum 1/rank, B)."""

@@ -41,6 +41,9 @@ def _checked(rule, *args, **kwargs):
         raise ValueError(str(e).splitlines()[0]) from None
 
 
+LP_EXCLUDE = {"none": 0, "self": 1, "reverse": 2}  # GCNConfig.lp_exclude (cfg key LP_EXCLUDE)
+
+
 def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, drop_rate=0.5,
                rng_mode=_abi.NTS_RNG_PHILOX, weight="sum", fused_gather=True,
                bias_correction=False, deterministic_backward=True, shuffle=True, profile=False,
@@ -53,7 +56,8 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gat_heads=None, layer_norm=False, layer_norm_eps=1e-5, gat_attn_drop=0.0,
                gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False,
                weighted_sampling=False, edge_weighted=False, batch_norm=False,
-               batch_norm_eps=1e-5, batch_norm_momentum=0.1, neg_per_pos=1):
+               batch_norm_eps=1e-5, batch_norm_momentum=0.1, neg_per_pos=1, lp_exclude="none",
+               filter_negatives=False):
     if weighted_sampling:  # neighbours drawn in proportion to the graph's edge_prob
         if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
             raise ValueError("weighted_sampling is not supported with an MT19937 rng_mode (it "
@@ -134,6 +138,12 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
     c.profile = bool(profile)
     c.seed = int(seed)
     c.neg_per_pos = int(neg_per_pos)  # LinkPredictor only; no other driver reads it
+    if lp_exclude not in LP_EXCLUDE:
+        raise ValueError(f"lp_exclude must be 'none', 'self' or 'reverse', got {lp_exclude!r}")
+    if LP_EXCLUDE[lp_exclude]:  # target-edge exclusion; LinkPredictor only
+        c.lp_exclude = LP_EXCLUDE[lp_exclude]
+    if filter_negatives:  # (the defaults leave both fields as constructed)
+        c.lp_filter_neg = True
     return c
 
 

@@ -291,7 +291,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("shuffle", &GCNConfig::shuffle)
       .def_readwrite("profile", &GCNConfig::profile)
       .def_readwrite("seed", &GCNConfig::seed)
-      .def_readwrite("neg_per_pos", &GCNConfig::neg_per_pos);
+      .def_readwrite("neg_per_pos", &GCNConfig::neg_per_pos)
+      .def_readwrite("lp_exclude", &GCNConfig::lp_exclude)
+      .def_readwrite("lp_filter_neg", &GCNConfig::lp_filter_neg);
 
   // the constructor's option and shape rules on facts about its inputs: no
   // tensor, no device (RuntimeError with the rule's text as its first line)
@@ -339,6 +341,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("evaluate", &LinkPredictor::evaluate, py::arg("edges"),
            py::call_guard<py::gil_scoped_release>())
       .def("synchronize", &LinkPredictor::synchronize)
+      .def("excluded_edges", &LinkPredictor::excluded_edges)
+      .def("unresolved_negatives", &LinkPredictor::unresolved_negatives)
       .def_property_readonly("loss", [](LinkPredictor& d) { return d.loss; })
       .def_readonly("batches", &LinkPredictor::batches)
       .def_readonly("train_seq", &LinkPredictor::train_seq)

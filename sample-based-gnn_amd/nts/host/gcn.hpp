@@ -204,6 +204,15 @@ struct GCNConfig {
   // LinkPredictor only (nts/host/linkpred.hpp): uniform negatives
   // drawn per positive edge of a batch.  No node-classification driver reads it.
   int neg_per_pos = 1;
+  // LinkPredictor only.  lp_exclude: 0 = none, 1 = self: every
+  // sampled edge of a batch's blocks that is one of the batch's positive edges
+  // (src = head, dst = tail) aggregates with coefficient 0; 2 = reverse: the
+  // positives turned round as well.  After selection: a destination above its
+  // fanout may aggregate fewer than fanout neighbours.  lp_filter_neg: a
+  // negative that is a self pair or a graph edge in either direction is drawn
+  // again, up to 16 times.
+  int lp_exclude = 0;
+  bool lp_filter_neg = false;
 };
 
 // Sampler-only throughput of the GPU sampler (SURVEY §8d "sampler-only"

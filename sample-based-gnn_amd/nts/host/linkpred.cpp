@@ -25,7 +25,13 @@ std::pair<NtsVar, NtsVar> edges_to_device(const NtsVar& edges, int64_t n_vertice
 }
 }  // namespace
 
-void LpBatch::alloc(int64_t b_cap, int K_, int device) {
+void LpBatch::alloc(int64_t b_cap, int K_, int device, bool exclude) {
+  counters = torch::zeros({2}, u32_opts(device));
+  if (exclude) {
+    excl_keys = torch::empty({2 * b_cap}, torch::TensorOptions().dtype(torch::kInt64).device(
+                                               torch::kCUDA, device));
+    n_keys = torch::zeros({1}, u32_opts(device));
+  }
   const int64_t P = b_cap * (1 + (int64_t)K_);
   pos_src = torch::empty({b_cap}, u32_opts(device));
   pos_dst = torch::empty({b_cap}, u32_opts(device));
@@ -59,8 +65,22 @@ LinkPredictor::LinkPredictor(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
   }
   std::tie(train_src_, train_dst_) =
       edges_to_device(train_edges, (int64_t)graph->global_vertices, graph->device, &order);
+  if (cfg.lp_filter_neg) {
+    // row_indices ascending within each destination's segment: one sort of the
+    // (dst << 32 | src) keys (check_link_pred_options: V <= 2^31, so they are
+    // non-negative int64)
+    const auto dev = torch::Device(torch::kCUDA, graph->device);
+    NtsVar deg = graph->column_offset.narrow(0, 1, (int64_t)graph->global_vertices) -
+                 graph->column_offset.narrow(0, 0, (int64_t)graph->global_vertices);
+    NtsVar dst = torch::repeat_interleave(
+        torch::arange((int64_t)graph->global_vertices, torch::TensorOptions().dtype(torch::kInt64).device(dev)),
+        deg, 0, (int64_t)graph->global_edges);
+    NtsVar src = graph->row_indices.to(torch::kInt64).bitwise_and(0xFFFFFFFFll);
+    NtsVar keys = std::get<0>(torch::sort(dst * (int64_t(1) << 32) + src));
+    sorted_rows_ = keys.bitwise_and(0xFFFFFFFFll).to(torch::kInt32).contiguous();
+  }
   sampler = make_sampler();
-  batch.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device);
+  batch.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device, cfg.lp_exclude != 0);
   // size the scratch arena once so the training loop never allocates
   const uint64_t pairs_cap = (uint64_t)cfg.batch_size * (1 + (uint64_t)cfg.neg_per_pos);
   uint64_t items = std::max<uint64_t>(graph->global_vertices, 8 * pairs_cap);
@@ -88,7 +108,8 @@ std::unique_ptr<FastSampler> LinkPredictor::make_sampler() const {
   csr[L - 1] = false;
   auto s = std::make_unique<FastSampler>(graph, std::vector<VertexId>(), L, (int)(2 * P), cfg.fanout,
                                          1, csr,
-                                         cfg.weight_type != WeightType::None || cfg.edge_weighted);
+                                         cfg.weight_type != WeightType::None || cfg.edge_weighted ||
+                                             cfg.lp_exclude != 0);
   s->rng_mode = cfg.rng_mode;
   s->weighted = cfg.weighted_sampling;
   s->coef = cfg.edge_weighted;
@@ -102,18 +123,68 @@ SampledSubgraph* LinkPredictor::build(LpBatch& b, FastSampler& s, const NtsVar& 
   b.batch_seq = seq;
   b.pos_src.narrow(0, 0, B).copy_(src.narrow(0, off, B));
   b.pos_dst.narrow(0, 0, B).copy_(dst.narrow(0, off, B));
-  hip_check(nts_hip_lp_batch(cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B,
-                             b.K, graph->global_vertices, seq, (uint32_t)b.destination.numel(),
-                             dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size),
-                             dptr<uint32_t>(b.pair_u), dptr<uint32_t>(b.pair_v),
-                             dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot)),
-            "nts_hip_lp_batch");
+  uint32_t* counters = dptr<uint32_t>(b.counters);
+  if (cfg.lp_filter_neg || cfg.lp_exclude)
+    TORCH_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), (hipStream_t)cs->stream()) ==
+                    hipSuccess,
+                "hipMemsetAsync");
+  if (cfg.lp_filter_neg) {
+    const nts_graph_dev g = graph->dev();
+    hip_check(nts_hip_lp_batch_filtered(
+                  cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B, b.K,
+                  graph->global_vertices, seq, (uint32_t)b.destination.numel(),
+                  dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size), dptr<uint32_t>(b.pair_u),
+                  dptr<uint32_t>(b.pair_v), dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot),
+                  &g, dptr<uint32_t>(sorted_rows_), counters + 1),
+              "nts_hip_lp_batch_filtered");
+  } else {
+    hip_check(nts_hip_lp_batch(cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B,
+                               b.K, graph->global_vertices, seq, (uint32_t)b.destination.numel(),
+                               dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size),
+                               dptr<uint32_t>(b.pair_u), dptr<uint32_t>(b.pair_v),
+                               dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot)),
+              "nts_hip_lp_batch");
+  }
+  if (cfg.lp_exclude)
+    hip_check(nts_hip_lp_exclude_keys(cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst),
+                                      b.B, cfg.lp_exclude == 2, graph->global_vertices,
+                                      (uint32_t)b.excl_keys.numel(),
+                                      reinterpret_cast<uint64_t*>(b.excl_keys.data_ptr<int64_t>()),
+                                      dptr<uint32_t>(b.n_keys)),
+              "nts_hip_lp_exclude_keys");
   b.pairs = {dptr<uint32_t>(b.pair_u),   dptr<uint32_t>(b.pair_v), dptr<uint32_t>(b.inc_offset),
              dptr<uint32_t>(b.inc_slot), dptr<uint32_t>(b.v_size), b.B,
              b.K};
   const uint64_t P = (uint64_t)b.B * (1 + (uint64_t)b.K);
   s.batch_seq = seq;
   s.issue_gpu_sample_dev(b.destination, b.v_size, (VertexId)(2 * P), 0, *cs, cfg.weight_type);
+  if (cfg.lp_exclude) {
+    // behind the layers on the same stream: the target edges' coefficients to
+    // 0 in every block; the blocks' structure stays the sampler's
+    const bool had = cfg.weight_type != WeightType::None || cfg.edge_weighted;
+    for (sampCSC* l : s.ssg->sampled_sgs) {
+      nts_sampcsc_dev o{};
+      o.v_cap = l->v_cap;
+      o.e_cap = l->e_cap;
+      o.s_cap = l->s_cap;
+      o.destination = dptr<uint32_t>(l->destination);
+      o.sample_ans = dptr<uint32_t>(l->sample_ans);
+      o.edge_dst = dptr<uint32_t>(l->edge_dst);
+      o.source = dptr<uint32_t>(l->source);
+      o.edge_weight_forward = dptr<float>(l->edge_weight_forward);
+      if (l->has_csr) {
+        o.row_offset = dptr<uint32_t>(l->row_offset);
+        o.column_indices = dptr<uint32_t>(l->column_indices);
+        o.edge_weight_backward = dptr<float>(l->edge_weight_backward);
+      }
+      o.sizes = dptr<uint32_t>(l->sizes);
+      hip_check(nts_hip_lp_mask_block(
+                    cs->ctx(), &o,
+                    reinterpret_cast<const uint64_t*>(b.excl_keys.data_ptr<int64_t>()),
+                    dptr<uint32_t>(b.n_keys), had, counters),
+                "nts_hip_lp_mask_block");
+    }
+  }
   return s.finish_gpu_sample(0);
 }
 
@@ -193,6 +264,18 @@ void LinkPredictor::set_weights(const std::vector<NtsVar>& ws) {
   cs->synchronize();
 }
 
+int64_t LinkPredictor::excluded_edges() {
+  auto guard = cs->guard();
+  cs->synchronize();
+  return (int64_t)(uint32_t)batch.counters.cpu()[0].item<int32_t>();
+}
+
+int64_t LinkPredictor::unresolved_negatives() {
+  auto guard = cs->guard();
+  cs->synchronize();
+  return (int64_t)(uint32_t)batch.counters.cpu()[1].item<int32_t>();
+}
+
 double LinkPredictor::evaluate(const NtsVar& edges) {
   auto guard = cs->guard();
   NtsVar src, dst;
@@ -202,7 +285,7 @@ double LinkPredictor::evaluate(const NtsVar& edges) {
   // last_batch() stay as the last training step left them
   auto es = make_sampler();
   LpBatch eb;
-  eb.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device);
+  eb.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device, cfg.lp_exclude != 0);
   NtsVar counter = torch::zeros({2}, f32_opts(graph->device));
   const bool was_train = ctx.is_train();
   ctx.eval();

@@ -24,7 +24,11 @@ struct LpBatch {
   uint32_t B = 0, K = 0;               // the live batch
   uint64_t batch_seq = 0;
   LpPairs pairs{};                     // the raw pointers the loss op takes
-  void alloc(int64_t b_cap, int K, int device);
+  // the excluded edges' sorted key table (int64 [2 b_cap], with
+  // lp_exclude), its live count, and the batch's counters {CSC edges excluded
+  // over all blocks, negatives still a true edge after 16 draws}
+  NtsVar excl_keys, n_keys, counters;
+  void alloc(int64_t b_cap, int K, int device, bool exclude = false);
 };
 
 class LinkPredictor {
@@ -49,6 +53,11 @@ class LinkPredictor {
   // training stream (batch_seq, position in the pass, dropout offsets) moves.
   double evaluate(const NtsVar& edges);
   void synchronize() { cs->synchronize(); }
+  // of the last training batch, read back on request only: the
+  // sampled edges, over all its blocks, that lp_exclude set to 0, and the
+  // negatives lp_filter_neg could not resolve in 16 draws
+  int64_t excluded_edges();
+  int64_t unresolved_negatives();
 
   std::shared_ptr<FullyRepGraph> graph;
   NtsVar F, loss;
@@ -72,6 +81,7 @@ class LinkPredictor {
   std::unique_ptr<FastSampler> make_sampler() const;
   uint64_t dropout_key() const { return (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1; }
   NtsVar train_src_, train_dst_;  // int32 [n] on the device, in training order
+  NtsVar sorted_rows_;            // lp_filter_neg: row_indices sorted within each destination
   int64_t n_train_ = 0, offset_ = 0;
   uint64_t dropout_calls_ = 0;
 };

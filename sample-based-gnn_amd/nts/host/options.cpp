@@ -205,6 +205,20 @@ void check_link_pred_options(const GCNConfig& cfg, const LinkPredInputs& in) {
            c10::str("takes an embedding width of at most 1024, got ", cfg.layer_size.back())},
           {(cfg.weighted_sampling || cfg.edge_weighted) && !in.has_edge_prob,
            "with weighted_sampling / edge_weighted needs a graph with edge_prob"}});
+  // target-edge exclusion
+  refuse("lp_exclude ",
+         {{cfg.lp_exclude < 0 || cfg.lp_exclude > 2,
+           c10::str("must be 0 (none), 1 (self) or 2 (reverse), got ", cfg.lp_exclude)},
+          {cfg.lp_exclude != 0 && cfg.weight_type == WeightType::MeanSampled,
+           "is not supported with the mean-sampled weights (their normaliser counts the sampled "
+           "edges, the excluded one among them)"},
+          {cfg.lp_exclude != 0 && cfg.up_degree,
+           "is not supported with up_degree (its degrees count the sampled edges, the excluded "
+           "one among them)"}});
+  refuse("lp_filter_neg ",
+         {{cfg.lp_filter_neg && in.n_vertices > (int64_t(1) << 31),
+           "takes a graph of at most 2^31 vertices (its sorted adjacency is built from signed "
+           "64-bit keys)"}});
   refuse("", {{!(in.feature_on_gpu && in.feature_dtype == torch::kFloat32 &&
                  in.feature_cols == cfg.layer_size[0]),
                "feature table must be fp32 [V, layer_size[0]] on the GPU"},

@@ -75,7 +75,13 @@ is the sigmoid BCE of the pairs' dot products.  VAL_EDGE_RATE:r (default 0.1) of
 the edge list, chosen by SEED, is held out of the training pairs and scored
 after every epoch (`Epoch e: Loss: .. Val MRR: ..`, each positive ranked
 against its own negatives).  The held-out edges are NOT removed from the
-message-passing graph.  LABEL_FILE and MASK_FILE are not used.
+message-passing graph unless LP_HOLDOUT_REMOVE:1: the graph is
+then built without them and without their reverses where EDGE_FILE has them.
+LP_EXCLUDE:self|reverse gives every sampled edge of a batch's blocks that is
+one of the batch's own positive edges (reverse: turned round as well) the
+coefficient 0, after selection, in training and in the validation passes;
+LP_FILTER_NEG:1 draws a negative that is a self pair or a graph edge again, up
+to 16 times.  LABEL_FILE and MASK_FILE are not used.
 
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
@@ -247,6 +253,8 @@ def refuse_link_pred_cfg(info: dataloader.InputInfo):
         (info.neg_per_pos < 1, f"NEG_PER_POS must be >= 1, got {info.neg_per_pos}"),
         (not 0.0 <= info.val_edge_rate < 1.0,
          f"VAL_EDGE_RATE must be in [0, 1), got {info.val_edge_rate}"),
+        (info.lp_exclude not in ("none", "self", "reverse"),
+         f"LP_EXCLUDE must be none, self or reverse, got {info.lp_exclude}"),
         (len(info.layers) < 2 or len(info.fanout) != len(info.layers) - 1,
          "LAYERS needs at least one layer and FANOUT one entry per layer"),
         (bool(info.multi_label or info.root_weight or info.layer_norm or info.batch_norm
@@ -268,6 +276,18 @@ def split_edges(n_edges: int, rate: float, seed: int):
     return np.sort(perm[n_val:]), np.sort(perm[:n_val])
 
 
+def message_passing_edges(src: np.ndarray, dst: np.ndarray, val_pos: np.ndarray) -> np.ndarray:
+    """LP_HOLDOUT_REMOVE: the positions of the edge list that stay in the
+    message-passing graph, ascending.  Position p leaves when (src[p], dst[p])
+    is a held-out edge (s, d) (`val_pos`, and every other copy of it in the
+    list) or the reverse (d, s) of one; every other edge stays, with its
+    multiplicity."""
+    s, d = np.asarray(src).astype(np.uint64), np.asarray(dst).astype(np.uint64)
+    key = (s << np.uint64(32)) | d
+    gone = np.concatenate([key[val_pos], (d[val_pos] << np.uint64(32)) | s[val_pos]])
+    return np.flatnonzero(~np.isin(key, gone))
+
+
 def run_link_pred(info: dataloader.InputInfo, base: pathlib.Path, epochs=None, device=0,
                   out=print) -> dict:
     from . import host
@@ -278,19 +298,31 @@ def run_link_pred(info: dataloader.InputInfo, base: pathlib.Path, epochs=None, d
     E = host.ext()
     t0 = time.time()
     src, dst, feats, _, _ = load_inputs(info, base, info.layers[-1], device=dev)
-    G = E.FullyRepGraph.from_edges(src, dst, info.vertices)  # every edge: held-out ones too
     feat = torch.from_numpy(feats).to(dev)
     edges = torch.stack([src.cpu().to(torch.int64), dst.cpu().to(torch.int64)])
     tr, va = split_edges(edges.shape[1], info.val_edge_rate, info.seed)
     train_edges, val_edges = edges[:, torch.from_numpy(tr)], edges[:, torch.from_numpy(va)]
+    if info.lp_holdout_remove:
+        keep = torch.from_numpy(message_passing_edges(edges[0].numpy(), edges[1].numpy(), va)).to(dev)
+        G = E.FullyRepGraph.from_edges(src[keep].contiguous(), dst[keep].contiguous(), info.vertices)
+    else:
+        G = E.FullyRepGraph.from_edges(src, dst, info.vertices)  # every edge: held-out ones too
     cfg = host.gcn_config(info.layers, info.fanout, info.batch_size, learn_rate=info.learn_rate,
                           weight_decay=info.weight_decay, drop_rate=info.drop_rate,
                           shared_sampling=bool(info.sample_shared), pipeline=False, shuffle=True,
-                          seed=info.seed, neg_per_pos=info.neg_per_pos)
+                          seed=info.seed, neg_per_pos=info.neg_per_pos,
+                          lp_exclude=info.lp_exclude, filter_negatives=bool(info.lp_filter_neg))
     drv = host.link_predictor(G, feat, train_edges, cfg)
+    kept = "kept in the message-passing graph"
+    if info.lp_holdout_remove:
+        kept = (f"removed from the message-passing graph with their reverses: "
+                f"{int(keep.numel())} of {edges.shape[1]} edges carry messages")
     out(f"link prediction: {train_edges.shape[1]} training edges, {val_edges.shape[1]} held out "
-        f"(kept in the message-passing graph), {info.neg_per_pos} negative(s) per positive; "
+        f"({kept}), {info.neg_per_pos} negative(s) per positive; "
         f"loaded in {time.time() - t0:.2f}s")
+    if info.lp_exclude != "none" or info.lp_filter_neg:
+        out(f"link prediction: target-edge exclusion {info.lp_exclude}, filtered negatives "
+            f"{'on' if info.lp_filter_neg else 'off'}")
     res = {"algorithm": info.algorithm, "n_train_edges": int(train_edges.shape[1]),
            "n_val_edges": int(val_edges.shape[1]), "epochs": []}
     if val_edges.shape[1]:
