@@ -1143,6 +1143,38 @@ int nts_hip_lp_batch_filtered(nts_hip_ctx *ctx, const uint32_t *pos_src, const u
                               uint32_t *pair_u, uint32_t *pair_v, uint32_t *inc_offset,
                               uint32_t *inc_slot, const nts_graph_dev *graph,
                               const uint32_t *sorted_rows, uint32_t *unresolved_dev);
+/* All-candidate ranking (csrc/lprank.hip).  Query i < M has the
+ * head u = q_head[i] and the true tail v = q_tail[i]; its candidates are the
+ * rows w = cand[j], j < n_cand, of H [n_rows, D] (pitch ldh), or every row
+ * 0 .. n_rows - 1 when cand is NULL (n_cand is then not read).  With
+ *   s(a, b) = the fp32 fmaf chain over k = 0 .. D-1 ascending, from 0,
+ * which is what the f32 MFMA computes and what the positive's pre-pass
+ * computes, a score depends on the two rows only.  A candidate is VALID iff
+ * w != v and, with the filter (adj_offset [n_rows + 1] = the graph's
+ * column_offset, adj_sorted = its row_indices ascending within each
+ * destination's segment: nts_hip_lp_batch_filtered's arrays and test),
+ * w != u and the graph holds neither u -> w nor w -> u.  Then
+ *   n_valid[i] = the valid candidates,
+ *   greater[i] = the valid candidates with s(u, w) >  s(u, v),
+ *   equal[i]   = the valid candidates with s(u, w) == s(u, v),
+ * a candidate id repeated in cand counting once per occurrence and the true
+ * tail never, wherever it stands.  The three arrays ([M] each) are
+ * overwritten.  The [n_cand, M] scores are never written: an LDS-tiled
+ * product on v_mfma_f32_32x32x2_f32 (k past D zero-filled, the row pad never
+ * read) whose epilogue compares and counts; integer atomics only, so two
+ * calls give the same bytes.  The filter's binary searches run for a
+ * candidate with s >= s(u, v) only; the filtered n_valid is a pass of its
+ * own over every (query, candidate).  Ids are not validated on the device:
+ * q_head, q_tail and cand entries must be < n_rows.  M floats of the
+ * context's scratch.
+ * NTS_ERR_INVALID, nothing written: a NULL ctx, H, q_head, q_tail or output,
+ * D == 0, D > 1024, ldh < D, M == 0, n_rows == 0, exactly one of adj_offset /
+ * adj_sorted, cand with n_cand == 0, more than 2^32 - 1 candidates. */
+int nts_hip_lp_rank(nts_hip_ctx *ctx, const float *H, uint64_t ldh, uint32_t D, uint32_t n_rows,
+                    const uint32_t *q_head, const uint32_t *q_tail, uint32_t M,
+                    const uint32_t *cand, uint64_t n_cand, const uint64_t *adj_offset,
+                    const uint32_t *adj_sorted, uint32_t *greater, uint32_t *equal,
+                    uint32_t *n_valid);
 
 /* ---- GraphSAGE root weight (csrc/aggregate.hip; no counterpart in the reference) --
  * The graph op of X' = act([A X | X_dst] W), W = [W_n; W_s] stacked on K.

@@ -8,6 +8,7 @@
 // as_edge_prediction_sampler + negative_sampler.Uniform and PyG's
 // LinkNeighborLoader.
 #include "common.hpp"
+#include "lp_filter.hpp"
 
 namespace nts_hip {
 
@@ -19,19 +20,6 @@ constexpr int kLpPosPerBlock = 16;  // positives (with their negatives) per bloc
 // ---------------------------------------------------------------------------
 // batch construction
 // ---------------------------------------------------------------------------
-// x in rows[beg, end), a segment sorted ascending
-__device__ __forceinline__ bool lp_row_has(const uint32_t* __restrict__ rows, uint64_t beg,
-                                           uint64_t end, uint32_t x) {
-  while (beg < end) {
-    const uint64_t mid = beg + ((end - beg) >> 1);
-    const uint32_t r = rows[mid];
-    if (r == x) return true;
-    if (r < x) beg = mid + 1;
-    else end = mid;
-  }
-  return false;
-}
-
 // keys[2p] / keys[2p + 1] = the global ids of pair p's two ends.  FILTER
 // (DESIGN §8u): up to kLpTries draws, try t under the tag kLpLayerTag | t (t = 0
 // is the unfiltered draw); a tail w is rejected when w == u or the graph holds
@@ -66,9 +54,7 @@ __global__ __launch_bounds__(kLpThreads) void k_lp_pairs(const uint32_t* __restr
       const uint4 r = philox4x32_10(c, key);
       const uint32_t x = j == 0 ? r.x : (j == 1 ? r.y : (j == 2 ? r.z : r.w));
       v = (uint32_t)(((uint64_t)x * V) >> 32);
-      if constexpr (FILTER)
-        ok = v != u && !lp_row_has(srows, goff[v], goff[(uint64_t)v + 1], u) &&
-             !lp_row_has(srows, goff[u], goff[(uint64_t)u + 1], v);
+      if constexpr (FILTER) ok = lp_pair_free(goff, srows, u, v);
     }
     if constexpr (FILTER)
       if (!ok) atomicAdd(unresolved, 1u);

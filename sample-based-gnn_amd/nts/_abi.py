@@ -72,6 +72,7 @@ EXPORTED = (
     "nts_hip_bn_act_fwd", "nts_hip_bn_act_eval", "nts_hip_bn_act_bwd",
     "nts_hip_lp_batch", "nts_hip_lp_bce_fwd", "nts_hip_lp_bce_train",
     "nts_hip_lp_exclude_keys", "nts_hip_lp_mask_block", "nts_hip_lp_batch_filtered",
+    "nts_hip_lp_rank",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -243,6 +244,8 @@ def lib() -> C.CDLL:
         "nts_hip_lp_mask_block": ([P, C.POINTER(SampCSCDev), P, P, I, P], I),
         "nts_hip_lp_batch_filtered": ([P, P, P, U32, U32, U64, U64, U32, P, P, P, P, P, P,
                                        C.POINTER(GraphDev), P, P], I),
+        # all-candidate ranking
+        "nts_hip_lp_rank": ([P, P, U64, U32, U32, P, P, U32, P, U64, P, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

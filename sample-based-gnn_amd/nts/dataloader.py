@@ -431,6 +431,11 @@ class InputInfo:
     lp_exclude: str = "none"
     lp_filter_neg: int = 0
     lp_holdout_remove: int = 0
+    # LP_FULL_EVAL / LP_FULL_FILTER (ALGORITHM:LINKPREDSAMPLE): after
+    # the last epoch the held-out edges ranked against every vertex on
+    # full-neighbour embeddings; LP_FULL_FILTER:1 drops a head's neighbours
+    lp_full_eval: int = 0
+    lp_full_filter: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -476,6 +481,8 @@ class InputInfo:
             "LP_EXCLUDE": ("lp_exclude", lambda s: s.lower()),
             "LP_FILTER_NEG": ("lp_filter_neg", int),
             "LP_HOLDOUT_REMOVE": ("lp_holdout_remove", int),
+            "LP_FULL_EVAL": ("lp_full_eval", int),
+            "LP_FULL_FILTER": ("lp_full_filter", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -771,6 +771,20 @@ class HipContext:
                                             ptr(v_size), inc_offset.numel() - 1, ptr(score),
                                             ptr(loss), ptr(dH), dH.stride(0), ptr(mrr)))
 
+    def lp_rank(self, H, D, n_rows, q_head, q_tail, greater, equal, n_valid, cand=None,
+                adj_offset=None, adj_sorted=None):
+        """All-candidate ranking: for query i (head q_head[i], true
+        tail q_tail[i]) the candidates (`cand`, int32, or every row < n_rows)
+        that are valid, and of those the ones scoring above / equal to the true
+        tail, into n_valid / greater / equal (int32 [M], overwritten).  With
+        adj_offset (int64 [n_rows + 1]) and adj_sorted (lp_batch_filtered's
+        sorted_rows) a candidate that is the head or its neighbour in either
+        direction is dropped.  The score matrix is never written."""
+        check(self.lib.nts_hip_lp_rank(self.h, ptr(H), H.stride(0), D, n_rows, ptr(q_head),
+                                       ptr(q_tail), q_head.numel(), ptr(cand),
+                                       0 if cand is None else cand.numel(), ptr(adj_offset),
+                                       ptr(adj_sorted), ptr(greater), ptr(equal), ptr(n_valid)))
+
     def adam(self, w, g, m, v, alpha, beta1, beta2, eps, wd, beta1_t, beta2_t, bias_correction):
         check(self.lib.nts_hip_adam(self.h, ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), alpha,
                                     beta1, beta2, eps, wd, beta1_t, beta2_t, int(bias_correction)))

@@ -325,6 +325,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("feature_cols"), py::arg("edge_shape"), py::arg("edges_on_host"),
       py::arg("n_vertices"), py::arg("has_edge_prob"));
 
+  m.def("check_link_pred_full", &check_link_pred_full, py::arg("cfg"), py::kw_only(),
+        py::arg("n_vertices"), py::arg("filtered"));
+
   // link prediction
   py::class_<LinkPredictor>(m, "LinkPredictor")
       .def(py::init([](std::shared_ptr<FullyRepGraph> g, torch::Tensor feature,
@@ -340,6 +343,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("set_weights", &LinkPredictor::set_weights)
       .def("evaluate", &LinkPredictor::evaluate, py::arg("edges"),
            py::call_guard<py::gil_scoped_release>())
+      // full-graph embeddings and all-candidate ranking
+      .def("embed_full", &LinkPredictor::embed_full, py::call_guard<py::gil_scoped_release>())
+      .def("evaluate_full",
+           [](LinkPredictor& d, const torch::Tensor& edges, std::vector<int64_t> ks, bool filtered,
+              bool both_sides, py::object candidates) {
+             torch::Tensor cand;
+             if (!candidates.is_none()) cand = candidates.cast<torch::Tensor>();
+             std::vector<std::pair<std::string, double>> r;
+             {
+               py::gil_scoped_release nogil;
+               r = d.evaluate_full(edges, ks, filtered, both_sides, cand);
+             }
+             py::dict o;
+             for (const auto& kv : r) {
+               if (kv.first == "n" || kv.first == "ties") o[py::str(kv.first)] = (int64_t)kv.second;
+               else o[py::str(kv.first)] = kv.second;
+             }
+             return o;
+           },
+           py::arg("edges"), py::arg("ks") = std::vector<int64_t>{1, 10, 50},
+           py::arg("filtered") = false, py::arg("both_sides") = false,
+           py::arg("candidates") = py::none())
+      .def("embed_sampled",
+           [](LinkPredictor& d, const torch::Tensor& edges) {
+             auto r = d.embed_sampled(edges);
+             return py::make_tuple(r.first, r.second);
+           },
+           py::arg("edges"))
       .def("synchronize", &LinkPredictor::synchronize)
       .def("excluded_edges", &LinkPredictor::excluded_edges)
       .def("unresolved_negatives", &LinkPredictor::unresolved_negatives)

@@ -65,20 +65,7 @@ LinkPredictor::LinkPredictor(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
   }
   std::tie(train_src_, train_dst_) =
       edges_to_device(train_edges, (int64_t)graph->global_vertices, graph->device, &order);
-  if (cfg.lp_filter_neg) {
-    // row_indices ascending within each destination's segment: one sort of the
-    // (dst << 32 | src) keys (check_link_pred_options: V <= 2^31, so they are
-    // non-negative int64)
-    const auto dev = torch::Device(torch::kCUDA, graph->device);
-    NtsVar deg = graph->column_offset.narrow(0, 1, (int64_t)graph->global_vertices) -
-                 graph->column_offset.narrow(0, 0, (int64_t)graph->global_vertices);
-    NtsVar dst = torch::repeat_interleave(
-        torch::arange((int64_t)graph->global_vertices, torch::TensorOptions().dtype(torch::kInt64).device(dev)),
-        deg, 0, (int64_t)graph->global_edges);
-    NtsVar src = graph->row_indices.to(torch::kInt64).bitwise_and(0xFFFFFFFFll);
-    NtsVar keys = std::get<0>(torch::sort(dst * (int64_t(1) << 32) + src));
-    sorted_rows_ = keys.bitwise_and(0xFFFFFFFFll).to(torch::kInt32).contiguous();
-  }
+  if (cfg.lp_filter_neg) ensure_sorted_rows();
   sampler = make_sampler();
   batch.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device, cfg.lp_exclude != 0);
   // size the scratch arena once so the training loop never allocates
@@ -97,6 +84,22 @@ LinkPredictor::LinkPredictor(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
 
 LinkPredictor::~LinkPredictor() {
   for (auto* p : P) delete p;
+}
+
+// row_indices ascending within each destination's segment: one sort of the
+// (dst << 32 | src) keys (the callers' option rules: V <= 2^31, so they are
+// non-negative int64)
+void LinkPredictor::ensure_sorted_rows() {
+  if (sorted_rows_.defined()) return;
+  const auto dev = torch::Device(torch::kCUDA, graph->device);
+  NtsVar deg = graph->column_offset.narrow(0, 1, (int64_t)graph->global_vertices) -
+               graph->column_offset.narrow(0, 0, (int64_t)graph->global_vertices);
+  NtsVar dst = torch::repeat_interleave(
+      torch::arange((int64_t)graph->global_vertices, torch::TensorOptions().dtype(torch::kInt64).device(dev)),
+      deg, 0, (int64_t)graph->global_edges);
+  NtsVar src = graph->row_indices.to(torch::kInt64).bitwise_and(0xFFFFFFFFll);
+  NtsVar keys = std::get<0>(torch::sort(dst * (int64_t(1) << 32) + src));
+  sorted_rows_ = keys.bitwise_and(0xFFFFFFFFll).to(torch::kInt32).contiguous();
 }
 
 // one slot whose layer-0 capacity is the most endpoints a batch can have;
@@ -188,7 +191,7 @@ SampledSubgraph* LinkPredictor::build(LpBatch& b, FastSampler& s, const NtsVar& 
   return s.finish_gpu_sample(0);
 }
 
-NtsVar LinkPredictor::forward(SampledSubgraph* sg, LpBatch& b, float* mrr) {
+NtsVar LinkPredictor::forward(SampledSubgraph* sg, LpBatch& b, float* mrr, NtsVar* emb) {
   const int L = (int)P.size();
   const double p = ctx.is_train() ? (double)cfg.drop_rate : 0.0;
   NtsVar X, out;
@@ -209,7 +212,12 @@ NtsVar LinkPredictor::forward(SampledSubgraph* sg, LpBatch& b, float* mrr) {
           Y);
     } else {  // the embedding and the pairs' loss, one autograd segment
       out = ctx.runVertexForward(
-          [&](NtsVar& a) { return hip_lp_bce(P[l]->forward(a), b.pairs, b.score, cs.get(), mrr); }, Y);
+          [&](NtsVar& a) {
+            NtsVar h = P[l]->forward(a);
+            if (emb) *emb = h;
+            return hip_lp_bce(h, b.pairs, b.score, cs.get(), mrr);
+          },
+          Y);
     }
   }
   return out;
@@ -308,6 +316,143 @@ double LinkPredictor::evaluate(const NtsVar& edges) {
   cs->synchronize();
   if (was_train) ctx.train();
   return n > 0 ? rr / n : 0.0;
+}
+
+std::pair<NtsVar, NtsVar> LinkPredictor::embed_sampled(const NtsVar& edges) {
+  auto guard = cs->guard();
+  NtsVar src, dst;
+  std::tie(src, dst) = edges_to_device(edges, (int64_t)graph->global_vertices, graph->device, nullptr);
+  auto es = make_sampler();
+  LpBatch eb;
+  eb.alloc(cfg.batch_size, cfg.neg_per_pos, graph->device, cfg.lp_exclude != 0);
+  const bool was_train = ctx.is_train();
+  ctx.eval();
+  NtsVar emb, ids;
+  {
+    torch::NoGradGuard ng;
+    const int64_t B = std::min<int64_t>(cfg.batch_size, src.size(0));
+    SampledSubgraph* sg = build(eb, *es, src, dst, 0, B, kEvalSeq);
+    forward(sg, eb, nullptr, &emb);
+    const int64_t v = sg->sampled_sgs[0]->v_size;
+    ids = eb.destination.narrow(0, 0, v).clone();
+    emb = emb.narrow(0, 0, v).clone();
+  }
+  cs->synchronize();
+  if (was_train) ctx.train();
+  return {ids, emb};
+}
+
+// Each layer is one O(E) aggregation over the global CSC plus one GEMM over
+// all V rows (DESIGN §8d's pass with the link predictor's layers).
+NtsVar LinkPredictor::embed_full() {
+  check_link_pred_full(cfg, (int64_t)graph->global_vertices, false);
+  auto guard = cs->guard();
+  const int L = (int)P.size();
+  const int64_t V = (int64_t)graph->global_vertices;
+  const int wt = cfg.weight_type == WeightType::Sum    ? NTS_WEIGHT_SUM
+                 : cfg.weight_type == WeightType::Mean ? NTS_WEIGHT_MEAN
+                                                       : NTS_WEIGHT_NONE;
+  const nts_graph_dev g = graph->dev();
+  auto aggregate = [&](const NtsVar& x, bool relu) {
+    NtsVar xr = row_major(x);
+    NtsVar y = row_padded_empty(V, xr.size(1), graph->device);
+    if (cfg.edge_weighted)
+      hip_check(nts_hip_spmm_graph_fwd_coef(cs->ctx(), &g, dptr<float>(graph->edge_prob), 0,
+                                            (uint64_t)V, wt, relu ? 1 : 0, xr.data_ptr<float>(),
+                                            (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+                                            y.data_ptr<float>(), (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd_coef");
+    else
+      hip_check(nts_hip_spmm_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+                                       xr.data_ptr<float>(), (uint64_t)xr.stride(0),
+                                       (uint32_t)xr.size(1), y.data_ptr<float>(),
+                                       (uint64_t)y.stride(0)),
+                "nts_hip_spmm_graph_fwd");
+    return y;
+  };
+  const bool was_train = ctx.is_train();
+  ctx.eval();
+  NtsVar X = F;
+  {
+    torch::NoGradGuard ng;
+    for (int l = 0; l < L; ++l) {
+      const NtsVar& W = P[l]->W;
+      if (l == L - 1) {  // the embedding: (A X) W, no activation
+        X = P[l]->forward(aggregate(X, false));
+      } else if (W.size(0) > W.size(1)) {  // relu(A (X W)), the relu in the kernel
+        X = aggregate(P[l]->forward(X), true);
+      } else {  // relu((A X) W)
+        NtsVar Y = aggregate(X, false);
+        if (cfg.hip_gemm && cfg.fuse_activation)  // p = 0: no mask, no offset drawn
+          X = hip_linear_act(Y, W, 0.0, 0, 0, cs.get(), false);
+        else
+          X = torch::relu(P[l]->forward(Y));
+      }
+    }
+  }
+  if (was_train) ctx.train();
+  cs->synchronize();
+  return X;
+}
+
+std::vector<std::pair<std::string, double>> LinkPredictor::evaluate_full(
+    const NtsVar& edges, const std::vector<int64_t>& ks, bool filtered, bool both_sides,
+    const NtsVar& candidates) {
+  const int64_t V = (int64_t)graph->global_vertices;
+  check_link_pred_full(cfg, V, filtered);
+  for (int64_t k : ks) TORCH_CHECK(k >= 1, "evaluate_full: hits@k needs k >= 1, got ", k);
+  NtsVar H = embed_full();
+  auto guard = cs->guard();
+  torch::NoGradGuard ng;
+  const auto dev = torch::Device(torch::kCUDA, graph->device);
+  NtsVar src, dst;
+  std::tie(src, dst) = edges_to_device(edges, V, graph->device, nullptr);
+  NtsVar cand;
+  if (candidates.defined()) {
+    TORCH_CHECK(!candidates.is_cuda() && candidates.dim() == 1 && candidates.size(0) >= 1 &&
+                    candidates.scalar_type() == torch::kInt64,
+                "evaluate_full: candidates must be int64 [n] on the host, n >= 1");
+    TORCH_CHECK(candidates.min().item<int64_t>() >= 0 && candidates.max().item<int64_t>() < V,
+                "evaluate_full: candidates must be vertex ids in [0, V)");
+    cand = candidates.to(torch::kInt32).to(dev).contiguous();
+  }
+  if (filtered) ensure_sorted_rows();
+  const nts_graph_dev g = graph->dev();
+  const int64_t m = src.size(0), total = both_sides ? 2 * m : m;
+  NtsVar counts = torch::empty({3, total}, u32_opts(graph->device));  // greater | equal | n_valid
+  uint32_t* cg = dptr<uint32_t>(counts);
+  for (int side = 0; side < (both_sides ? 2 : 1); ++side) {
+    const NtsVar& heads = side ? dst : src;
+    const NtsVar& tails = side ? src : dst;
+    for (int64_t off = 0; off < m; off += cfg.batch_size) {
+      const int64_t B = std::min<int64_t>(cfg.batch_size, m - off);
+      uint32_t* out = cg + side * m + off;
+      hip_check(nts_hip_lp_rank(cs->ctx(), H.data_ptr<float>(), (uint64_t)H.stride(0),
+                                (uint32_t)H.size(1), (uint32_t)V, dptr<uint32_t>(heads) + off,
+                                dptr<uint32_t>(tails) + off, (uint32_t)B,
+                                cand.defined() ? dptr<uint32_t>(cand) : nullptr,
+                                cand.defined() ? (uint64_t)cand.numel() : 0,
+                                filtered ? g.column_offset : nullptr,
+                                filtered ? dptr<uint32_t>(sorted_rows_) : nullptr, out, out + total,
+                                out + 2 * total),
+                "nts_hip_lp_rank");
+    }
+  }
+  // the metrics on the device, in double; one small tensor comes back
+  NtsVar c = counts.to(torch::kInt64).bitwise_and(0xFFFFFFFFll).to(torch::kFloat64);
+  NtsVar rank = c[0] + c[1] + 1.0, rank_opt = c[0] + 1.0;
+  std::vector<NtsVar> vals = {rank.reciprocal().mean(), rank_opt.reciprocal().mean(), rank.mean()};
+  for (int64_t k : ks) vals.push_back(rank.le((double)k).to(torch::kFloat64).mean());
+  vals.push_back(c[1].sum());
+  NtsVar h = torch::stack(vals).cpu();
+  cs->synchronize();
+  const double* p = h.data_ptr<double>();
+  std::vector<std::pair<std::string, double>> out = {
+      {"mrr", p[0]}, {"mrr_optimistic", p[1]}, {"mean_rank", p[2]}};
+  for (size_t i = 0; i < ks.size(); ++i) out.push_back({"hits@" + std::to_string(ks[i]), p[3 + i]});
+  out.push_back({"n", (double)total});
+  out.push_back({"ties", p[3 + ks.size()]});
+  return out;
 }
 
 }  // namespace nts

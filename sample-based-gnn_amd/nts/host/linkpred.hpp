@@ -52,6 +52,34 @@ class LinkPredictor {
   // positives (each ranked against its own K negatives).  Nothing of the
   // training stream (batch_seq, position in the pass, dropout offsets) moves.
   double evaluate(const NtsVar& edges);
+  // DESIGN §8v.  The model's own embedding of EVERY vertex, fp32 [V,
+  // layer_size.back()]: layer by layer over the whole graph with the
+  // whole-graph aggregation (nts_hip_spmm_graph_fwd, _coef with edge_weighted)
+  // and the driver's GEMMs; hidden layers relu on the narrower side of the
+  // layer, the last (A X) W without activation.  Eval mode, no
+  // grad, no random stream; nothing of the training state moves (train_seq,
+  // the position in the pass, the dropout offsets, the sampler slot, `batch`).
+  // Refuses mean-sampled weights and up_degree (check_link_pred_full).
+  NtsVar embed_full();
+  // One embed_full(), then every edge of `edges` (int64 [2, m], host) ranked
+  // against all V tails (or `candidates`, int64 ids on the host; undefined:
+  // all) by nts_hip_lp_rank in chunks of at most batch_size queries; with
+  // both_sides a second pass ranks the heads (heads and tails swapped).
+  // filtered: a candidate that is the head or its neighbour in either
+  // direction is dropped (sorted_rows_ is built on demand).  The metrics are
+  // formed on the device from the three count arrays, one small tensor comes
+  // back: {mrr, mrr_optimistic, mean_rank, hits@k for each k, n, ties}, rank =
+  // 1 + greater + equal (ties count against the positive), optimistic 1 +
+  // greater, ties = sum of equal.
+  std::vector<std::pair<std::string, double>> evaluate_full(const NtsVar& edges,
+                                                            const std::vector<int64_t>& ks,
+                                                            bool filtered, bool both_sides,
+                                                            const NtsVar& candidates);
+  // Eval mode, the first min(batch_size, m) edges of `edges` as one batch of
+  // the evaluation stream: {the batch's distinct endpoints (global ids), their
+  // embedding rows from the sampled blocks} (tests compare them with
+  // embed_full()).  Nothing of the training state moves.
+  std::pair<NtsVar, NtsVar> embed_sampled(const NtsVar& edges);
   void synchronize() { cs->synchronize(); }
   // of the last training batch, read back on request only: the
   // sampled edges, over all its blocks, that lp_exclude set to 0, and the
@@ -77,8 +105,10 @@ class LinkPredictor {
                          int64_t off, int64_t B, uint64_t seq);
   // the embedding of the batch's endpoints, then the loss (and, training, its
   // recorded backward); mrr: the device counter pair (evaluation)
-  NtsVar forward(SampledSubgraph* sg, LpBatch& b, float* mrr);
+  // emb (nullable): receives the embedding rows
+  NtsVar forward(SampledSubgraph* sg, LpBatch& b, float* mrr, NtsVar* emb = nullptr);
   std::unique_ptr<FastSampler> make_sampler() const;
+  void ensure_sorted_rows();  // sorted_rows_, once
   uint64_t dropout_key() const { return (uint64_t)cfg.seed * 0x9E3779B97F4A7C15ull + 1; }
   NtsVar train_src_, train_dst_;  // int32 [n] on the device, in training order
   NtsVar sorted_rows_;            // lp_filter_neg: row_indices sorted within each destination

@@ -229,4 +229,16 @@ void check_link_pred_options(const GCNConfig& cfg, const LinkPredInputs& in) {
                "link prediction: batch_size x (1 + neg_per_pos) above 2^28 pairs"}});
 }
 
+// (infer_full()'s wording for the two weight rules, lp_filter_neg's for the key width)
+void check_link_pred_full(const GCNConfig& cfg, int64_t n_vertices, bool filtered) {
+  refuse("embed_full: ",
+         {{cfg.up_degree, "UP_DEGREE weights are a property of a sample, not of the whole graph"},
+          {cfg.weight_type == WeightType::MeanSampled,
+           "MeanSampled weights are a property of a sample, not of the whole graph"}});
+  refuse("evaluate_full: filtered ",
+         {{filtered && n_vertices > (int64_t(1) << 31),
+           "takes a graph of at most 2^31 vertices (its sorted adjacency is built from signed "
+           "64-bit keys)"}});
+}
+
 }  // namespace nts

@@ -37,6 +37,9 @@ struct LinkPredInputs {
   bool has_edge_prob = false;
 };
 void check_link_pred_options(const GCNConfig& cfg, const LinkPredInputs& in);
+// what LinkPredictor::embed_full() / evaluate_full(filtered) refuse of a
+// predictor that was built
+void check_link_pred_full(const GCNConfig& cfg, int64_t n_vertices, bool filtered);
 
 // the rules nts.host.gcn_config also applies, each at its place in the pass
 void check_gat_heads(const std::vector<int>& layer_size, bool gat, const std::vector<int>& heads);

@@ -81,7 +81,11 @@ LP_EXCLUDE:self|reverse gives every sampled edge of a batch's blocks that is
 one of the batch's own positive edges (reverse: turned round as well) the
 coefficient 0, after selection, in training and in the validation passes;
 LP_FILTER_NEG:1 draws a negative that is a self pair or a graph edge again, up
-to 16 times.  LABEL_FILE and MASK_FILE are not used.
+to 16 times.  LP_FULL_EVAL:1 adds, after the last epoch, `Full Val
+MRR: .. Hits@10: ..`: every held-out edge ranked against all VERTICES tails on
+full-neighbour embeddings (no sampling, no negatives drawn); LP_FULL_FILTER:1
+drops a head's own neighbours from its candidates.  LABEL_FILE and MASK_FILE
+are not used.
 
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
@@ -212,6 +216,11 @@ def refuse_cfg(info: dataloader.InputInfo):
          "only)"),
         (info.batch_norm and info.layer_norm,
          "BATCH_NORM is not supported with LAYER_NORM:1 (one normalisation per hidden layer)"),
+        (bool(info.lp_full_eval),
+         f"LP_FULL_EVAL is not supported outside ALGORITHM:{LINK_PRED} (FULL_INFERENCE:1 is the "
+         "node classifiers' exact pass)"),
+        (bool(info.lp_full_filter),
+         f"LP_FULL_FILTER is not supported outside ALGORITHM:{LINK_PRED}"),
     )
     for hit, text in rows:
         if hit:
@@ -262,6 +271,8 @@ def refuse_link_pred_cfg(info: dataloader.InputInfo):
               or info.aggregator != "sum" or info.sample_weighted or info.edge_weight_agg),
          "takes GCN layers with the sum aggregator only (of the model keys, SAMPLE_SHARED alone)"),
         (int(os.environ.get("WORLD_SIZE", "1")) > 1, "is not data parallel (one process)"),
+        (bool(info.lp_full_filter) and not info.lp_full_eval,
+         "LP_FULL_FILTER needs LP_FULL_EVAL:1 (it filters the full evaluation's candidates)"),
     )
     for hit, text in rows:
         if hit:
@@ -339,6 +350,15 @@ def run_link_pred(info: dataloader.InputInfo, base: pathlib.Path, epochs=None, d
             line += f" Val MRR: {row['val_mrr']:.6f}"
         out(line)
         res["epochs"].append(row)
+    if info.lp_full_eval and val_edges.shape[1]:
+        # LP_FULL_EVAL:1 — the reportable score of the final weights: every
+        # held-out edge ranked against all V tails on full-neighbour embeddings
+        # (no sampling, no negatives drawn: the same numbers for every run)
+        full = drv.evaluate_full(val_edges, filtered=bool(info.lp_full_filter))
+        res["full_val"] = full
+        out(f"Full Val MRR: {full['mrr']:.6f} Hits@10: {full['hits@10']:.6f} "
+            f"({full['n']} edges against {info.vertices} candidates"
+            f"{', filtered' if info.lp_full_filter else ''})")
     res["driver"] = drv
     return res
 
