@@ -7,6 +7,7 @@
 // [fused feature gather +] graph op -> vertexForward ... -> Loss ->
 // self_backward -> Update (all-reduce + Adam) -> zero_grad.
 #include "gcn.hpp"
+#include "ops_util.hpp"
 #include "options.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -18,10 +19,6 @@
 #include <cstdlib>
 
 namespace nts {
-
-static double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 // cfg.feature_f16: the table as IEEE half with rows a lane can load 16 bytes
 // of.  The pitch is the row rounded up to 8 halves; rows of 256 bytes and more
@@ -77,7 +74,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   else
     cs = std::make_unique<NtsStream>(graph->device, nullptr, (uint64_t)cfg.seed,
                                      cfg.pipeline && cfg.sampler_priority < 0);
-  hip_check(nts_hip_ctx_set_gemm_mode(cs->ctx(), cfg.gemm_mode), "nts_hip_ctx_set_gemm_mode");
+  NTS_CALL(nts_hip_ctx_set_gemm_mode, cs->ctx(), cfg.gemm_mode);
   // inputs were produced on other streams: order them before our stream
   TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
   auto guard = cs->guard();
@@ -136,18 +133,16 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
       const int64_t ldq = 4 * Kp + 8 <= 2560 ? 1280 : 2 * Kp;
       pairs_->Q = torch::empty({V, ldq}, torch::TensorOptions().dtype(torch::kInt16).device(F.device()))
                       .narrow(1, 0, 2 * Kp);
-      hip_check(nts_hip_h2_split_rows_planar(cs->ctx(), (uint64_t)V, (uint32_t)K, F.data_ptr<float>(),
-                                             (uint64_t)F.stride(0), (uint32_t)Kp,
-                                             reinterpret_cast<uint16_t*>(pairs_->Q.data_ptr<int16_t>()),
-                                             (uint64_t)ldq, pairs_->rs.data_ptr<float>()),
-                "nts_hip_h2_split_rows_planar");
+      NTS_CALL(nts_hip_h2_split_rows_planar, cs->ctx(), (uint64_t)V, (uint32_t)K,
+               F.data_ptr<float>(), (uint64_t)F.stride(0), (uint32_t)Kp,
+               reinterpret_cast<uint16_t*>(pairs_->Q.data_ptr<int16_t>()), (uint64_t)ldq,
+               pairs_->rs.data_ptr<float>());
     } else {
       pairs_->P = torch::empty({V, Kp}, torch::TensorOptions().dtype(torch::kInt32).device(F.device()));
-      hip_check(nts_hip_h2_split_rows(cs->ctx(), (uint64_t)V, (uint32_t)K, F.data_ptr<float>(),
-                                      (uint64_t)F.stride(0), (uint32_t)Kp,
-                                      reinterpret_cast<uint32_t*>(pairs_->P.data_ptr<int32_t>()),
-                                      (uint64_t)Kp, pairs_->rs.data_ptr<float>()),
-                "nts_hip_h2_split_rows");
+      NTS_CALL(nts_hip_h2_split_rows, cs->ctx(), (uint64_t)V, (uint32_t)K, F.data_ptr<float>(),
+               (uint64_t)F.stride(0), (uint32_t)Kp,
+               reinterpret_cast<uint32_t*>(pairs_->P.data_ptr<int32_t>()), (uint64_t)Kp,
+               pairs_->rs.data_ptr<float>());
     }
   }
   // CSR transposes only where a graph-op backward runs (every hop but the
@@ -186,10 +181,10 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // size the scratch arenas once so the training loop never allocates
   uint64_t items = graph->global_vertices;
   for (auto* s : sampler->ssg->sampled_sgs) items = std::max<uint64_t>({items, s->e_cap, s->v_cap});
-  hip_check(nts_hip_ctx_reserve(cs->ctx(), graph->global_vertices, items), "nts_hip_ctx_reserve");
+  NTS_CALL(nts_hip_ctx_reserve, cs->ctx(), graph->global_vertices, items);
   if (ss) {
-    hip_check(nts_hip_ctx_reserve(ss->ctx(), graph->global_vertices, items), "nts_hip_ctx_reserve");
-    hip_check(nts_hip_ctx_set_gemm_mode(ss->ctx(), cfg.gemm_mode), "nts_hip_ctx_set_gemm_mode");
+    NTS_CALL(nts_hip_ctx_reserve, ss->ctx(), graph->global_vertices, items);
+    NTS_CALL(nts_hip_ctx_set_gemm_mode, ss->ctx(), cfg.gemm_mode);
   }
   // The bottom graph op Y_0 = A_0 X depends on the sampled graph and the
   // feature table only (not on the weights), so it is issued right behind the
@@ -283,10 +278,8 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
   if (cfg.root_weight)  // the backward's inverse maps, next to the sampling
     for (auto* s : sampler->ssgs[slot]->sampled_sgs)
       if (s->src_dst.defined())
-        hip_check(nts_hip_root_inverse_map(st.ctx(), s->dev_dst_local_id(), s->dev_v_size(),
-                                           s->v_cap, s->dev_src_size(), s->s_cap,
-                                           dptr<uint32_t>(s->src_dst)),
-                  "nts_hip_root_inverse_map");
+        NTS_CALL(nts_hip_root_inverse_map, st.ctx(), s->dev_dst_local_id(), s->dev_v_size(),
+                 s->v_cap, s->dev_src_size(), s->s_cap, dptr<uint32_t>(s->src_dst));
   if (!cfg.multi_label) {  // load_label_gpu for this batch, on the sampling stream next to its
      // subgraph (off the training stream; ordered by ready_[slot] below);
      // multi_label: the loss reads the packed table by the seeds' ids itself
@@ -297,10 +290,8 @@ void GCN_SAMPLE_ALLGPU_impl::issue(int slot, NtsStream& st) {
       t = torch::empty({std::max<int64_t>(n, cfg.batch_size)},
                        torch::TensorOptions().dtype(torch::kInt64).device(torch::kCUDA, graph->device));
     if (n > 0)
-      hip_check(nts_hip_gather_labels(st.ctx(), L_GT.data_ptr<int64_t>(),
-                                      q->sampled_sgs[0]->dev_dst(), nullptr, (uint32_t)n,
-                                      t.data_ptr<int64_t>()),
-                "nts_hip_gather_labels");
+      NTS_CALL(nts_hip_gather_labels, st.ctx(), L_GT.data_ptr<int64_t>(),
+               q->sampled_sgs[0]->dev_dst(), nullptr, (uint32_t)n, t.data_ptr<int64_t>());
   }
   if (early_) {
     auto guard = st.guard();
@@ -486,7 +477,7 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
         if (fuse) {
           const bool bits = s->act_bits.defined() && nts_hip_act_bits_words((uint32_t)X.size(1));
           ab = {X.data_ptr<float>(), (uint64_t)X.stride(0),
-                p < 1.0 ? 1.0f / (1.0f - (float)p) : 0.f,
+                (float)keep_scale(p),
                 bits ? reinterpret_cast<const uint32_t*>(s->act_bits.data_ptr<int32_t>()) : nullptr};
         }
         sg->sampled_sgs[hop - 1]->act_bwd = ab;
@@ -523,11 +514,9 @@ std::vector<NtsVar> GCN_SAMPLE_ALLGPU_impl::forward(SampledSubgraph* sg, bool ke
       X = ctx.runVertexForward(
           [&](NtsVar& a) {
             NtsVar Z = P[0]->forward(a);
-            hip_check(nts_hip_pd_load_share(cs->ctx(), dptr<uint32_t>(s->omit_row), nullptr,
-                                            s->v_size, pd_share_.data_ptr<float>(),
-                                            (uint64_t)pd_share_.stride(0), (uint32_t)Z.size(1),
-                                            Z.data_ptr<float>(), (uint64_t)Z.stride(0)),
-                      "nts_hip_pd_load_share");
+            NTS_CALL(nts_hip_pd_load_share, cs->ctx(), dptr<uint32_t>(s->omit_row), nullptr,
+                     s->v_size, pd_share_.data_ptr<float>(), (uint64_t)pd_share_.stride(0),
+                     (uint32_t)Z.size(1), Z.data_ptr<float>(), (uint64_t)Z.stride(0));
             if (l == L - 1) return Z.log_softmax(1);
             return hip_relu_dropout(Z, p, dropout_key(), off, cs.get());
           },
@@ -1008,35 +997,25 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full() {
     }
     const float* coef = cfg.edge_weighted ? dptr<float>(graph->edge_prob) : nullptr;
     if (coef && xr.dtype() == torch::kFloat16)  // edge_weighted: the _coef siblings
-      hip_check(nts_hip_spmm_graph_fwd_coef_h(cs->ctx(), &g, coef, 0, (uint64_t)V, wt, relu ? 1 : 0,
-                                              dptr<const uint16_t>(xr), (uint64_t)xr.stride(0),
-                                              (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                              (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd_coef_h");
+      NTS_CALL(nts_hip_spmm_graph_fwd_coef_h, cs->ctx(), &g, coef, 0, (uint64_t)V, wt, relu ? 1 : 0,
+               dptr<const uint16_t>(xr), (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+               y.data_ptr<float>(), (uint64_t)y.stride(0));
     else if (coef)
-      hip_check(nts_hip_spmm_graph_fwd_coef(cs->ctx(), &g, coef, 0, (uint64_t)V, wt, relu ? 1 : 0,
-                                            xr.data_ptr<float>(), (uint64_t)xr.stride(0),
-                                            (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                            (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd_coef");
+      NTS_CALL(nts_hip_spmm_graph_fwd_coef, cs->ctx(), &g, coef, 0, (uint64_t)V, wt, relu ? 1 : 0,
+               xr.data_ptr<float>(), (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+               y.data_ptr<float>(), (uint64_t)y.stride(0));
     else if (xr.dtype() == torch::kFloat16)  // feature_f16: layer 0 reads the half table
-      hip_check(nts_hip_spmm_graph_fwd_h(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
-                                         dptr<const uint16_t>(xr), (uint64_t)xr.stride(0),
-                                         (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                         (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd_h");
+      NTS_CALL(nts_hip_spmm_graph_fwd_h, cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+               dptr<const uint16_t>(xr), (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+               y.data_ptr<float>(), (uint64_t)y.stride(0));
     else if (max_aggr())
-      hip_check(nts_hip_spmm_graph_fwd_max(cs->ctx(), &g, 0, (uint64_t)V, relu ? 1 : 0,
-                                           xr.data_ptr<float>(), (uint64_t)xr.stride(0),
-                                           (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                           (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd_max");
+      NTS_CALL(nts_hip_spmm_graph_fwd_max, cs->ctx(), &g, 0, (uint64_t)V, relu ? 1 : 0,
+               xr.data_ptr<float>(), (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+               y.data_ptr<float>(), (uint64_t)y.stride(0));
     else
-      hip_check(nts_hip_spmm_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
-                                       xr.data_ptr<float>(), (uint64_t)xr.stride(0),
-                                       (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                       (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd");
+      NTS_CALL(nts_hip_spmm_graph_fwd, cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+               xr.data_ptr<float>(), (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+               y.data_ptr<float>(), (uint64_t)y.stride(0));
     if (cfg.profile) (void)hipEventRecord(evs.back().second, st);
     return y;
   };
@@ -1147,15 +1126,11 @@ NtsVar GCN_SAMPLE_ALLGPU_impl::infer_full_gat() {
         evs.push_back({a, b});
         (void)hipEventRecord(a, st);
       }
-      hip_check(nts_hip_gat_scores(cs->ctx(), H.data_ptr<float>(), (uint64_t)H.stride(0),
-                                   (uint64_t)V, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(),
-                                   S.data_ptr<float>()),
-                "nts_hip_gat_scores");
-      hip_check(nts_hip_gat_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, H.data_ptr<float>(),
-                                      (uint64_t)H.stride(0), (uint32_t)K, (uint32_t)D,
-                                      S.data_ptr<float>(), Y.data_ptr<float>(),
-                                      (uint64_t)Y.stride(0), mean ? 1 : 0),
-                "nts_hip_gat_graph_fwd");
+      NTS_CALL(nts_hip_gat_scores, cs->ctx(), H.data_ptr<float>(), (uint64_t)H.stride(0),
+               (uint64_t)V, (uint32_t)K, (uint32_t)D, A.data_ptr<float>(), S.data_ptr<float>());
+      NTS_CALL(nts_hip_gat_graph_fwd, cs->ctx(), &g, 0, (uint64_t)V, H.data_ptr<float>(),
+               (uint64_t)H.stride(0), (uint32_t)K, (uint32_t)D, S.data_ptr<float>(),
+               Y.data_ptr<float>(), (uint64_t)Y.stride(0), mean ? 1 : 0);
       if (cfg.profile) (void)hipEventRecord(evs.back().second, st);
       X = Y;
     }
@@ -1214,12 +1189,10 @@ std::pair<std::vector<uint32_t>, std::vector<uint32_t>> GCN_SAMPLE_ALLGPU_impl::
   const int layers = (int)cfg.fanout.size();
   for (uint64_t b = 0; b < n_sb; ++b) {
     const uint64_t beg = b * sbs, n = std::min<uint64_t>(sbs, ids.size() - beg);
-    hip_check(nts_hip_presample_counts(cs->ctx(), &g, dptr<uint32_t>(seeds) + beg, (uint32_t)n,
-                                       layers, dptr<uint32_t>(counts), dptr<uint32_t>(tmp)),
-              "nts_hip_presample_counts");
-    hip_check(nts_hip_presample_select(cs->ctx(), dptr<uint32_t>(counts), V, (float)cfg.pd_rate,
-                                       dptr<uint32_t>(out), dptr<uint32_t>(n_dev)),
-              "nts_hip_presample_select");
+    NTS_CALL(nts_hip_presample_counts, cs->ctx(), &g, dptr<uint32_t>(seeds) + beg, (uint32_t)n,
+             layers, dptr<uint32_t>(counts), dptr<uint32_t>(tmp));
+    NTS_CALL(nts_hip_presample_select, cs->ctx(), dptr<uint32_t>(counts), V, (float)cfg.pd_rate,
+             dptr<uint32_t>(out), dptr<uint32_t>(n_dev));
     cs->synchronize();
     cnt[b] = (uint32_t)n_dev.cpu().item<int32_t>();
     auto h = out.narrow(0, 0, (int64_t)cnt[b]).cpu();
@@ -1287,10 +1260,8 @@ void GCN_SAMPLE_ALLGPU_impl::pd_issue(int slot, NtsStream& st) {
     pd_next_key_++;
     const uint32_t n = pd_counts_[sb];
     auto guard = st.guard();
-    hip_check(nts_hip_pd_set_cache(st.ctx(), dptr<uint32_t>(pd_ids_) + pd_offset_[sb], n,
-                                   pd_next_key_, dptr<uint32_t>(pd_cache_map_),
-                                   dptr<uint32_t>(pd_cache_loc_)),
-              "nts_hip_pd_set_cache");
+    NTS_CALL(nts_hip_pd_set_cache, st.ctx(), dptr<uint32_t>(pd_ids_) + pd_offset_[sb], n,
+             pd_next_key_, dptr<uint32_t>(pd_cache_map_), dptr<uint32_t>(pd_cache_loc_));
     if (n) {
       const int ring = (int)(pd_next_key_ % kPdRing);
       pd_sampler_->work_offset = (VertexId)pd_offset_[sb];
@@ -1333,11 +1304,7 @@ void GCN_SAMPLE_ALLGPU_impl::pd_train(int slot) {
   auto guard = cs->guard();
   torch::NoGradGuard ng;
   NtsVar Wc = P[0]->W.contiguous();
-  hip_check(nts_hip_gemm_f32(cs->ctx(), 0, (int)n, (int)Wc.size(1), (int)Wc.size(0),
-                             pd_y_[ring].data_ptr<float>(), (uint64_t)pd_y_[ring].stride(0),
-                             Wc.data_ptr<float>(), (uint64_t)Wc.size(1),
-                             pd_share_.data_ptr<float>(), (uint64_t)pd_share_.stride(0)),
-            "nts_hip_gemm_f32(pd share)");
+  gemm(*cs, 0, fmat(pd_y_[ring]).top(n), Wc, fmat(pd_share_).top(n), "pd share");
   TORCH_CHECK(hipEventRecord(pd_sampler_->ssgs[ring]->consumed, (hipStream_t)cs->stream()) ==
                   hipSuccess,
               "hipEventRecord");
@@ -1368,7 +1335,7 @@ SamplerRate sampler_throughput(std::shared_ptr<FullyRepGraph> g, const std::vect
   s.coef = coef;
   uint64_t items = g->global_vertices;
   for (auto* x : s.ssg->sampled_sgs) items = std::max<uint64_t>({items, x->e_cap, x->v_cap});
-  hip_check(nts_hip_ctx_reserve(st.ctx(), g->global_vertices, items), "nts_hip_ctx_reserve");
+  NTS_CALL(nts_hip_ctx_reserve, st.ctx(), g->global_vertices, items);
   SamplerRate r;
   auto run = [&](int n, bool count) {
     int pending[kS] = {0, 0, 0};

@@ -1,5 +1,6 @@
 // LinkPredictor: link prediction composed from the NtsContext ops.
 #include "linkpred.hpp"
+#include "ops_util.hpp"
 
 #include <algorithm>
 #include <random>
@@ -52,7 +53,7 @@ LinkPredictor::LinkPredictor(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
                                 train_edges.sizes().vec(), !train_edges.is_cuda(),
                                 (int64_t)graph->global_vertices, graph->edge_prob.defined()});
   cs = std::make_unique<NtsStream>(graph->device, nullptr, (uint64_t)cfg.seed);
-  hip_check(nts_hip_ctx_set_gemm_mode(cs->ctx(), cfg.gemm_mode), "nts_hip_ctx_set_gemm_mode");
+  NTS_CALL(nts_hip_ctx_set_gemm_mode, cs->ctx(), cfg.gemm_mode);
   // inputs were produced on other streams: order them before our stream
   TORCH_CHECK(hipDeviceSynchronize() == hipSuccess, "hipDeviceSynchronize");
   auto guard = cs->guard();
@@ -72,7 +73,7 @@ LinkPredictor::LinkPredictor(std::shared_ptr<FullyRepGraph> g, NtsVar feature,
   const uint64_t pairs_cap = (uint64_t)cfg.batch_size * (1 + (uint64_t)cfg.neg_per_pos);
   uint64_t items = std::max<uint64_t>(graph->global_vertices, 8 * pairs_cap);
   for (auto* s : sampler->ssg->sampled_sgs) items = std::max<uint64_t>({items, s->e_cap, s->v_cap});
-  hip_check(nts_hip_ctx_reserve(cs->ctx(), graph->global_vertices, items), "nts_hip_ctx_reserve");
+  NTS_CALL(nts_hip_ctx_reserve, cs->ctx(), graph->global_vertices, items);
   for (size_t i = 0; i + 1 < cfg.layer_size.size(); ++i) {
     P.push_back(new Parameter((size_t)cfg.layer_size[i], (size_t)cfg.layer_size[i + 1],
                                     cfg.learn_rate, cfg.beta1, cfg.beta2, cfg.epsilon,
@@ -133,28 +134,24 @@ SampledSubgraph* LinkPredictor::build(LpBatch& b, FastSampler& s, const NtsVar& 
                 "hipMemsetAsync");
   if (cfg.lp_filter_neg) {
     const nts_graph_dev g = graph->dev();
-    hip_check(nts_hip_lp_batch_filtered(
-                  cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B, b.K,
-                  graph->global_vertices, seq, (uint32_t)b.destination.numel(),
-                  dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size), dptr<uint32_t>(b.pair_u),
-                  dptr<uint32_t>(b.pair_v), dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot),
-                  &g, dptr<uint32_t>(sorted_rows_), counters + 1),
-              "nts_hip_lp_batch_filtered");
+    NTS_CALL(nts_hip_lp_batch_filtered, cs->ctx(), dptr<uint32_t>(b.pos_src),
+             dptr<uint32_t>(b.pos_dst), b.B, b.K, graph->global_vertices, seq,
+             (uint32_t)b.destination.numel(), dptr<uint32_t>(b.destination),
+             dptr<uint32_t>(b.v_size), dptr<uint32_t>(b.pair_u), dptr<uint32_t>(b.pair_v),
+             dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot), &g,
+             dptr<uint32_t>(sorted_rows_), counters + 1);
   } else {
-    hip_check(nts_hip_lp_batch(cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B,
-                               b.K, graph->global_vertices, seq, (uint32_t)b.destination.numel(),
-                               dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size),
-                               dptr<uint32_t>(b.pair_u), dptr<uint32_t>(b.pair_v),
-                               dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot)),
-              "nts_hip_lp_batch");
+    NTS_CALL(nts_hip_lp_batch, cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst), b.B,
+             b.K, graph->global_vertices, seq, (uint32_t)b.destination.numel(),
+             dptr<uint32_t>(b.destination), dptr<uint32_t>(b.v_size), dptr<uint32_t>(b.pair_u),
+             dptr<uint32_t>(b.pair_v), dptr<uint32_t>(b.inc_offset), dptr<uint32_t>(b.inc_slot));
   }
   if (cfg.lp_exclude)
-    hip_check(nts_hip_lp_exclude_keys(cs->ctx(), dptr<uint32_t>(b.pos_src), dptr<uint32_t>(b.pos_dst),
-                                      b.B, cfg.lp_exclude == 2, graph->global_vertices,
-                                      (uint32_t)b.excl_keys.numel(),
-                                      reinterpret_cast<uint64_t*>(b.excl_keys.data_ptr<int64_t>()),
-                                      dptr<uint32_t>(b.n_keys)),
-              "nts_hip_lp_exclude_keys");
+    NTS_CALL(nts_hip_lp_exclude_keys, cs->ctx(), dptr<uint32_t>(b.pos_src),
+             dptr<uint32_t>(b.pos_dst), b.B, cfg.lp_exclude == 2, graph->global_vertices,
+             (uint32_t)b.excl_keys.numel(),
+             reinterpret_cast<uint64_t*>(b.excl_keys.data_ptr<int64_t>()),
+             dptr<uint32_t>(b.n_keys));
   b.pairs = {dptr<uint32_t>(b.pair_u),   dptr<uint32_t>(b.pair_v), dptr<uint32_t>(b.inc_offset),
              dptr<uint32_t>(b.inc_slot), dptr<uint32_t>(b.v_size), b.B,
              b.K};
@@ -181,11 +178,9 @@ SampledSubgraph* LinkPredictor::build(LpBatch& b, FastSampler& s, const NtsVar& 
         o.edge_weight_backward = dptr<float>(l->edge_weight_backward);
       }
       o.sizes = dptr<uint32_t>(l->sizes);
-      hip_check(nts_hip_lp_mask_block(
-                    cs->ctx(), &o,
-                    reinterpret_cast<const uint64_t*>(b.excl_keys.data_ptr<int64_t>()),
-                    dptr<uint32_t>(b.n_keys), had, counters),
-                "nts_hip_lp_mask_block");
+      NTS_CALL(nts_hip_lp_mask_block, cs->ctx(), &o,
+               reinterpret_cast<const uint64_t*>(b.excl_keys.data_ptr<int64_t>()),
+               dptr<uint32_t>(b.n_keys), had, counters);
     }
   }
   return s.finish_gpu_sample(0);
@@ -357,17 +352,13 @@ NtsVar LinkPredictor::embed_full() {
     NtsVar xr = row_major(x);
     NtsVar y = row_padded_empty(V, xr.size(1), graph->device);
     if (cfg.edge_weighted)
-      hip_check(nts_hip_spmm_graph_fwd_coef(cs->ctx(), &g, dptr<float>(graph->edge_prob), 0,
-                                            (uint64_t)V, wt, relu ? 1 : 0, xr.data_ptr<float>(),
-                                            (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
-                                            y.data_ptr<float>(), (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd_coef");
+      NTS_CALL(nts_hip_spmm_graph_fwd_coef, cs->ctx(), &g, dptr<float>(graph->edge_prob), 0,
+               (uint64_t)V, wt, relu ? 1 : 0, xr.data_ptr<float>(), (uint64_t)xr.stride(0),
+               (uint32_t)xr.size(1), y.data_ptr<float>(), (uint64_t)y.stride(0));
     else
-      hip_check(nts_hip_spmm_graph_fwd(cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
-                                       xr.data_ptr<float>(), (uint64_t)xr.stride(0),
-                                       (uint32_t)xr.size(1), y.data_ptr<float>(),
-                                       (uint64_t)y.stride(0)),
-                "nts_hip_spmm_graph_fwd");
+      NTS_CALL(nts_hip_spmm_graph_fwd, cs->ctx(), &g, 0, (uint64_t)V, wt, relu ? 1 : 0,
+               xr.data_ptr<float>(), (uint64_t)xr.stride(0), (uint32_t)xr.size(1),
+               y.data_ptr<float>(), (uint64_t)y.stride(0));
     return y;
   };
   const bool was_train = ctx.is_train();
@@ -427,15 +418,13 @@ std::vector<std::pair<std::string, double>> LinkPredictor::evaluate_full(
     for (int64_t off = 0; off < m; off += cfg.batch_size) {
       const int64_t B = std::min<int64_t>(cfg.batch_size, m - off);
       uint32_t* out = cg + side * m + off;
-      hip_check(nts_hip_lp_rank(cs->ctx(), H.data_ptr<float>(), (uint64_t)H.stride(0),
-                                (uint32_t)H.size(1), (uint32_t)V, dptr<uint32_t>(heads) + off,
-                                dptr<uint32_t>(tails) + off, (uint32_t)B,
-                                cand.defined() ? dptr<uint32_t>(cand) : nullptr,
-                                cand.defined() ? (uint64_t)cand.numel() : 0,
-                                filtered ? g.column_offset : nullptr,
-                                filtered ? dptr<uint32_t>(sorted_rows_) : nullptr, out, out + total,
-                                out + 2 * total),
-                "nts_hip_lp_rank");
+      NTS_CALL(nts_hip_lp_rank, cs->ctx(), H.data_ptr<float>(), (uint64_t)H.stride(0),
+               (uint32_t)H.size(1), (uint32_t)V, dptr<uint32_t>(heads) + off,
+               dptr<uint32_t>(tails) + off, (uint32_t)B,
+               cand.defined() ? dptr<uint32_t>(cand) : nullptr,
+               cand.defined() ? (uint64_t)cand.numel() : 0, filtered ? g.column_offset : nullptr,
+               filtered ? dptr<uint32_t>(sorted_rows_) : nullptr, out, out + total,
+               out + 2 * total);
     }
   }
   // the metrics on the device, in double; one small tensor comes back

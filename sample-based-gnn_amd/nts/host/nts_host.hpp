@@ -634,6 +634,10 @@ struct PairTable {
   NtsVar rs;  // fp32 [V] row scales
   bool tn = true;
   NtsVar Q;   // int16 [V, 2 Kp] planar form (defined: the weight gradient on k_h2_tn3)
+  // the tables as the C-ABI takes them, and Kp of the one that is there
+  const uint16_t* q_ptr() const { return reinterpret_cast<const uint16_t*>(Q.data_ptr<int16_t>()); }
+  const uint32_t* p_ptr() const { return reinterpret_cast<const uint32_t*>(P.data_ptr<int32_t>()); }
+  int kp() const { return (int)(Q.defined() ? Q.size(1) / 2 : P.size(1)); }
 };
 // Stream-phase hooks of the transform-first bottom layer (the driver's
 // sampler gating, GCNConfig::sampler_gate): called on the host right after

@@ -25,7 +25,9 @@ def build(verbose: bool = False):
     os.environ.setdefault("MAX_JOBS", str(min(os.cpu_count() or 8, 16)))
     mod = cpp_extension.load(
         name=NAME,
-        sources=[str(SRC / f) for f in ("core.cpp", "options.cpp", "gcn.cpp", "linkpred.cpp", "bindings.cpp")],
+        sources=[str(SRC / f) for f in ("runtime.cpp", "sampler.cpp", "graph_ops.cpp", "nn_ops.cpp",
+                                        "attention.cpp", "options.cpp", "gcn.cpp", "linkpred.cpp",
+                                        "bindings.cpp")],
         extra_include_paths=[str(ROOT / "include"), str(SRC), "/opt/rocm/include"],
         extra_cflags=["-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
                       "-Wno-unused-variable"],

@@ -58,7 +58,7 @@ def spmm_bytes(V, E, F):
 
 
 def block_bytes(V, E, K, D):
-    """the sampled kernel on the whole graph as a block: what core.cpp counts for it"""
+    """the sampled kernel on the whole graph as a block: what attention.cpp counts for it"""
     F = K * D
     return 4 * F * V + 4 * (V + 1) + (4 + 8 * K) * E + 4 * V + 8 * F + 4 * F * V
 
