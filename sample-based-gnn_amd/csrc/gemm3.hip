@@ -12,7 +12,8 @@
 // product exact in the fp32 accumulator of v_mfma_f32_16x16x32_bf16.  Six
 // bf16 MFMAs cost 6/16 of one fp32-input MFMA for the same k: 2.7x the fp32
 // rate.  The error vs an fp64 GEMM is measured against the native fp32 MFMA
-// kernels in tests/test_hip_kernels.py (test_split3_gemm_*).  Values beyond
+// kernels in tests/test_gemm_split3.py (test_split3_gemm_*) and, per layout
+// route, in tests/test_gemm_layout_kernel.py.  Values beyond
 // bf16's range behave like fp32 except |x| within 2^-8 of FLT_MAX (x0 rounds
 // to inf): irrelevant to activations and weights.
 //

@@ -941,7 +941,11 @@ int x3_nn(nts_hip_ctx* ctx, bool epi, int M, int N, int K, const float* A, uint6
     hipLaunchKernelGGL((k_x3_nn<E>), grid, dim3(kX3Threads), kX3NnLds, ctx->stream, M, N, K, A, \
                        lda, amap, bimg, C, ldc, rounds, ep);                                   \
   } while (0)
-  if (x3_nn7_ok(M, N, K, A, lda)) {
+  // k_x3_nn7's plain store is one unconditional 16-byte store per tile and
+  // lane: a C off 16 bytes or with ldc % 4 != 0 stays on k_x3_nn, which
+  // switches its store (the epilogue forms store floats)
+  const bool c16 = ldc % 4 == 0 && (uintptr_t)C % 16 == 0;
+  if (x3_nn7_ok(M, N, K, A, lda) && (epi || c16)) {
     // k_x3_nn7: 4-wave blocks, at most one per CU and column block, each wave
     // kX3N7RT tiles a round
     const int T7 = (M + 15) / 16;

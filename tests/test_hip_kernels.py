@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from gat_blocks import gat_chain as _gat_torch  # the materialised-message reference chain
+from gemm_layouts import _dropout_keep, _philox4x32_10  # noqa: F401  (the Philox keep-mask restatement)
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -792,37 +793,6 @@ def test_gemm_tn_gather_rows(hip, M, N, K):
     torch.testing.assert_close(C.double(), Xg.double().t() @ G.double(), rtol=tol, atol=tol * 4)
     if ld == M:  # same operand layout -> same kernel and k order
         assert torch.equal(C, C2)
-
-
-def _philox4x32_10(c, k):
-    """Philox4x32-10 reference (numpy uint64 arithmetic), c: 4 x uint32 arrays, k: 2 ints."""
-    M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
-    c = [x.astype(np.uint64) for x in c]
-    k0, k1 = np.uint64(k[0]), np.uint64(k[1])
-    mask = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0 = np.uint64(M0) * c[0]
-        p1 = np.uint64(M1) * c[2]
-        hi0, lo0 = p0 >> np.uint64(32), p0 & mask
-        hi1, lo1 = p1 >> np.uint64(32), p1 & mask
-        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
-        k0 = (k0 + np.uint64(W0)) & mask
-        k1 = (k1 + np.uint64(W1)) & mask
-    return [x.astype(np.uint32) for x in c]
-
-
-def _dropout_keep(M, N, p, seed, offset):
-    """Element (row, col): 16 bits of Philox4x32-10 at counter {row/4, col/2, offset}
-    (word row % 4, low half for even col, high half for odd), kept iff >= floor(p * 2^16)."""
-    rows = np.arange(M, dtype=np.uint64)[:, None] * np.ones((1, N), np.uint64)
-    cols = np.ones((M, 1), np.uint64) * np.arange(N, dtype=np.uint64)[None, :]
-    c = [(rows >> np.uint64(2)).astype(np.uint32), (cols >> np.uint64(1)).astype(np.uint32),
-         np.full((M, N), offset & 0xFFFFFFFF, np.uint32), np.full((M, N), offset >> 32, np.uint32)]
-    w = _philox4x32_10(c, (seed & 0xFFFFFFFF, seed >> 32))
-    word = np.choose((rows & np.uint64(3)).astype(np.int64), w).astype(np.uint64)
-    bits = np.where((cols & np.uint64(1)) == 1, word >> np.uint64(16), word & np.uint64(0xFFFF))
-    thr = 65536 if p >= 1.0 else min(int(p * 65536.0), 65536)
-    return bits >= np.uint64(thr)
 
 
 @pytest.mark.parametrize("M,N,K,p", [(5000, 128, 602, 0.5), (333, 41, 100, 0.3), (1000, 128, 128, 0.0),
