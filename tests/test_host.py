@@ -212,7 +212,7 @@ def _gcn_chain_grads(drv, feat, labels, W0, dtype):
     X1 = torch.relu(agg(bottom, X0) @ W[0])
     out = (agg(top, X1) @ W[1]).log_softmax(1)
     tgt = labels.cpu()[top["destination"].cpu().long()]
-    torch.nn.functional.nll_loss(out.log_softmax(1), tgt).backward()
+    torch.nn.functional.nll_loss(out, tgt).backward()  # (out is the log-softmax already)
     return [w.grad for w in W]
 
 

@@ -64,6 +64,11 @@ def _nontrivial(drv, seed):
     return ws
 
 
+def _ln(Z, gamma, beta):
+    """LayerNorm over the columns of Z (the expression of every chain here)"""
+    return torch.nn.functional.layer_norm(Z, (Z.shape[1],), gamma, beta, EPS)
+
+
 def _chain(lays, data, ws, dtype, root=False, mx=False, labels=None):
     """the model over the sampled layers `lays` (top first) in `dtype`; returns
     (parameters, loss, hidden outputs, gap of the top hop's maxima)"""
@@ -82,8 +87,7 @@ def _chain(lays, data, ws, dtype, root=False, mx=False, labels=None):
             Y = torch.cat([Y, own], 1)
         Z = Y @ P[l]
         if l < L - 1:
-            X = torch.relu(torch.nn.functional.layer_norm(Z, (Z.shape[1],), P[L + 2 * l],
-                                                          P[L + 2 * l + 1], EPS))
+            X = torch.relu(_ln(Z, P[L + 2 * l], P[L + 2 * l + 1]))
             hidden.append(X)
     dst = lays[0]["destination"].cpu().long()
     if labels is None:

@@ -43,6 +43,16 @@ def _dense(layer, dtype):
     return torch.from_numpy(A).to(dtype)
 
 
+def _pair_loss(X, lb):
+    """(mean BCE of the batch's pair scores on the embeddings X, the scores)"""
+    u = torch.from_numpy(lb["pair_u"].cpu().numpy().view(np.uint32).astype(np.int64))
+    v = torch.from_numpy(lb["pair_v"].cpu().numpy().view(np.uint32).astype(np.int64))
+    s = (X[u] * X[v]).sum(1)
+    y = torch.zeros_like(s)
+    y[:lb["B"]] = 1
+    return torch.nn.functional.binary_cross_entropy_with_logits(s, y), s
+
+
 def _chain(W, feat, lb, dtype):
     """the step's loss and weight gradients in libtorch at `dtype`"""
     layers = lb["layers"]
@@ -55,12 +65,7 @@ def _chain(W, feat, lb, dtype):
         X = Y @ Ws[l]
         if l < L - 1:
             X = torch.relu(X)
-    u = torch.from_numpy(lb["pair_u"].cpu().numpy().view(np.uint32).astype(np.int64))
-    v = torch.from_numpy(lb["pair_v"].cpu().numpy().view(np.uint32).astype(np.int64))
-    s = (X[u] * X[v]).sum(1)
-    y = torch.zeros_like(s)
-    y[:lb["B"]] = 1
-    loss = torch.nn.functional.binary_cross_entropy_with_logits(s, y)
+    loss, s = _pair_loss(X, lb)
     loss.backward()
     return float(loss.detach()), [w.grad for w in Ws], s.detach()
 
