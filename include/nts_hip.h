@@ -50,8 +50,9 @@ extern "C" {
                                       nts_hip_spmm_csr_bwd_postmask_bits);
                                   11: MT19937 re-run of a short stream (nts_hip_mt_budget_scale,
                                       nts_hip_mt_checkpoint, nts_hip_mt_rewind);
-                                      later entry points (nts_hip_lp_* among them) are
-                                      additions: no struct or existing signature changed */
+                                      later entry points (nts_hip_lp_*, nts_hip_random_walk and
+                                      nts_hip_induced_layer among them) are additions: no
+                                      struct or existing signature changed */
 
 /* status codes */
 #define NTS_OK 0
@@ -294,6 +295,53 @@ int nts_hip_sample_layer_coef(nts_hip_ctx *ctx, const nts_graph_dev *graph,
 int nts_hip_weighted_keys(nts_hip_ctx *ctx, const nts_graph_dev *graph, const float *edge_prob,
                           const uint32_t *destination, uint32_t v, int layer,
                           uint64_t batch_seq, uint32_t *keys_out, const uint64_t *out_offset);
+
+/* ---- subgraph sampling ---------------------------------------- */
+/* Random walks over in-neighbours (the CSC row of a vertex: the direction
+ * messages come from), GraphSAINT-RW's node set.  roots[0 .. n) with
+ * n = min(*n_roots, cap) (device ids, device count: the convention of
+ * nts_sampcsc_dev::v_size); out receives cap * (walk_len + 1) ids, walk-major:
+ * out[i (walk_len + 1)] = roots[i], and step t < walk_len of the walk rooted at
+ * r, standing at u, moves to the neighbour at CSC position
+ *   mulhi32(x, deg(u)),  x = word 0 of Philox4x32-10(counter = (0, r,
+ *   0x10000000 | t, lo32(batch_seq)), keyed as the sampler's streams are).
+ * The counter words in use are disjoint: the plain layer number (PHILOX),
+ * layer | 0x80000000 (PHILOX_SHARED), layer | 0x40000000 (weighted),
+ * 0x20000000 | t (link prediction's negatives) and 0x10000000 | t here
+ * (walk_len < 2^28).  deg(u) == 0: the walk stays at u.  No rejection step:
+ * the position's bias is at most deg / 2^32.  Two roots with the same id walk
+ * the same path.  Slots of walks past the live count are not written.
+ * Stateless; two calls give the same bytes. */
+int nts_hip_random_walk(nts_hip_ctx *ctx, const nts_graph_dev *graph, const uint32_t *roots,
+                        const uint32_t *n_roots, uint32_t cap, int walk_len, uint64_t batch_seq,
+                        uint32_t *out);
+/* The block a vertex set induces: out->destination / out->v_size are inputs as
+ * for nts_hip_sample_layer, set_ids[0 .. min(*set_size, set_cap)) is the set
+ * (device ids in any order, duplicates allowed, device count).  Every
+ * destination must be a member of the set (the caller guarantees it; it is not
+ * checked on the device).  Output, in nts_hip_sample_layer's layout:
+ *   source       the distinct members of the set, ascending — the whole set,
+ *                members that are nobody's neighbour included;
+ *   column i     the neighbours of destination[i] that are in the set, in the
+ *                graph's CSC order (a neighbour listed twice is kept twice);
+ *   row_indices  local ids into source; sample_ans, edge_dst, the weight_type
+ *                weights (NTS_WEIGHT_UP_DEGREE honoured), the CSR transpose with
+ *                its weights, csr_edge_id, dst_local_id, sizes (overflow flag
+ *                included) and sizes_host as nts_hip_sample_layer fills them —
+ *                the same launches from the frontier compaction on.
+ * A block above e_cap is cut at a destination boundary as a sampled layer is
+ * (sizes[1] = the offset of the first destination that does not fit, flag bit
+ * 0), and every column_offset entry is then clamped to sizes[1]: the cut
+ * destinations are empty columns, so a consumer enqueued before the host reads
+ * the flag stays inside the written edges.
+ * Nothing is drawn: there is no rng_mode, layer or batch_seq argument and no
+ * generator state is touched (an MT19937 caller has nothing to keep in step).
+ * Integer work only apart from the weights, no atomics on floats: two calls
+ * give the same bytes.  NTS_ERR_INVALID, before any write: set_ids == NULL,
+ * set_size == NULL, out->omit_map set. */
+int nts_hip_induced_layer(nts_hip_ctx *ctx, const nts_graph_dev *graph, const uint32_t *set_ids,
+                          const uint32_t *set_size, uint32_t set_cap, int weight_type,
+                          nts_sampcsc_dev *out);
 
 /* ---- feature / label movement ------------------------------------------- */
 /* out[i,:] = table[index[i],:] for i < *n (n == NULL: n_cap rows).

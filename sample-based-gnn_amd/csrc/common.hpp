@@ -273,6 +273,10 @@ struct CountArgs {
   uint32_t omit_key;
   const uint32_t* omit_loc;
   uint32_t* omit_row;
+  // set (nts_hip_induced_layer): item i's count is counts[i] as given, not a
+  // degree; goff, dst, fanout and the omit fields are not read.  counts may be
+  // the array the scan writes: a tile reads its items before it writes any
+  const uint32_t* counts = nullptr;
 };
 int count_scan(nts_hip_ctx* ctx, const CountArgs& ca, uint32_t* co, hipStream_t stream);
 // words the sampler's workspace layout keeps in front of its block counts

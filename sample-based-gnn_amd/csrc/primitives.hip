@@ -215,6 +215,14 @@ template <int IT>
 __device__ __forceinline__ void count_items(const CountArgs& ca, uint64_t base, uint64_t n,
                                             uint32_t (&x)[IT]) {
   const int t = threadIdx.x;
+  if (ca.counts) {  // the induced layer's counts, already per item
+#pragma unroll
+    for (int k = 0; k < IT; ++k) {
+      const uint64_t i = base + (uint64_t)k * kScanThreads + t;
+      x[k] = i < n ? ca.counts[i] : 0u;
+    }
+    return;
+  }
   uint32_t d[IT];
   uint64_t lo[IT], hi[IT];
 #pragma unroll

@@ -1985,6 +1985,110 @@ __global__ void k_csr_finalize(const uint32_t* __restrict__ skey, const uint32_t
     for (uint32_t r = 0; r <= s; ++r) ro[r] = 0;
 }
 
+
+// ---- subgraph sampling -----------------------------------------
+// Random walks over in-neighbours, one thread per walk: walk i of root r
+// writes out[i (len + 1) + t], position 0 the root.  Step t at vertex u moves to
+// the CSC neighbour at mulhi32(x, deg(u)), x = word 0 of the Philox stream
+// (0, r, 0x10000000 | t, batch_seq); deg(u) == 0 stays at u.  A walk is `len`
+// dependent loads (offset pair, then the neighbour): latency-bound, kept plain.
+constexpr uint32_t kWalkTag = 0x10000000u;
+__global__ void k_random_walk(const uint64_t* __restrict__ goff, const uint32_t* __restrict__ grows,
+                              const uint32_t* __restrict__ roots, const uint32_t* n_dev,
+                              uint32_t cap, uint32_t len, uint64_t seed, uint64_t batch_seq,
+                              uint32_t* __restrict__ out) {
+  const uint32_t n = min(*n_dev, cap);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t r = roots[i];
+    uint32_t* w = out + (uint64_t)i * (len + 1);
+    w[0] = r;
+    uint32_t u = r;
+    for (uint32_t t = 0; t < len; ++t) {
+      const uint64_t beg = goff[u];
+      const uint32_t deg = (uint32_t)(goff[u + 1] - beg);
+      if (deg) {
+        const uint32_t x = philox_word(seed, r, kWalkTag | t, batch_seq, 0);
+        u = grows[beg + __umulhi(x, deg)];
+      }
+      w[t + 1] = u;
+    }
+  }
+}
+
+// stage a of the induced layer: the set's members into the byte map (an id
+// outside the graph is dropped rather than written past the map)
+__global__ void k_set_mark(const uint32_t* __restrict__ ids, const uint32_t* n_dev, uint32_t cap,
+                           uint64_t n_vertices, uint8_t* __restrict__ marks) {
+  const uint32_t n = min(*n_dev, cap);
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t id = ids[i];
+    if (id < n_vertices) marks[id] = 1;
+  }
+}
+
+// stages b and c: one wave per destination, its CSC row in 64-wide strides.
+// FILL = false: counts[i] = neighbours of dst[i] that are marked (the ballot's
+// popcount, summed).  FILL = true: the kept neighbour at lane l of a stride
+// takes slot co[i] + (kept in the strides before) + popcount(ballot below l),
+// so the column keeps the graph's CSC order without atomics; a destination
+// whose column does not fit whole is skipped, as the sampler's selection does
+// (count_scan flagged the overflow and cut e_size at its first edge).
+template <bool FILL>
+__global__ __launch_bounds__(kSelThreads) void k_induced(
+    const uint64_t* __restrict__ goff, const uint32_t* __restrict__ grows,
+    const uint32_t* __restrict__ dst, const uint32_t* v_in, uint32_t v_cap,
+    const uint8_t* __restrict__ marks, uint32_t* __restrict__ counts,
+    const uint32_t* __restrict__ co, uint32_t e_cap, uint32_t* __restrict__ ans,
+    uint32_t* __restrict__ edst) {
+  const uint32_t v = min(*v_in, v_cap);
+  const int lane = threadIdx.x & 63;
+  const uint64_t below = (1ull << lane) - 1;
+  for (uint32_t i = blockIdx.x * kSelWaves + (threadIdx.x >> 6); i < v;
+       i += gridDim.x * kSelWaves) {
+    const uint32_t d = dst[i];
+    const uint64_t beg = goff[d];
+    const uint32_t deg = (uint32_t)(goff[d + 1] - beg);
+    uint32_t run = 0, c = 0;
+    if constexpr (FILL) {
+      c = co[i];
+      if (c + (co[i + 1] - c) > e_cap) continue;  // capacity overflow (flagged by count_scan)
+    }
+    for (uint32_t k0 = 0; k0 < deg; k0 += kWave) {
+      const uint32_t k = k0 + lane;
+      uint32_t gsrc = 0;
+      bool in = false;
+      if (k < deg) {
+        gsrc = grows[beg + k];
+        in = marks[gsrc] != 0;
+      }
+      const uint64_t b = __ballot(in);
+      if constexpr (FILL) {
+        if (in) {
+          const uint32_t pos = c + run + (uint32_t)__popcll(b & below);
+          ans[pos] = gsrc;
+          edst[pos] = i;
+        }
+      }
+      run += (uint32_t)__popcll(b);
+    }
+    if constexpr (!FILL) {
+      if (lane == 0) counts[i] = run;
+    }
+  }
+}
+
+
+// An induced layer that overflowed its edge capacity: every offset is clamped
+// to e_size, so the destinations that were cut read as empty columns.  The
+// driver launches its bottom aggregation behind the sampling, before the host
+// has seen the overflow flag; with the offsets left as counted that launch
+// would walk row_indices past e_size.  No flag: nothing is written.
+__global__ void k_induced_clamp(uint32_t* __restrict__ co, const uint32_t* sizes) {
+  if ((sizes[3] & 1u) == 0) return;
+  const uint32_t v = sizes[0], e = sizes[1];
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= v; i += gridDim.x * blockDim.x)
+    if (co[i] > e) co[i] = e;
+}
 }  // namespace nts_hip
 
 namespace nts_hip {
@@ -2181,6 +2285,172 @@ using namespace nts_hip;
 // `edge_coef` != nullptr (nts_hip_sample_layer_coef, which has refused what the
 // coefficient path does not cover): the COEF instantiations of the selection
 // and of k_relabel, and the weights always travel through the CSR transpose.
+// The scratch of one layer call (u32 words, then the sort's bytes): the count
+// scan's words, the frontier's tile counts and their scan, the CSR transpose's
+// keys / edge ids / payloads, the UP_DEGREE counts, `mt_n` words of the caller
+// (the MT19937 modes), the radix sort's workspace.
+struct LayerScratch {
+  uint32_t *t_blk, *t_scan_blk, *t_skey, *t_seid, *t_sdst, *t_swf, *t_up, *t_mt;
+  void* t_sort;
+  uint64_t up_n;
+};
+
+static int layer_scratch(nts_hip_ctx* ctx, const nts_sampcsc_dev* o, bool csr, bool up,
+                         uint32_t nblk_marks, uint64_t mt_n, LayerScratch* ls) {
+  // scratch layout (u32 words)
+  auto al = [](uint64_t x) { return (x + 63) / 64 * 64; };
+  const uint64_t scan_co = al(count_scan_tmp_elems(o->v_cap) + 1);
+  const uint64_t blk = al(nblk_marks + 1);
+  const uint64_t scan_blk = al(scan_tmp_elems<uint32_t>(nblk_marks) + 1);
+  const uint64_t sort_k = csr ? al(o->e_cap) : 0, sort_v = sort_k;
+  const uint64_t sort_p = csr ? 2 * al(o->e_cap) : 0;  // k_csr_bucket's payloads
+  const size_t sort_tmp =
+      csr ? std::max(radix_tmp_bytes(o->e_cap), radix_pass_tmp_bytes(o->e_cap)) : 0;
+  const uint64_t up_n = up ? al(o->s_cap) : 0;
+  const size_t need = (scan_co + blk + scan_blk + sort_k + sort_v + sort_p + up_n + mt_n) *
+                          sizeof(uint32_t) + sort_tmp + 256;
+  NTS_RET(ensure_scratch(ctx, need));
+  uint32_t* w0 = (uint32_t*)ctx->scratch;
+  uint32_t* t_scan_co = w0;
+  ls->t_blk = t_scan_co + scan_co;
+  ls->t_scan_blk = ls->t_blk + blk;
+  ls->t_skey = ls->t_scan_blk + scan_blk;
+  ls->t_seid = ls->t_skey + sort_k;
+  ls->t_sdst = ls->t_seid + sort_v;
+  ls->t_swf = ls->t_sdst + sort_p / 2;
+  ls->t_up = ls->t_sdst + sort_p;
+  ls->t_mt = ls->t_up + up_n;
+  ls->t_sort = (void*)(ls->t_mt + mt_n);
+  ls->up_n = up_n;
+  return NTS_OK;
+}
+
+// Stages 3-5 of a layer, behind whatever filled sample_ans / edge_dst /
+// column_offset / sizes[0..1] and marked the frontier in ctx->marks: the
+// frontier from the byte map (cleared again), dst_local_id, relabel + weights,
+// the CSR transpose.  nts_hip_sample_layer* and nts_hip_induced_layer both end
+// here.
+static int layer_tail(nts_hip_ctx* ctx, const nts_graph_dev* g, nts_sampcsc_dev* o,
+                      int weight_type, bool up, bool coef, const LayerScratch& ls,
+                      hipStream_t st) {
+  const uint64_t V = g->n_vertices;
+  const uint32_t nblk_marks = ceil_div(V, kMarkTile);
+  const bool csr = o->row_offset != nullptr;
+  uint32_t *t_blk = ls.t_blk, *t_scan_blk = ls.t_scan_blk, *t_skey = ls.t_skey,
+           *t_seid = ls.t_seid, *t_sdst = ls.t_sdst, *t_swf = ls.t_swf, *t_up = ls.t_up;
+  void* t_sort = ls.t_sort;
+  const uint64_t up_n = ls.up_n;
+  const uint32_t gv = std::max(1u, std::min(ceil_div(o->v_cap, 256), kMaxGrid));
+  const uint32_t ge = std::max(1u, std::min(ceil_div(o->e_cap, 256), kMaxGrid));
+  if (o->dst_local_id) {
+    hipLaunchKernelGGL(k_mark_dst, dim3(gv), dim3(256), 0, st, o->destination, o->sizes,
+                       ctx->marks);
+    NTS_LAUNCH_CHECK();
+  }
+
+  // 3) frontier: ascending compaction of the byte map — single pass up to
+  // kMarkFusedMaxTiles tiles (C2's 57), else count + write: at products' 598
+  // tiles the look-back chain took 23 us a layer against 5 + 9 for the pair
+  constexpr uint32_t kMarkFusedMaxTiles = 256;
+  if (nblk_marks <= kMarkFusedMaxTiles) {
+    NTS_RET(ensure_scan_state(ctx, scan1_state_elems((uint64_t)nblk_marks * 4096)));
+    hipLaunchKernelGGL(k_mark_fused, dim3(nblk_marks), dim3(kMarkThreads), 0, st, ctx->marks,
+                       nblk_marks, V, o->s_cap, o->source, ctx->src_index, o->sizes,
+                       ctx->scan_state, scan_next_epoch(ctx), scan_ticket(ctx));
+    NTS_LAUNCH_CHECK();
+  } else {
+    hipLaunchKernelGGL(k_mark_count, dim3(nblk_marks), dim3(kMarkThreads), 0, st, ctx->marks,
+                       t_blk);
+    NTS_LAUNCH_CHECK();
+    if (nblk_marks <= kMarkDirectTiles) {  // up to 8M vertices: no scan kernel
+      hipLaunchKernelGGL(k_mark_write<true>, dim3(nblk_marks), dim3(kMarkThreads), 0, st,
+                         ctx->marks, t_blk, nblk_marks, V, o->s_cap, o->source, ctx->src_index,
+                         o->sizes);
+    } else {
+      NTS_RET(scan_exclusive<uint32_t>(t_blk, t_blk, nullptr, nblk_marks, t_scan_blk, st));
+      hipLaunchKernelGGL(k_mark_write<false>, dim3(nblk_marks), dim3(kMarkThreads), 0, st,
+                         ctx->marks, t_blk, nblk_marks, V, o->s_cap, o->source, ctx->src_index,
+                         o->sizes);
+    }
+    NTS_LAUNCH_CHECK();
+  }
+
+  if (o->dst_local_id) {
+    hipLaunchKernelGGL(k_dst_local, dim3(gv), dim3(256), 0, st, o->destination, ctx->src_index,
+                       o->sizes, o->dst_local_id);
+    NTS_LAUNCH_CHECK();
+  }
+
+  // 4) relabel to local ids + forward weights
+  RelabelArgs ra{o->sample_ans,      o->edge_dst, o->destination, ctx->src_index,
+                 g->out_degree,      g->in_degree, o->column_offset, o->sizes,
+                 weight_type,        o->row_indices, o->edge_weight_forward,
+                 up ? t_up : nullptr, (up || csr) ? nullptr : o->sizes_host};
+  if (up) NTS_HIP_TRY(hipMemsetAsync(t_up, 0, up_n * sizeof(uint32_t), st));
+  if (coef)
+    hipLaunchKernelGGL(k_relabel<true>, dim3(ge), dim3(256), 0, st, ra);
+  else
+    hipLaunchKernelGGL(k_relabel<false>, dim3(ge), dim3(256), 0, st, ra);
+  NTS_LAUNCH_CHECK();
+  if (up) {
+    hipLaunchKernelGGL(k_up_weight, dim3(ge), dim3(256), 0, st, o->row_indices, o->edge_dst,
+                       o->column_offset, t_up, o->sizes, weight_type, o->edge_weight_forward,
+                       csr ? nullptr : o->sizes_host);
+    NTS_LAUNCH_CHECK();
+  }
+
+  // 5) CSR transpose (stable in edge order = ascending local dst): radix sort
+  // of (local src, edge id), then the CSR arrays.  Measured and dropped in
+  // round 4 (C2, per layer): fusing the relabel with the first pass's digit
+  // counts (20 vs 11 + 8 us: a tile per block is fewer threads for its random
+  // gathers), the CSR writes into the last pass (45 vs 16 + 20 us), and the
+  // later passes' tile offsets by a per-digit decoupled look-back (48-91 us)
+  // or counted by the pass before with atomics (65 vs 16 us).
+  if (csr) {
+    const uint32_t bits = ceil_log2((uint64_t)o->s_cap + 1);
+    if (bits >= 11 && bits <= 19) {
+      // one radix pass on the high H bits, then k_csr_bucket per 2^L sources
+      const uint32_t H = std::min(9u, bits - 6), L = bits - H;
+      const uint32_t* totals = nullptr;
+      const bool wpl = (weight_type != NTS_WEIGHT_NONE || coef) && o->edge_weight_backward;
+      RadixPayload pl;
+      pl.p1_in = o->edge_dst;
+      pl.p1_out = t_sdst;
+      if (wpl) {
+        pl.p2_in = reinterpret_cast<const uint32_t*>(o->edge_weight_forward);
+        pl.p2_out = t_swf;
+      }
+      // (the edge ids only where the CSR's edge-id map is asked for: GAT)
+      NTS_RET(radix_pass_pairs(o->row_indices, nullptr, t_skey, o->csr_edge_id ? t_seid : nullptr,
+                               o->sizes + 1, o->e_cap, L, H, t_sort, st, &totals, pl));
+      const uint32_t* swf = wpl ? t_swf : nullptr;
+#define NTS_CSR_BUCKET(LL)                                                                        \
+  hipLaunchKernelGGL(k_csr_bucket<LL>, dim3(1u << H), dim3(kCsrBucketThreads), 0, st, t_skey,   \
+                     t_seid, totals, t_sdst, swf, o->sizes, o->row_offset, o->column_indices,   \
+                     o->edge_weight_backward, o->csr_edge_id, o->sizes_host)
+      switch (L) {
+        case 6: NTS_CSR_BUCKET(6); break;
+        case 7: NTS_CSR_BUCKET(7); break;
+        case 8: NTS_CSR_BUCKET(8); break;
+        case 9: NTS_CSR_BUCKET(9); break;
+        default: NTS_CSR_BUCKET(10); break;
+      }
+#undef NTS_CSR_BUCKET
+      NTS_LAUNCH_CHECK();
+      return NTS_OK;
+    }
+    NTS_RET(radix_sort_pairs(o->row_indices, nullptr, t_skey, t_seid, o->sizes + 1, o->e_cap,
+                             bits, t_sort, st, ctx));
+    hipLaunchKernelGGL(k_csr_finalize, dim3(ge), dim3(256), 0, st, t_skey, t_seid, o->edge_dst,
+                       weight_type == NTS_WEIGHT_NONE && !coef ? nullptr : o->edge_weight_forward,
+                       o->sizes, o->row_offset, o->column_indices, o->edge_weight_backward,
+                       o->csr_edge_id, o->sizes_host);
+    NTS_LAUNCH_CHECK();
+  }
+  return NTS_OK;
+}
+
+
 static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanout, int layer,
                              uint64_t batch_seq, int rng_mode, int weight_type,
                              nts_sampcsc_dev* o, const float* edge_prob,
@@ -2218,16 +2488,7 @@ static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanou
   NTS_RET(ensure_vertices(ctx, V));
   const uint32_t nblk_marks = ceil_div(V, kMarkTile);
 
-  // scratch layout (u32 words)
   auto al = [](uint64_t x) { return (x + 63) / 64 * 64; };
-  const uint64_t scan_co = al(count_scan_tmp_elems(o->v_cap) + 1);
-  const uint64_t blk = al(nblk_marks + 1);
-  const uint64_t scan_blk = al(scan_tmp_elems<uint32_t>(nblk_marks) + 1);
-  const uint64_t sort_k = csr ? al(o->e_cap) : 0, sort_v = sort_k;
-  const uint64_t sort_p = csr ? 2 * al(o->e_cap) : 0;  // k_csr_bucket's payloads
-  const size_t sort_tmp =
-      csr ? std::max(radix_tmp_bytes(o->e_cap), radix_pass_tmp_bytes(o->e_cap)) : 0;
-  const uint64_t up_n = up ? al(o->s_cap) : 0;
   // MT19937 modes: per-dst info; the chunked resolver (fanout 1..32) adds the
   // draws' scan, chunk stats, the bulk word stream + raw blocks, the window
   // tables and the chunk entries
@@ -2261,23 +2522,11 @@ static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanou
   const uint64_t mt_misc_n = mt_chunked ? 64 : 0;
   const uint64_t mt_n = mt_info_n + mt_base_n + mt_stat_n + mt_win_n + mt_tab_n + mt_ent_n +
                         mt_misc_n;
-  const size_t need = (scan_co + blk + scan_blk + sort_k + sort_v + sort_p + up_n + mt_n) *
-                          sizeof(uint32_t) + sort_tmp + 256;
-  NTS_RET(ensure_scratch(ctx, need));
-  uint32_t* w0 = (uint32_t*)ctx->scratch;
-  uint32_t* t_scan_co = w0;
-  uint32_t* t_blk = t_scan_co + scan_co;
-  uint32_t* t_scan_blk = t_blk + blk;
-  uint32_t* t_skey = t_scan_blk + scan_blk;
-  uint32_t* t_seid = t_skey + sort_k;
-  uint32_t* t_sdst = t_seid + sort_v;
-  uint32_t* t_swf = t_sdst + sort_p / 2;
-  uint32_t* t_up = t_sdst + sort_p;
-  uint32_t* t_mt = t_up + up_n;  // MT19937 modes: per-dst MtInfo (16-byte aligned)
-  void* t_sort = (void*)(t_mt + mt_n);
+  LayerScratch ls;
+  NTS_RET(layer_scratch(ctx, o, csr, up, nblk_marks, mt_n, &ls));
+  uint32_t* t_mt = ls.t_mt;  // MT19937 modes: per-dst MtInfo (16-byte aligned)
 
   const uint32_t gv = std::max(1u, std::min(ceil_div(o->v_cap, 256), kMaxGrid));
-  const uint32_t ge = std::max(1u, std::min(ceil_div(o->e_cap, 256), kMaxGrid));
 
   // 1) per-dst counts -> column_offset, v_size, e_size (count + scan)
   {
@@ -2429,112 +2678,7 @@ static int sample_layer_impl(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanou
   NTS_LAUNCH_CHECK();
 
 frontier:
-  if (o->dst_local_id) {
-    hipLaunchKernelGGL(k_mark_dst, dim3(gv), dim3(256), 0, st, o->destination, o->sizes,
-                       ctx->marks);
-    NTS_LAUNCH_CHECK();
-  }
-
-  // 3) frontier: ascending compaction of the byte map — single pass up to
-  // kMarkFusedMaxTiles tiles (C2's 57), else count + write: at products' 598
-  // tiles the look-back chain took 23 us a layer against 5 + 9 for the pair
-  constexpr uint32_t kMarkFusedMaxTiles = 256;
-  if (nblk_marks <= kMarkFusedMaxTiles) {
-    NTS_RET(ensure_scan_state(ctx, scan1_state_elems((uint64_t)nblk_marks * 4096)));
-    hipLaunchKernelGGL(k_mark_fused, dim3(nblk_marks), dim3(kMarkThreads), 0, st, ctx->marks,
-                       nblk_marks, V, o->s_cap, o->source, ctx->src_index, o->sizes,
-                       ctx->scan_state, scan_next_epoch(ctx), scan_ticket(ctx));
-    NTS_LAUNCH_CHECK();
-  } else {
-    hipLaunchKernelGGL(k_mark_count, dim3(nblk_marks), dim3(kMarkThreads), 0, st, ctx->marks,
-                       t_blk);
-    NTS_LAUNCH_CHECK();
-    if (nblk_marks <= kMarkDirectTiles) {  // up to 8M vertices: no scan kernel
-      hipLaunchKernelGGL(k_mark_write<true>, dim3(nblk_marks), dim3(kMarkThreads), 0, st,
-                         ctx->marks, t_blk, nblk_marks, V, o->s_cap, o->source, ctx->src_index,
-                         o->sizes);
-    } else {
-      NTS_RET(scan_exclusive<uint32_t>(t_blk, t_blk, nullptr, nblk_marks, t_scan_blk, st));
-      hipLaunchKernelGGL(k_mark_write<false>, dim3(nblk_marks), dim3(kMarkThreads), 0, st,
-                         ctx->marks, t_blk, nblk_marks, V, o->s_cap, o->source, ctx->src_index,
-                         o->sizes);
-    }
-    NTS_LAUNCH_CHECK();
-  }
-
-  if (o->dst_local_id) {
-    hipLaunchKernelGGL(k_dst_local, dim3(gv), dim3(256), 0, st, o->destination, ctx->src_index,
-                       o->sizes, o->dst_local_id);
-    NTS_LAUNCH_CHECK();
-  }
-
-  // 4) relabel to local ids + forward weights
-  RelabelArgs ra{o->sample_ans,      o->edge_dst, o->destination, ctx->src_index,
-                 g->out_degree,      g->in_degree, o->column_offset, o->sizes,
-                 weight_type,        o->row_indices, o->edge_weight_forward,
-                 up ? t_up : nullptr, (up || csr) ? nullptr : o->sizes_host};
-  if (up) NTS_HIP_TRY(hipMemsetAsync(t_up, 0, up_n * sizeof(uint32_t), st));
-  if (coef)
-    hipLaunchKernelGGL(k_relabel<true>, dim3(ge), dim3(256), 0, st, ra);
-  else
-    hipLaunchKernelGGL(k_relabel<false>, dim3(ge), dim3(256), 0, st, ra);
-  NTS_LAUNCH_CHECK();
-  if (up) {
-    hipLaunchKernelGGL(k_up_weight, dim3(ge), dim3(256), 0, st, o->row_indices, o->edge_dst,
-                       o->column_offset, t_up, o->sizes, weight_type, o->edge_weight_forward,
-                       csr ? nullptr : o->sizes_host);
-    NTS_LAUNCH_CHECK();
-  }
-
-  // 5) CSR transpose (stable in edge order = ascending local dst): radix sort
-  // of (local src, edge id), then the CSR arrays.  Measured and dropped in
-  // round 4 (C2, per layer): fusing the relabel with the first pass's digit
-  // counts (20 vs 11 + 8 us: a tile per block is fewer threads for its random
-  // gathers), the CSR writes into the last pass (45 vs 16 + 20 us), and the
-  // later passes' tile offsets by a per-digit decoupled look-back (48-91 us)
-  // or counted by the pass before with atomics (65 vs 16 us).
-  if (csr) {
-    const uint32_t bits = ceil_log2((uint64_t)o->s_cap + 1);
-    if (bits >= 11 && bits <= 19) {
-      // one radix pass on the high H bits, then k_csr_bucket per 2^L sources
-      const uint32_t H = std::min(9u, bits - 6), L = bits - H;
-      const uint32_t* totals = nullptr;
-      const bool wpl = (weight_type != NTS_WEIGHT_NONE || coef) && o->edge_weight_backward;
-      RadixPayload pl;
-      pl.p1_in = o->edge_dst;
-      pl.p1_out = t_sdst;
-      if (wpl) {
-        pl.p2_in = reinterpret_cast<const uint32_t*>(o->edge_weight_forward);
-        pl.p2_out = t_swf;
-      }
-      // (the edge ids only where the CSR's edge-id map is asked for: GAT)
-      NTS_RET(radix_pass_pairs(o->row_indices, nullptr, t_skey, o->csr_edge_id ? t_seid : nullptr,
-                               o->sizes + 1, o->e_cap, L, H, t_sort, st, &totals, pl));
-      const uint32_t* swf = wpl ? t_swf : nullptr;
-#define NTS_CSR_BUCKET(LL)                                                                        \
-  hipLaunchKernelGGL(k_csr_bucket<LL>, dim3(1u << H), dim3(kCsrBucketThreads), 0, st, t_skey,   \
-                     t_seid, totals, t_sdst, swf, o->sizes, o->row_offset, o->column_indices,   \
-                     o->edge_weight_backward, o->csr_edge_id, o->sizes_host)
-      switch (L) {
-        case 6: NTS_CSR_BUCKET(6); break;
-        case 7: NTS_CSR_BUCKET(7); break;
-        case 8: NTS_CSR_BUCKET(8); break;
-        case 9: NTS_CSR_BUCKET(9); break;
-        default: NTS_CSR_BUCKET(10); break;
-      }
-#undef NTS_CSR_BUCKET
-      NTS_LAUNCH_CHECK();
-      return NTS_OK;
-    }
-    NTS_RET(radix_sort_pairs(o->row_indices, nullptr, t_skey, t_seid, o->sizes + 1, o->e_cap,
-                             bits, t_sort, st, ctx));
-    hipLaunchKernelGGL(k_csr_finalize, dim3(ge), dim3(256), 0, st, t_skey, t_seid, o->edge_dst,
-                       weight_type == NTS_WEIGHT_NONE && !coef ? nullptr : o->edge_weight_forward,
-                       o->sizes, o->row_offset, o->column_indices, o->edge_weight_backward,
-                       o->csr_edge_id, o->sizes_host);
-    NTS_LAUNCH_CHECK();
-  }
-  return NTS_OK;
+  return layer_tail(ctx, g, o, weight_type, up, coef, ls, st);
 }
 
 extern "C" int nts_hip_sample_layer(nts_hip_ctx* ctx, const nts_graph_dev* g, int fanout,
@@ -2612,4 +2756,84 @@ extern "C" int nts_hip_mt_rewind(nts_hip_ctx* ctx, const uint32_t* dev_state625)
   NTS_HIP_TRY(hipMemcpyAsync(ctx->mt_state, dev_state625, 625 * sizeof(uint32_t),
                              hipMemcpyDeviceToDevice, ctx->stream));
   return mt_ring_rebase(ctx);
+}
+
+extern "C" int nts_hip_random_walk(nts_hip_ctx* ctx, const nts_graph_dev* g, const uint32_t* roots,
+                                   const uint32_t* n_roots, uint32_t cap, int walk_len,
+                                   uint64_t batch_seq, uint32_t* out) {
+  NTS_CHECK_ARG(ctx && g, "NULL argument");
+  NTS_CHECK_ARG(g->column_offset && g->row_indices, "graph not on device");
+  NTS_CHECK_ARG(walk_len >= 0 && (uint32_t)walk_len < kWalkTag,
+                "walk_len must be in [0, 2^28) (the step shares its counter word with the tag)");
+  NTS_CHECK_ARG(cap == 0 || (roots && n_roots && out), "NULL argument");
+  NTS_CHECK_ARG(g->n_vertices <= 0xFFFFFFFFull, "vertex count exceeds uint32 ids");
+  if (cap == 0) return NTS_OK;
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  const uint32_t gs = std::max(1u, std::min(ceil_div(cap, 256), kMaxGrid));
+  hipLaunchKernelGGL(k_random_walk, dim3(gs), dim3(256), 0, ctx->stream, g->column_offset,
+                     g->row_indices, roots, n_roots, cap, (uint32_t)walk_len, ctx->seed, batch_seq,
+                     out);
+  NTS_LAUNCH_CHECK();
+  return NTS_OK;
+}
+
+extern "C" int nts_hip_induced_layer(nts_hip_ctx* ctx, const nts_graph_dev* g,
+                                     const uint32_t* set_ids, const uint32_t* set_size,
+                                     uint32_t set_cap, int weight_type, nts_sampcsc_dev* o) {
+  NTS_CHECK_ARG(ctx && g && o, "NULL argument");
+  NTS_CHECK_ARG(set_ids && set_size, "the vertex set is NULL");
+  NTS_CHECK_ARG(!o->omit_map, "an induced layer with omit_map (PD cache) is not supported");
+  NTS_CHECK_ARG(g->column_offset && g->row_indices, "graph not on device");
+  NTS_CHECK_ARG((o->destination || o->v_cap == 0) && o->v_size && o->column_offset &&
+                    o->row_indices && o->sample_ans && o->edge_dst && o->source && o->sizes,
+                "missing sampCSC buffer");
+  const bool up_degree = (weight_type & NTS_WEIGHT_UP_DEGREE) != 0;
+  weight_type &= 0xF;
+  NTS_CHECK_ARG(weight_type >= NTS_WEIGHT_SUM && weight_type <= NTS_WEIGHT_MEAN_SAMPLED,
+                "weight_type");
+  NTS_CHECK_ARG(weight_type == NTS_WEIGHT_NONE || (o->edge_weight_forward && g->in_degree &&
+                                                   g->out_degree),
+                "weights requested without buffers/degrees");
+  const bool up = up_degree && weight_type != NTS_WEIGHT_NONE;
+  NTS_CHECK_ARG(g->n_vertices <= 0xFFFFFFFFull, "vertex count exceeds uint32 ids");
+  const bool csr = o->row_offset != nullptr;
+  NTS_CHECK_ARG(!csr || o->column_indices, "CSR requested without column_indices");
+  NTS_HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const uint64_t V = g->n_vertices;
+  NTS_RET(ensure_vertices(ctx, V));
+  LayerScratch ls;
+  NTS_RET(layer_scratch(ctx, o, csr, up, ceil_div(V, kMarkTile), 0, &ls));
+
+  // a) the set into the byte map (all zeros here, the sampler's invariant)
+  const uint32_t gset = std::max(1u, std::min(ceil_div(set_cap, 256), kMaxGrid));
+  hipLaunchKernelGGL(k_set_mark, dim3(gset), dim3(256), 0, st, set_ids, set_size, set_cap, V,
+                     ctx->marks);
+  NTS_LAUNCH_CHECK();
+  // b) per-destination counts (left in column_offset), then the count scan:
+  // column_offset, sizes[0..1] and the overflow flag, as for a sampled layer
+  const uint32_t gs = std::max(1u, std::min(ceil_div(o->v_cap, kSelWaves), 4096u));
+  hipLaunchKernelGGL(k_induced<false>, dim3(gs), dim3(kSelThreads), 0, st, g->column_offset,
+                     g->row_indices, o->destination, o->v_size, o->v_cap, ctx->marks,
+                     o->column_offset, nullptr, o->e_cap, nullptr, nullptr);
+  NTS_LAUNCH_CHECK();
+  CountArgs ca{};
+  ca.v_in = o->v_size;
+  ca.v_cap = o->v_cap;
+  ca.sizes = o->sizes;
+  ca.e_cap = o->e_cap;
+  ca.counts = o->column_offset;
+  NTS_RET(count_scan(ctx, ca, o->column_offset, st));
+  // c) the kept edges, in CSC order
+  hipLaunchKernelGGL(k_induced<true>, dim3(gs), dim3(kSelThreads), 0, st, g->column_offset,
+                     g->row_indices, o->destination, o->v_size, o->v_cap, ctx->marks, nullptr,
+                     o->column_offset, o->e_cap, o->sample_ans, o->edge_dst);
+  NTS_LAUNCH_CHECK();
+  {  // an overflowed layer: the cut destinations as empty columns
+    const uint32_t gc = std::max(1u, std::min(ceil_div((uint64_t)o->v_cap + 1, 256), kMaxGrid));
+    hipLaunchKernelGGL(k_induced_clamp, dim3(gc), dim3(256), 0, st, o->column_offset, o->sizes);
+    NTS_LAUNCH_CHECK();
+  }
+  // d) frontier (the whole set), relabel + weights, CSR transpose
+  return layer_tail(ctx, g, o, weight_type, up, false, ls, st);
 }

@@ -73,6 +73,7 @@ EXPORTED = (
     "nts_hip_lp_batch", "nts_hip_lp_bce_fwd", "nts_hip_lp_bce_train",
     "nts_hip_lp_exclude_keys", "nts_hip_lp_mask_block", "nts_hip_lp_batch_filtered",
     "nts_hip_lp_rank",
+    "nts_hip_random_walk", "nts_hip_induced_layer",
 )
 NTS_NOT_CACHED = 0xFFFFFFFF
 
@@ -145,6 +146,10 @@ def lib() -> C.CDLL:
         "nts_hip_spmm_graph_fwd_coef_h": ([P, C.POINTER(GraphDev), P, U64, U64, I, I, P, U64, U32,
                                            P, U64], I),
         "nts_hip_weighted_keys": ([P, C.POINTER(GraphDev), P, P, U32, I, U64, P, P], I),
+        # subgraph sampling: roots, their device count, capacity, walk_len,
+        # batch_seq, out; and the set, its device count, capacity, weight_type, the block
+        "nts_hip_random_walk": ([P, C.POINTER(GraphDev), P, P, U32, I, U64, P], I),
+        "nts_hip_induced_layer": ([P, C.POINTER(GraphDev), P, P, U32, I, C.POINTER(SampCSCDev)], I),
         "nts_hip_gather_rows": ([P, P, U64, P, P, U32, U32, P, U64], I),
         "nts_hip_gather_labels": ([P, P, P, P, U32, P], I),
         "nts_hip_spmm_csc_fwd": ([P, P, P, P, P, U32, P, U64, P, U32, P, U64], I),

@@ -21,6 +21,7 @@ import ctypes as C
 import io
 import os
 import pathlib
+import re
 import sys
 import tempfile
 import zipfile
@@ -436,6 +437,15 @@ class InputInfo:
     # full-neighbour embeddings; LP_FULL_FILTER:1 drops a head's neighbours
     lp_full_eval: int = 0
     lp_full_filter: int = 0
+    # SUBGRAPH / SUBGRAPH_WALK / SUBGRAPH_EDGE_CAP (this build's keys, DESIGN
+    # §8w): 1 = a batch is one vertex set — its seeds and SUBGRAPH_WALK
+    # random-walk steps from each (default 0: the seeds alone) — and every layer
+    # runs on the subgraph it induces; FANOUT must be -1 per layer.
+    # SUBGRAPH_EDGE_CAP: the blocks' edge capacity (0 = the default bound).
+    # Philox-sampled GCN / GraphSAGE algorithms without PD cache
+    subgraph: int = 0
+    subgraph_walk: int = 0
+    subgraph_edge_cap: int = 0
     extra: dict = field(default_factory=dict)
 
     @property
@@ -444,7 +454,9 @@ class InputInfo:
 
     @property
     def fanout(self) -> list[int]:
-        return [int(x) for x in self.fanout_string.split("-") if x]
+        # entries separated by "-"; an entry may carry a sign of its own ("-1--1":
+        # two layers of all neighbours, what SUBGRAPH:1 takes)
+        return [int(x) for x in re.findall(r"(?:^|-)(-?\d+)", self.fanout_string.strip())]
 
     @classmethod
     def from_cfg(cls, path) -> "InputInfo":
@@ -483,6 +495,9 @@ class InputInfo:
             "LP_HOLDOUT_REMOVE": ("lp_holdout_remove", int),
             "LP_FULL_EVAL": ("lp_full_eval", int),
             "LP_FULL_FILTER": ("lp_full_filter", int),
+            "SUBGRAPH": ("subgraph", int),
+            "SUBGRAPH_WALK": ("subgraph_walk", int),
+            "SUBGRAPH_EDGE_CAP": ("subgraph_edge_cap", int),
         }
         for raw in pathlib.Path(path).read_text().splitlines():
             line = raw.strip()

@@ -115,6 +115,27 @@ class HipContext:
                                              ptr(out_offset)))
         return keys[:total]
 
+    def random_walk(self, graph: "DeviceGraph", roots, n_roots, walk_len: int, batch_seq: int,
+                    out):
+        """nts_hip_random_walk: `roots` int32 [cap] with its live
+        count in the device scalar `n_roots`; `out` int32 [cap * (walk_len + 1)],
+        walk-major, slots past the live count left as they are."""
+        g = graph.as_struct()
+        assert out.numel() >= roots.numel() * (walk_len + 1)
+        check(self.lib.nts_hip_random_walk(self.h, C.byref(g), ptr(roots), ptr(n_roots),
+                                           roots.numel(), walk_len, batch_seq, ptr(out)))
+
+    def induced_layer(self, graph: "DeviceGraph", lay: "LayerBuffers", set_ids, set_size,
+                      weight_type: int):
+        """nts_hip_induced_layer: the block the set induces on the
+        layer's destinations; `set_ids` int32 [cap] (any order, duplicates
+        allowed) with its live count in the device scalar `set_size`."""
+        g = graph.as_struct()
+        o = lay.as_struct()
+        check(self.lib.nts_hip_induced_layer(self.h, C.byref(g), ptr(set_ids), ptr(set_size),
+                                             set_ids.numel() if set_ids is not None else 0,
+                                             weight_type, C.byref(o)))
+
     # ---- movement / aggregation ------------------------------------------------
     def gather_rows(self, table, index, n_dev, n_cap, out):
         F = table.shape[1]

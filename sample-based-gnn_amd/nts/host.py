@@ -57,7 +57,7 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
                gat_feat_drop=0.0, gat_v2=False, shared_sampling=False, feature_f16=False,
                weighted_sampling=False, edge_weighted=False, batch_norm=False,
                batch_norm_eps=1e-5, batch_norm_momentum=0.1, neg_per_pos=1, lp_exclude="none",
-               filter_negatives=False):
+               filter_negatives=False, subgraph=False, subgraph_walk=0, subgraph_edge_cap=0):
     if weighted_sampling:  # neighbours drawn in proportion to the graph's edge_prob
         if int(rng_mode) in (_abi.NTS_RNG_MT19937_LEMIRE, _abi.NTS_RNG_MT19937_DIV):
             raise ValueError("weighted_sampling is not supported with an MT19937 rng_mode (it "
@@ -144,6 +144,10 @@ def gcn_config(layers, fanout, batch_size, learn_rate=0.01, weight_decay=1e-4, d
         c.lp_exclude = LP_EXCLUDE[lp_exclude]
     if filter_negatives:  # (the defaults leave both fields as constructed)
         c.lp_filter_neg = True
+    if subgraph:  # subgraph-sampled training; refusals: the driver.  Off: the
+        c.subgraph = True  # three fields stay as constructed
+        c.subgraph_walk = int(subgraph_walk)
+        c.subgraph_edge_cap = int(subgraph_edge_cap)
     return c
 
 

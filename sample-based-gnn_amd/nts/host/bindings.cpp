@@ -94,7 +94,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::class_<PySampler>(m, "FastSampler")
       .def(py::init([](std::shared_ptr<FullyRepGraph> g, const torch::Tensor& seeds, int layers,
                        int batch, std::vector<int> fanout, int rng_mode, uint64_t seed,
-                       bool csr, int pipeline, bool weighted, bool coef) {
+                       bool csr, int pipeline, bool weighted, bool coef, int subgraph_walk,
+                       uint64_t subgraph_edge_cap) {
              TORCH_CHECK(!(weighted || coef) || g->edge_prob.defined(),
                          "weighted / coef: the graph has no edge_prob");
              auto p = new PySampler();
@@ -103,7 +104,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              auto guard = p->cs->guard();
              std::vector<bool> c(layers, csr);
              p->s = std::make_unique<FastSampler>(g, to_ids(seeds), layers, batch, fanout, pipeline,
-                                                  c, true);
+                                                  c, true, false, false, subgraph_walk,
+                                                  subgraph_edge_cap);
              p->s->rng_mode = rng_mode;
              p->s->weighted = weighted;
              p->s->coef = coef;
@@ -112,7 +114,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("graph"), py::arg("seeds"), py::arg("layers"), py::arg("batch_size"),
            py::arg("fanout"), py::arg("rng_mode") = (int)NTS_RNG_PHILOX, py::arg("seed") = 2000,
            py::arg("csr") = true, py::arg("pipeline") = 1, py::arg("weighted") = false,
-           py::arg("coef") = false)
+           py::arg("coef") = false, py::arg("subgraph_walk") = -1,
+           py::arg("subgraph_edge_cap") = 0)
       // the split form (several slots in flight, finished in issue order)
       .def("issue",
            [](PySampler& p, int batch, int slot, WeightType w) {
@@ -293,7 +296,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("seed", &GCNConfig::seed)
       .def_readwrite("neg_per_pos", &GCNConfig::neg_per_pos)
       .def_readwrite("lp_exclude", &GCNConfig::lp_exclude)
-      .def_readwrite("lp_filter_neg", &GCNConfig::lp_filter_neg);
+      .def_readwrite("lp_filter_neg", &GCNConfig::lp_filter_neg)
+      .def_readwrite("subgraph", &GCNConfig::subgraph)
+      .def_readwrite("subgraph_walk", &GCNConfig::subgraph_walk)
+      .def_readwrite("subgraph_edge_cap", &GCNConfig::subgraph_edge_cap);
 
   // the constructor's option and shape rules on facts about its inputs: no
   // tensor, no device (RuntimeError with the rule's text as its first line)

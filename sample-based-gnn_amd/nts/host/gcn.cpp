@@ -107,7 +107,7 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   // rows, at the price of a GEMM over the src rows instead of the dst rows.
   const bool tf_ok = L >= 2 && !cfg.gat && !fcache && cfg.hip_gemm && cfg.fuse_activation &&
                      !cfg.pd_cache && !cfg.root_weight && !max_aggr() && !cfg.layer_norm &&
-                     !cfg.batch_norm;
+                     !cfg.batch_norm && !cfg.subgraph;
   // auto (-1): transform first where the first layer narrows the rows at
   // least 4x and its GEMMs run on the whole-row fp32-exact kernels
   // (csrc/gemmx3.hip, split-bf16) or the f16 pair tables (C2: 602 -> 128,
@@ -160,7 +160,9 @@ GCN_SAMPLE_ALLGPU_impl::GCN_SAMPLE_ALLGPU_impl(std::shared_ptr<FullyRepGraph> g,
   sampler = std::make_unique<FastSampler>(graph, train_nids, L, cfg.batch_size, cfg.fanout,
                                           nslots_, csr,
                                           sample_weight() != WeightType::None || cfg.edge_weighted,
-                                          cfg.gat || cfg.root_weight, max_aggr());
+                                          cfg.gat || cfg.root_weight, max_aggr(),
+                                          cfg.subgraph ? cfg.subgraph_walk : -1,
+                                          (uint64_t)cfg.subgraph_edge_cap);
   sampler->rng_mode = cfg.rng_mode;
   sampler->weighted = cfg.weighted_sampling;
   sampler->coef = cfg.edge_weighted;
@@ -824,7 +826,9 @@ std::unique_ptr<FastSampler> GCN_SAMPLE_ALLGPU_impl::eval_sampler(const std::vec
   auto s = std::make_unique<FastSampler>(graph, ids, L, batch, cfg.fanout, 1,
                                          std::vector<bool>(L, cfg.gat),
                                          sample_weight() != WeightType::None || cfg.edge_weighted,
-                                         cfg.gat || cfg.root_weight);
+                                         cfg.gat || cfg.root_weight, false,
+                                         cfg.subgraph ? cfg.subgraph_walk : -1,
+                                         (uint64_t)cfg.subgraph_edge_cap);
   s->rng_mode = cfg.rng_mode;
   s->weighted = cfg.weighted_sampling;
   s->coef = cfg.edge_weighted;

@@ -213,6 +213,25 @@ struct GCNConfig {
   // again, up to 16 times.
   int lp_exclude = 0;
   bool lp_filter_neg = false;
+  // Subgraph-sampled training (GraphSAINT node / random-walk
+  // samplers, random-partition Cluster-GCN): per batch ONE vertex set S is
+  // drawn — the batch's seeds and subgraph_walk steps of a random walk over
+  // in-neighbours from each — and every layer runs on the subgraph S induces
+  // (nts_hip_random_walk + nts_hip_induced_layer in every sampler the driver
+  // builds).  Layer 0 has the seeds as destinations and S as sources; layers
+  // >= 1 are the square block S x S.  The loss rows are the seeds.  Every
+  // fanout must be -1.  subgraph_edge_cap: the edge capacity of every block
+  // (0 = min(E, s_cap * 4 * ceil(E / V)) with s_cap = batch_size * (1 +
+  // subgraph_walk)); a block above it raises the capacity error.  weight_type
+  // (all four), up_degree and root_weight are taken; not with gat, aggregator =
+  // max, pd_cache, sample_gpu, an MT19937 rng_mode, NTS_RNG_PHILOX_SHARED,
+  // weighted_sampling, edge_weighted, cache_rate >= 0, layer_norm, batch_norm,
+  // multi_label, feature_f16, transform_first = 1 (-1 resolves to 0),
+  // pair_table > 0, fused_gather = false or deterministic_backward = false.
+  // LinkPredictor does not read these fields.
+  bool subgraph = false;
+  int subgraph_walk = 0;
+  int64_t subgraph_edge_cap = 0;
 };
 
 // Sampler-only throughput of the GPU sampler (SURVEY §8d "sampler-only"

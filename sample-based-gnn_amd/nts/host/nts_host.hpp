@@ -190,10 +190,12 @@ class SampledSubgraph {
   hipEvent_t sampled = nullptr;   // recorded after the last issue's kernels
   hipEvent_t consumed = nullptr;  // recorded by the trainer once it is done with the slot
   int pending_batch = 0;          // seeds of the issued, not yet finished batch
+  // subgraph_walk >= 0: the capacities of a subgraph-sampled batch
   SampledSubgraph(int device, int layers, const std::vector<int>& fanout, VertexId batch,
                   VertexId vertices, uint64_t edges, const std::vector<bool>& csr,
                   bool weights,
-                  bool merge = false, bool edge_ids = false);
+                  bool merge = false, bool edge_ids = false, int subgraph_walk = -1,
+                  uint64_t subgraph_edge_cap = 0);
   ~SampledSubgraph();
   SampledSubgraph(const SampledSubgraph&) = delete;
   SampledSubgraph& operator=(const SampledSubgraph&) = delete;
@@ -260,6 +262,15 @@ class FastSampler {
   bool coef = false;
   bool up_degree = false;  // UP_DEGREE: weights from each sampled layer's own degrees
   uint64_t batch_seq = 0;  // keys the PHILOX / PHILOX_SHARED streams (one per sampled batch)
+  // Subgraph mode, fixed at construction: subgraph_walk >= 0 and a
+  // batch is ONE vertex set S — its seeds and subgraph_walk random-walk steps
+  // from each (nts_hip_random_walk, keyed by batch_seq) — with every layer the
+  // block S induces (nts_hip_induced_layer): layer 0 seeds x S, layers >= 1
+  // S x S (each rebuilt: the slots' arrays are per layer).  Capacities: s_cap =
+  // min(V, batch (1 + walk)), v_cap of layers >= 1 the same, e_cap =
+  // subgraph_edge_cap (0: min(E, s_cap 4 ceil(E / V))).  rng_mode must be
+  // NTS_RNG_PHILOX; weighted, coef and omit_map are refused at issue.
+  int subgraph_walk() const { return subgraph_walk_; }
   // sample_gpu_fast_omit (core/ntsFastSampler.hpp:711-915): when set, the
   // bottom layer skips the dsts with omit_map[d] == omit_key
   const uint32_t* omit_map = nullptr;
@@ -273,7 +284,8 @@ class FastSampler {
   FastSampler(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& index, int layers,
               int batch_size, const std::vector<int>& fanout, int pipeline_num = 1,
               std::vector<bool> csr_layers = {}, bool weights = true,
-              bool merge_src_dst = false, bool edge_ids = false);
+              bool merge_src_dst = false, bool edge_ids = false, int subgraph_walk = -1,
+              uint64_t subgraph_edge_cap = 0);
   ~FastSampler();
 
   SampledSubgraph* sample_gpu_fast(int batch_size, int ssg_id, NtsStream& cs,
@@ -339,6 +351,10 @@ class FastSampler {
   void rerun_from(int ssg_id);
   torch::Tensor dev_nids_;  // device copy of sample_nids
   torch::Tensor dev_iota_;  // 0, 1, ..., batch_cap: device scalars for the layer-0 v_size
+  int subgraph_walk_ = -1;  // >= 0: subgraph mode
+  torch::Tensor dev_walkn_;             // k (1 + walk), k = 0..batch_cap: the walk set's live count
+  std::vector<torch::Tensor> walk_;     // per slot: the walks' ids [batch_cap (1 + walk)]
+  void enqueue_subgraph(int ssg_id, const IssueRec& r);
   VertexId batch_cap_ = 0;
 };
 

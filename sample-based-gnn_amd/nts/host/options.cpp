@@ -177,6 +177,40 @@ void check_driver_options(const GCNConfig& cfg, const DriverInputs& in) {
                                                          ": ", cfg.layer_size[l], ")")});
     refuse("batch_norm is not supported with ", rows);
   }
+  // subgraph-sampled training
+  if (cfg.subgraph) {
+    bool all_fanout = true;
+    for (int f : cfg.fanout) all_fanout &= f == -1;
+    refuse("subgraph ",
+           {{!all_fanout, "needs every fanout = -1 (all induced neighbours; other values are "
+                          "kept for a fanout-capped meaning)"},
+            {cfg.subgraph_walk < 0 || cfg.subgraph_walk > 64,
+             c10::str("needs subgraph_walk in [0, 64], got ", cfg.subgraph_walk)},
+            {cfg.subgraph_edge_cap < 0 || cfg.subgraph_edge_cap > 0xFFFFFFFFll,
+             c10::str("needs subgraph_edge_cap in [0, 2^32) (0 = the default), got ",
+                      cfg.subgraph_edge_cap)},
+            {cfg.gat, "is not supported with gat (GCN / GraphSAGE layers only)"},
+            {max, "is not supported with aggregator = max"},
+            {cfg.pd_cache, "is not supported with pd_cache"},
+            {cfg.sample_gpu, "is not supported with sample_gpu (the reference's mt19937 stream)"},
+            {mt, "is not supported with an MT19937 rng_mode (the walks draw from a Philox stream "
+                 "of their own)"},
+            {cfg.rng_mode == NTS_RNG_PHILOX_SHARED,
+             "is not supported with rng_mode NTS_RNG_PHILOX_SHARED (shared_sampling): an induced "
+             "block selects nothing"},
+            {cfg.weighted_sampling, "is not supported with weighted_sampling (the walks are uniform)"},
+            {cfg.edge_weighted, "is not supported with edge_weighted"},
+            {!(cfg.cache_rate < 0.0), "is not supported with cache_rate >= 0"},
+            {cfg.layer_norm, "is not supported with layer_norm"},
+            {cfg.batch_norm, "is not supported with batch_norm"},
+            {cfg.multi_label, "is not supported with multi_label"},
+            {cfg.feature_f16, "is not supported with feature_f16"},
+            {cfg.transform_first == 1,
+             "is not supported with transform_first = 1 (aggregate-first only)"},
+            {cfg.pair_table > 0, "is not supported with pair_table > 0"},
+            {!cfg.fused_gather, "is not supported with fused_gather = false"},
+            {!cfg.deterministic_backward, "is not supported with deterministic_backward = false"}});
+  }
 }
 
 void check_link_pred_options(const GCNConfig& cfg, const LinkPredInputs& in) {

@@ -140,8 +140,22 @@ std::vector<VertexId> sampCSC::host_u32(const torch::Tensor& t, size_t n) const 
 
 static std::vector<std::array<uint64_t, 3>> layer_caps(VertexId batch,
                                                        const std::vector<int>& fanout,
-                                                       VertexId V, uint64_t E, bool merge) {
+                                                       VertexId V, uint64_t E, bool merge,
+                                                       int subgraph_walk = -1,
+                                                       uint64_t subgraph_edge_cap = 0) {
   std::vector<std::array<uint64_t, 3>> caps;
+  if (subgraph_walk >= 0) {
+    // one vertex set per batch: the seeds and `walk` steps from each; every
+    // block holds at most e_cap of the graph's edges (the default's factor 4
+    // over the mean degree is a guess)
+    const uint64_t s = std::min<uint64_t>((uint64_t)batch * (1 + (uint64_t)subgraph_walk), V);
+    const uint64_t mean_deg = V ? (E + V - 1) / V : 0;
+    const uint64_t e = subgraph_edge_cap ? std::min<uint64_t>(subgraph_edge_cap, E)
+                                         : std::min<uint64_t>(E, s * 4 * mean_deg);
+    TORCH_CHECK(e <= 0xFFFFFFFFull, "sampled layer exceeds 2^32 edges");
+    for (size_t l = 0; l < fanout.size(); ++l) caps.push_back({l == 0 ? (uint64_t)batch : s, e, s});
+    return caps;
+  }
   uint64_t v = batch;
   for (int f : fanout) {
     uint64_t e = f < 0 ? E : std::min<uint64_t>(v * (uint64_t)f, E);
@@ -156,9 +170,9 @@ static std::vector<std::array<uint64_t, 3>> layer_caps(VertexId batch,
 SampledSubgraph::SampledSubgraph(int device, int layers_, const std::vector<int>& fanout_,
                                  VertexId batch, VertexId vertices, uint64_t edges,
                                  const std::vector<bool>& csr, bool weights, bool merge,
-                                 bool edge_ids)
+                                 bool edge_ids, int subgraph_walk, uint64_t subgraph_edge_cap)
     : layers(layers_), fanout(fanout_) {
-  auto caps = layer_caps(batch, fanout, vertices, edges, merge);
+  auto caps = layer_caps(batch, fanout, vertices, edges, merge, subgraph_walk, subgraph_edge_cap);
   for (int l = 0; l < layers; ++l) {
     bool c = csr.empty() ? true : (bool)csr[l];
     sampled_sgs.push_back(new sampCSC(device, (VertexId)caps[l][0], (VertexId)caps[l][1],
@@ -192,14 +206,26 @@ SampledSubgraph::~SampledSubgraph() {
 FastSampler::FastSampler(std::shared_ptr<FullyRepGraph> g, const std::vector<VertexId>& index,
                          int layers, int batch_size, const std::vector<int>& fanout_,
                          int pipeline_num, std::vector<bool> csr_layers, bool weights,
-                         bool merge_src_dst, bool edge_ids)
-    : whole_graph(g), layer(layers), fanout(fanout_), batch_cap_((VertexId)batch_size) {
+                         bool merge_src_dst, bool edge_ids, int subgraph_walk,
+                         uint64_t subgraph_edge_cap)
+    : whole_graph(g), layer(layers), fanout(fanout_), batch_cap_((VertexId)batch_size),
+      subgraph_walk_(subgraph_walk) {
   TORCH_CHECK((int)fanout.size() == layers, "fanout size != layers");
   if (pipeline_num < 1) pipeline_num = 1;
+  if (subgraph_walk_ >= 0)
+    for (int f : fanout)
+      TORCH_CHECK(f == -1, "subgraph mode needs every fanout = -1 (all induced neighbours)");
   for (int i = 0; i < pipeline_num; ++i)
     ssgs.push_back(new SampledSubgraph(g->device, layers, fanout, batch_cap_, g->global_vertices,
                                        g->global_edges, csr_layers, weights, merge_src_dst,
-                                       edge_ids));
+                                       edge_ids, subgraph_walk, subgraph_edge_cap));
+  if (subgraph_walk_ > 0) {  // (walk 0: the set is the seeds themselves, no walk buffer)
+    const int64_t w1 = 1 + (int64_t)subgraph_walk_;
+    dev_walkn_ = torch::arange((int64_t)batch_cap_ + 1, u32_opts(g->device)) * w1;
+    for (int i = 0; i < pipeline_num; ++i)
+      walk_.push_back(torch::empty({std::max<int64_t>((int64_t)batch_cap_ * w1, 1)},
+                                   u32_opts(g->device)));
+  }
   ssg = ssgs[0];
   recs_.resize(ssgs.size());
   set_sample_nids(index);
@@ -264,6 +290,9 @@ void FastSampler::issue_gpu_sample(int batch_size, int ssg_id, NtsStream& cs, We
     // the generator state before the batch's first layer (stream order)
     NTS_CALL(nts_hip_mt_checkpoint, cs.ctx(), dptr<uint32_t>(r.mt_ckpt));
   }
+  TORCH_CHECK(subgraph_walk_ < 0 || (rng_mode == NTS_RNG_PHILOX && !weighted && !coef && !omit_map),
+              "subgraph mode draws its walks from a Philox stream of its own and selects nothing: "
+              "rng_mode NTS_RNG_PHILOX without weighted, coef or omit_map");
   issued_.push_back(ssg_id);
   enqueue_layers(ssg_id, r);
   if (host_profile()) fprintf(stderr, "[host] issue total: %.1f us\n", (now_s() - t0) * 1e6);
@@ -284,6 +313,7 @@ void FastSampler::issue_gpu_sample_dev(const torch::Tensor& dest, const torch::T
   TORCH_CHECK(!is_mt_mode(rng_mode), "issue_gpu_sample_dev: the MT19937 modes replay a host-ordered "
               "stream (Philox and Philox-shared only)");
   TORCH_CHECK(!omit_map, "issue_gpu_sample_dev is not supported with omit_map");
+  TORCH_CHECK(subgraph_walk_ < 0, "issue_gpu_sample_dev is not supported in subgraph mode");
   TORCH_CHECK(ssg_id >= 0 && ssg_id < (int)ssgs.size(), "ssg_id out of range");
   TORCH_CHECK(dest.defined() && dest.is_cuda() && dest.scalar_type() == torch::kInt32 &&
                   dest.is_contiguous() && v_size_dev.defined() && v_size_dev.is_cuda() &&
@@ -323,6 +353,7 @@ void FastSampler::issue_gpu_sample_dev(const torch::Tensor& dest, const torch::T
 
 // the batch's sampling kernels (every layer) on the record's stream
 void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
+  if (subgraph_walk_ >= 0) return enqueue_subgraph(ssg_id, r);
   ssg = ssgs[ssg_id];
   NtsStream& cs = *r.cs;
   hipStream_t st = (hipStream_t)cs.stream();
@@ -394,6 +425,62 @@ void FastSampler::enqueue_layers(int ssg_id, const IssueRec& r) {
   hip_rt(hipEventRecord(ssg->sampled, st), "hipEventRecord");
 }
 
+// Subgraph mode: the batch's vertex set S (the seeds, and the walks from them)
+// and the blocks it induces, every kernel on the record's stream.  Layer 0:
+// destinations the seeds, set = the walks' ids (duplicates and all); layers
+// >= 1: destinations and set both the previous layer's source, which is S.
+void FastSampler::enqueue_subgraph(int ssg_id, const IssueRec& r) {
+  ssg = ssgs[ssg_id];
+  NtsStream& cs = *r.cs;
+  hipStream_t st = (hipStream_t)cs.stream();
+  const nts_graph_dev g = whole_graph->dev();
+  const VertexId actual = r.actual;
+  const VertexId* dst = dptr<VertexId>(dev_nids_) + r.offset;
+  const VertexId* vsz = dptr<VertexId>(dev_iota_) + actual;
+  const VertexId* set = dst;
+  const VertexId* set_n = vsz;
+  uint32_t set_cap = batch_cap_;
+  if (subgraph_walk_ > 0) {
+    VertexId* w = dptr<VertexId>(walk_[ssg_id]);
+    NTS_CALL(nts_hip_random_walk, cs.ctx(), &g, dst, vsz, batch_cap_, subgraph_walk_, r.batch_seq, w);
+    set = w;
+    set_n = dptr<VertexId>(dev_walkn_) + actual;
+    set_cap = (uint32_t)walk_[ssg_id].numel();
+  }
+  for (int l = 0; l < layer; ++l) {
+    sampCSC* s = ssg->sampled_sgs[l];
+    nts_sampcsc_dev o{};
+    o.v_cap = s->v_cap;
+    o.e_cap = s->e_cap;
+    o.s_cap = s->s_cap;
+    o.destination = dst;
+    o.v_size = vsz;
+    o.column_offset = dptr<uint32_t>(s->column_offset);
+    o.row_indices = dptr<uint32_t>(s->row_indices);
+    o.sample_ans = dptr<uint32_t>(s->sample_ans);
+    o.edge_dst = dptr<uint32_t>(s->edge_dst);
+    o.source = dptr<uint32_t>(s->source);
+    o.edge_weight_forward = r.wt == NTS_WEIGHT_NONE ? nullptr : dptr<float>(s->edge_weight_forward);
+    o.row_offset = s->has_csr ? dptr<uint32_t>(s->row_offset) : nullptr;
+    o.column_indices = s->has_csr ? dptr<uint32_t>(s->column_indices) : nullptr;
+    o.edge_weight_backward =
+        (s->has_csr && r.wt != NTS_WEIGHT_NONE) ? dptr<float>(s->edge_weight_backward) : nullptr;
+    o.sizes = dptr<uint32_t>(s->sizes);
+    o.dst_local_id = dptr<uint32_t>(s->dst_local_id);  // undefined (NULL) unless merged
+    o.csr_edge_id = dptr<uint32_t>(s->csr_edge_id);
+    o.sizes_host = ssg->host_sizes_dev + 4 * l;
+    NTS_CALL(nts_hip_induced_layer, cs.ctx(), &g, set, set_n, set_cap, r.wt, &o);
+    if (l == 0)
+      s->destination = dev_nids_.narrow(0, r.offset, std::max<int64_t>(actual, 0));
+    else
+      s->destination = ssg->sampled_sgs[l - 1]->source;
+    dst = set = o.source;
+    vsz = set_n = o.sizes + 2;
+    set_cap = o.s_cap;
+  }
+  hip_rt(hipEventRecord(ssg->sampled, st), "hipEventRecord");
+}
+
 void FastSampler::set_mt_budget_scale(NtsStream& cs, double scale) {
   mt_budget_ = scale;
   NTS_CALL(nts_hip_mt_budget_scale, cs.ctx(), scale);
@@ -449,7 +536,8 @@ SampledSubgraph* FastSampler::finish_gpu_sample(int ssg_id) {
     s->v_size = (VertexId)hs[4 * l];
     s->e_size = (VertexId)hs[4 * l + 1];
     s->src_size = (VertexId)hs[4 * l + 2];
-    TORCH_CHECK(hs[4 * l + 3] == 0, "sampled layer ", l, " exceeded its capacity");
+    TORCH_CHECK(hs[4 * l + 3] == 0, "sampled layer ", l, " exceeded its capacity",
+                subgraph_walk_ >= 0 ? " (subgraph_edge_cap)" : "");
     sampled_edges += s->e_size;
   }
   all_time += now_s() - t0;

@@ -87,6 +87,17 @@ full-neighbour embeddings (no sampling, no negatives drawn); LP_FULL_FILTER:1
 drops a head's own neighbours from its candidates.  LABEL_FILE and MASK_FILE
 are not used.
 
+SUBGRAPH:1 (Philox-sampled GCN / GraphSAGE algorithms without PD cache; DESIGN
+§8w): subgraph-sampled training.  A batch is one vertex set — its BATCH_SIZE
+seeds and SUBGRAPH_WALK:n (default 0) random-walk steps over in-neighbours from
+each — and every layer runs on the subgraph the set induces; the loss rows are
+the seeds.  FANOUT must be -1 for every layer.  SUBGRAPH_EDGE_CAP:n bounds the
+edges of a block (default min(E, 4 |S|max ceil(E / V))); a block above it stops
+the job with the capacity error.  UP_DEGREE:1 gives the subgraph-degree
+normalisation of Cluster-GCN / GraphSAINT; ROOT_WEIGHT:1 is taken.  Not with
+AGGREGATOR:max, SAMPLE_SHARED, SAMPLE_WEIGHTED, EDGE_WEIGHT_AGG, LAYER_NORM,
+BATCH_NORM, MULTI_LABEL or FEATURE_F16.
+
 Usage:  python -m nts.run path/to/job.cfg [--epochs N] [--device D] [--json out.json]
 File paths inside the cfg are resolved relative to the cfg's directory.
 """
@@ -159,6 +170,7 @@ def refuse_cfg(info: dataloader.InputInfo):
     model, _, rng, _, place = ALGORITHMS.get(info.algorithm.upper(), (None,) * 5)
     gat, gcn, pd, mt = model == "gat", model == "gcn", place == "pd", rng == "mt"
     agg, weighted = bool(info.edge_weight_agg), bool(info.sample_weighted)
+    sub = bool(info.subgraph)
     rows = (
         (model is None,
          f"not supported by this build (supported: {', '.join(sorted(ALGORITHMS))})"),
@@ -221,6 +233,29 @@ def refuse_cfg(info: dataloader.InputInfo):
          "node classifiers' exact pass)"),
         (bool(info.lp_full_filter),
          f"LP_FULL_FILTER is not supported outside ALGORITHM:{LINK_PRED}"),
+        (sub and any(f != -1 for f in info.fanout),
+         "SUBGRAPH needs FANOUT -1 for every layer (all induced neighbours)"),
+        (sub and not 0 <= info.subgraph_walk <= 64,
+         f"SUBGRAPH_WALK must be in [0, 64], got {info.subgraph_walk}"),
+        (sub and info.subgraph_edge_cap < 0,
+         f"SUBGRAPH_EDGE_CAP must be >= 0, got {info.subgraph_edge_cap}"),
+        (sub and gat, "SUBGRAPH is not supported with GAT algorithms (GCN / GraphSAGE layers only)"),
+        (sub and info.aggregator == "max", "SUBGRAPH is not supported with AGGREGATOR:max"),
+        (sub and pd, "SUBGRAPH is not supported with the PD-cache algorithms"),
+        (sub and place == "sample_gpu",
+         "SUBGRAPH is not supported with GCNSAMPLEGPU (the reference's mt19937 stream)"),
+        (sub and mt,
+         "SUBGRAPH is not supported with the mt19937-stream algorithms (Philox-sampled "
+         "algorithms only)"),
+        (sub and bool(info.sample_shared), "SUBGRAPH is not supported with SAMPLE_SHARED:1"),
+        (sub and weighted, "SUBGRAPH is not supported with SAMPLE_WEIGHTED:1"),
+        (sub and agg, "SUBGRAPH is not supported with EDGE_WEIGHT_AGG:1"),
+        (sub and bool(info.layer_norm), "SUBGRAPH is not supported with LAYER_NORM:1"),
+        (sub and bool(info.batch_norm), "SUBGRAPH is not supported with BATCH_NORM:1"),
+        (sub and bool(info.multi_label), "SUBGRAPH is not supported with MULTI_LABEL:1"),
+        (sub and bool(info.feature_f16), "SUBGRAPH is not supported with FEATURE_F16:1"),
+        (not sub and bool(info.subgraph_walk or info.subgraph_edge_cap),
+         "SUBGRAPH_WALK / SUBGRAPH_EDGE_CAP are not supported without SUBGRAPH:1"),
     )
     for hit, text in rows:
         if hit:
@@ -252,7 +287,8 @@ def build_driver(E, info: dataloader.InputInfo, G, feat, labels, train_ids, devi
         shared_sampling=bool(info.sample_shared), feature_f16=bool(info.feature_f16),
         weighted_sampling=bool(info.sample_weighted),
         edge_weighted=bool(info.edge_weight_agg), seed=info.seed,
-        batch_norm=bool(info.batch_norm))
+        batch_norm=bool(info.batch_norm), subgraph=bool(info.subgraph),
+        subgraph_walk=info.subgraph_walk, subgraph_edge_cap=info.subgraph_edge_cap)
     return E.GCN_SAMPLE_ALLGPU_impl(G, feat, labels, train_ids, cfg, comm)
 
 
